@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — DDP iterations/sec of the batched HS-DDP solve (BASELINE.json metric) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong] [--dump-outputs DIR] [--full]
 
 Workload (config.workload), weak scaling (default): BASELINE.json configs[2] — Mini-Cheetah whole-body, N=200 knots as 4 contact
 phases (1111 -> 0110 -> 1001 -> 0110, dt=0.01), an ensemble of 4096 initial states PER GPU, synthetic inputs,
@@ -12,6 +12,12 @@ A "step" = one DDP iteration (cost, LQ approximation, regularised Riccati sweep,
 MultiPhaseDDP.cpp:277-387) of the whole batch.  Inputs are resident in HBM before the timed region.  One process per GPU; the only
 collective is the RCCL all-gather of the per-problem results (cafe-mpc_amd/launch.py).  Started without a launcher, `--gpus N`
 starts its own N ranks (before touching the GPU) and fails loudly if the node has fewer GPUs.
+A plain run sets up, warms up, times the solve and prints the line (headline figure, per-rank figures, the roofline of the timed launches).
+`--full` adds the legs that take runs of their own: the CPU baseline on the oracle and its parity sample against the timed run, the host-boundary
+leg and the batch-1 latency / MPC-tick probes (`--no-cpu-baseline`, `--no-latency` drop some of them again).
+`--dump-outputs DIR`: what the timed solve handed back, as DIR/<name>.npy (fp64): the per-problem result struct of every problem and the
+trajectories (XBAR, UBAR, Y) and feedback gains (K) of every phase for a fixed, seeded sample of the problems, so that two builds can be
+compared output for output (the inputs are seeded: the same arguments give the same inputs).
 """
 import argparse
 import ctypes
@@ -230,6 +236,28 @@ def host_boundary_probe(s, x0, opt, dt_resident):
     return out
 
 
+DUMP_SAMPLE = 32              # problems whose trajectories --dump-outputs writes (a fixed, seeded choice)
+DUMP_SEED = 20241220
+DUMP_BUDGET = 60 * 2 ** 20     # bytes: the whole dump stays under 64 MB
+
+
+def dump_outputs(pkg, out_dir, s, res_all):
+    """What a caller of the timed solve receives: the gathered result struct of every problem (one file per field) and, for a seeded sample of
+    this rank's problems, XBAR / UBAR / Y / K of every phase ([sample, knots, ...], numpy order).  fp64 throughout."""
+    os.makedirs(out_dir, exist_ok=True)
+    for j, name in enumerate(pkg.launch.RESULT_FIELDS):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(res_all[:, j], dtype=np.float64))
+    fields = [(i, f) for i in range(len(s.phases)) for f in ("XBAR", "UBAR", "Y", "K")]
+    per_problem = sum(s.field(i, f, 0, 1).nbytes for i, f in fields)
+    n = int(min(DUMP_SAMPLE, s.batch, max(1, (DUMP_BUDGET - res_all.nbytes) // max(per_problem, 1))))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(s.batch, size=n, replace=False))
+    np.save(os.path.join(out_dir, "sample_problems.npy"), idx.astype(np.float64))
+    for i, f in fields:
+        a = np.concatenate([s.field(i, f, int(b), 1) for b in idx])
+        if a.size:
+            np.save(os.path.join(out_dir, f"{f}_phase{i:02d}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -239,8 +267,11 @@ def main():
     ap.add_argument("--strong", action="store_true", help="fixed total work: config 4 (barrel roll, 8 phases, N=350), 8192 problems split over the ranks")
     ap.add_argument("--hkd", choices=["f32", "f64"], default=None, help="BASELINE config 5 instead: HKD 24/24/0, N=200 bound-gait schedule, 16384 problems per GPU, "
                                                                              "on an fp32 handle (fp32 LQ records + fp32 MFMA sweep) or an fp64 one")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline (and no parity sample)")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: no host-boundary leg, no latency / MPC-tick probes")
+    ap.add_argument("--full", action="store_true", help="also the legs that take runs of their own: CPU baseline + parity sample, host boundary, "
+                                                        "latency / MPC-tick probes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed solve computed as DIR/<name>.npy (fp64)")
     args = ap.parse_args()
 
     pkg = ge.load_package()
@@ -361,15 +392,17 @@ def main():
         line["collectives"] = "rccl" if dist is not None else "none (single process)"
         line["per_rank"] = {"solve_ms": [round(float(v), 3) for v in per_rank[:, 0]], "iterations": [int(v) for v in per_rank[:, 1]], "ls_trials": [int(v) for v in per_rank[:, 2]],
                             "iter_imbalance": float(per_rank[:, 1].max() / max(per_rank[:, 1].mean(), 1.0)), "time_imbalance": float(per_rank[:, 0].max() / max(per_rank[:, 0].mean(), 1e-9))}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:               # before any --full leg: host_boundary solves again on this handle
+            dump_outputs(pkg, args.dump_outputs, s, res_all)
+        if world == 1 and args.full and not args.no_cpu_baseline:
             so, line["cpu_baseline"] = cpu_baseline(pkg, phases_fn, x0_fn, opt_fn, args.steps)
             if so is not None:
                 if args.hkd != "f32":          # (an fp32 handle is outside the fp64 tolerances: tests/test_gpu_parity.py holds it to its own)
                     line["parity_sample"] = parity_sample(s, so, len(s.phases))
                 so.close()
-        if world == 1 and not args.no_latency:
+        if world == 1 and args.full and not args.no_latency:
             line["host_boundary"] = host_boundary_probe(s, x0, opt, dt)
-        if world == 1 and not args.no_latency and not args.strong and not args.hkd:
+        if world == 1 and args.full and not args.no_latency and not args.strong and not args.hkd:
             line["latency"] = latency_probe(pkg, args.steps)
             line["latency"]["mpc_tick"] = mpc_tick_probe(pkg)
             line["latency"]["mpc_tick_cpp"] = mpc_tick_cpp_probe()

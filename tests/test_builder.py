@@ -39,12 +39,13 @@ def test_mhpc_problem_from_shipped_bound_gait():
     assert abs(d[0].reb_torque.delta - 1.0) < 1e-15 and abs(d[0].reb_grf.eps - 0.05) < 1e-15 and d[0].al_td.sigma == 20.0
     assert list(d[0].q)[:6] == [0, 0, 10, 1, 2, 2] and abs(d[3].r[0] - 0.01) < 1e-15 and d[3].dt == 0.05
     assert np.allclose(phases[0]["bufs"]["yr"][0], [0, 0, 22.5] * 4)       # GRF reference of the first sample
-    if os.path.isdir("/root/reference/Reference/Data"):        # the trimmed fixture reproduces what the full tree gives
-        p2, i2, _ = builder.build_from_tree("/root/reference")
-        assert i2["horizons"] == info["horizons"]
-        for a, b in zip(phases, p2):
-            for k in a["bufs"]:
-                assert np.array_equal(a["bufs"][k], b["bufs"][k]), k
+    # the trimmed fixture reproduces what the full tree gives (stored by tests/golden/make_gait_fixture.py)
+    full = np.load(os.path.join(ROOT, "tests", "golden", "full_tree_bound_bufs.npz"))
+    assert list(full["horizons"]) == info["horizons"]
+    assert len(full.files) == 1 + sum(len(p["bufs"]) for p in phases)
+    for i, a in enumerate(phases):
+        for k in a["bufs"]:
+            assert np.array_equal(a["bufs"][k], full[f"p{i}_{k}"]), (i, k)
 
 
 @pytest.mark.parametrize("gait", ["bound", "trot/dynfeas"])

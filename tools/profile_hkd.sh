@@ -8,8 +8,8 @@ set -e -o pipefail
 TAG=${1:-r03x}; PREC=${2:-f32}
 OUT=gpurun_out/$TAG; mkdir -p $OUT profiles
 export TMPDIR=/tmp
-python3 bench.py --hkd $PREC --steps 20 --warmup 5 --no-latency > $OUT/hkd${PREC}_bench_steps20.json 2> $OUT/hkd${PREC}_bench20.err
-python3 bench.py --hkd $PREC --steps 10 --warmup 2 --no-latency > $OUT/hkd${PREC}_bench_steps10.json 2> $OUT/hkd${PREC}_bench10.err
+python3 bench.py --full --hkd $PREC --steps 20 --warmup 5 --no-latency > $OUT/hkd${PREC}_bench_steps20.json 2> $OUT/hkd${PREC}_bench20.err
+python3 bench.py --full --hkd $PREC --steps 10 --warmup 2 --no-latency > $OUT/hkd${PREC}_bench_steps10.json 2> $OUT/hkd${PREC}_bench10.err
 rocprofv3 --kernel-trace --stats -d $OUT/hkd${PREC}_stats -o run --output-format csv -- python3 bench.py --hkd $PREC --steps 20 --warmup 5 --no-cpu-baseline --no-latency > $OUT/hkd${PREC}_stats.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/hkd${PREC}_pmc_fetch -o run --output-format csv -- python3 bench.py --hkd $PREC --steps 8 --warmup 0 --batch 2048 --no-cpu-baseline --no-latency > $OUT/hkd${PREC}_pmc_fetch_bench.json 2> $OUT/hkd${PREC}_pmc_fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/hkd${PREC}_pmc_write -o run --output-format csv -- python3 bench.py --hkd $PREC --steps 8 --warmup 0 --batch 2048 --no-cpu-baseline --no-latency > $OUT/hkd${PREC}_pmc_write_bench.json 2> $OUT/hkd${PREC}_pmc_write.err

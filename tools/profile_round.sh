@@ -10,8 +10,8 @@ TAG=${1:-r02x}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT profiles
 export TMPDIR=/tmp
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench20.err
-python3 bench.py > $OUT/bench_steps10.json 2> $OUT/bench10.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench20.err
+python3 bench.py --full > $OUT/bench_steps10.json 2> $OUT/bench10.err
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-latency > $OUT/stats.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o run --output-format csv -- python3 bench.py --steps 12 --warmup 0 --batch 512 --no-cpu-baseline --no-latency > $OUT/pmc_fetch_bench.json 2> $OUT/pmc_fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o run --output-format csv -- python3 bench.py --steps 12 --warmup 0 --batch 512 --no-cpu-baseline --no-latency > $OUT/pmc_write_bench.json 2> $OUT/pmc_write.err
