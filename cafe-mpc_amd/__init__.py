@@ -12,6 +12,8 @@ from . import _abi
 from ._abi import Option, mhpc_ddp_setting, Solver, MODEL_WB, MODEL_SRB, MODEL_HKD, PREC_F64, PREC_F32  # noqa: F401
 from . import problems  # noqa: F401
 from . import launch  # noqa: F401
+from . import ensemble  # noqa: F401
+from .ensemble import ScheduleEnsemble, select_rows  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
 HIP_LIB_PATH = _os.path.join(_HERE, "libhsddp_hip.so")

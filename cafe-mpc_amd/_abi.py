@@ -134,6 +134,25 @@ def bind(lib):
     return lib
 
 
+# include/hsddp_ensemble.h: a header of its own (hsddp.h and EXPORTS above are the single-handle ABI both libraries export)
+ENSEMBLE_EXPORTS = ["hsddp_ensemble_create", "hsddp_ensemble_destroy", "hsddp_ensemble_solve", "hsddp_ensemble_select",
+                    "hsddp_ensemble_export_mpc_commands"]
+
+
+def bind_ensemble(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_ensemble.h.  Raises if the library lacks any of them."""
+    missing = [s for s in ENSEMBLE_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the ensemble entry points {missing}")
+    H = C.c_void_p
+    lib.hsddp_ensemble_create.argtypes = [C.POINTER(H), C.c_int, C.POINTER(H)]
+    lib.hsddp_ensemble_destroy.argtypes = [H]
+    lib.hsddp_ensemble_destroy.restype = None
+    lib.hsddp_ensemble_solve.argtypes = [H, C.POINTER(Option), C.c_float, C.c_int]
+    lib.hsddp_ensemble_select.argtypes = [H, C.POINTER(Option), IP, C.c_void_p]
+    lib.hsddp_ensemble_export_mpc_commands.argtypes = [H, C.c_int, IP, IP, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
+    return lib
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 

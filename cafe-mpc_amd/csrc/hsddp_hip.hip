@@ -6,13 +6,16 @@
 // kernel launches; the host reads back one 16-byte activity counter per line-search launch and per inner iteration to stop early.
 // Kernels: wb_knot.hpp (one wavefront per knot), sweep.hpp (one workgroup per problem).
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 #include <cmath>
 #include "hsddp.h"
+#include "hsddp_ensemble.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -20,6 +23,7 @@
 #include "srb_knot.hpp"
 #include "hkd_knot.hpp"
 #include "sweep.hpp"
+#include "ensemble.hpp"
 
 using namespace hs;
 
@@ -28,7 +32,9 @@ using namespace hs;
 #define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return HSDDP_ENODEV; } } while (0)
 
 struct SlotArrays { double *cost, *dsq, *ming, *maxh; };
-static long long g_dev_allocs = 0;      // device allocations made by this library (hsddp_debug_malloc_count: the MPC-tick test watches it)
+// device allocations made by this library (hsddp_debug_malloc_count: the MPC-tick test watches it); atomic: hsddp_ensemble_solve runs the
+// candidates' solves on one host thread each, and a first solve allocates its history buffers
+static std::atomic<long long> g_dev_allocs{0};
 #define hipMalloc(...) (++g_dev_allocs, hipMalloc(__VA_ARGS__))
 #ifdef ROLL_WPE
 #define ROLL_ATTR __attribute__((amdgpu_waves_per_eu(ROLL_WPE, ROLL_WPE)))
@@ -1295,6 +1301,176 @@ int hsddp_reset_kernel_times(hsddp_handle_t* h) {
     if (!h) return HSDDP_EINVAL;
     for (auto& v : h->kms) v = 0; for (auto& v : h->kcnt) v = 0;
     HIPCK(hipSetDevice(h->device)); HIPCK(hipMemset(h->d_units, 0, 8 * sizeof(unsigned long long)));
+    return HSDDP_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ schedule-candidate ensembles (hsddp_ensemble.h)
+}  // extern "C"
+struct hsddp_ensemble {
+    int S = 0, device = 0, batch = 0;                 // batch: common batch of the candidates, 0 when they differ (select refuses then)
+    std::vector<hsddp_handle*> c;
+    hipStream_t stream = nullptr;
+    const ProbState** d_st = nullptr;                 // [S] each candidate's ProbState array
+    const PhaseDev** d_ph = nullptr;                  // [S] each candidate's descriptor table
+    int* d_map = nullptr; int map_cap = 0;            // [2][S][map_cap] step -> (phase, k) of each candidate's leading whole-body control knots
+    std::vector<int> h_map; std::vector<int> map_n;   // what d_map holds; valid entries per candidate
+    float* d_status = nullptr; int st_stride = 0;     // [S][st_stride] status times of the last export that passed them
+    int* d_winner = nullptr; hsddp_info_t* d_best = nullptr;      // [batch]
+    int* d_pairs = nullptr; int pairs_cap = 0;        // [2][pairs_cap] (candidate, problem) of an export
+    unsigned int* d_out = nullptr; size_t out_cap = 0;   // staging of a host-destination export
+    std::vector<int> h_pairs; std::vector<float> h_status;
+};
+
+// step -> (phase, k) of the leading whole-body control knots of a handle (MHPCProblemData::get_index, as hsddp_export_mpc_command walks them)
+static int ens_step_map(const hsddp_handle* h, int cap, int* ph, int* kk) {
+    int n = 0;
+    for (int i = 0; i < h->nph && n < cap; i++) {
+        if (h->ph[i].model != HSDDP_MODEL_WB) break;
+        for (int k = 0; k < h->ph[i].h && n < cap; k++) { ph[n] = i; kk[n] = k; n++; }
+    }
+    return n;
+}
+
+static void ens_free(hsddp_ensemble* e) {
+    if (!e) return;
+    hipSetDevice(e->device);
+    if (e->stream) hipStreamSynchronize(e->stream);
+    void* p[] = {(void*)e->d_st, (void*)e->d_ph, e->d_map, e->d_status, e->d_winner, e->d_best, e->d_pairs, e->d_out};
+    for (void* q : p) if (q) hipFree(q);
+    if (e->stream) hipStreamDestroy(e->stream);
+    delete e;
+}
+
+// the ensemble's kernels read what the candidates' streams wrote
+static int ens_sync_candidates(hsddp_ensemble* e) {
+    for (auto* h : e->c) HIPCK(hipStreamSynchronize(h->stream));
+    return HSDDP_OK;
+}
+
+extern "C" {
+
+int hsddp_ensemble_create(hsddp_ensemble_t** out, int n_cands, hsddp_handle_t* const* cands) {
+    if (!out || n_cands <= 0 || !cands) return HSDDP_EINVAL;
+    for (int i = 0; i < n_cands; i++) if (!cands[i]) return HSDDP_EINVAL;
+    const hsddp_handle* c0 = cands[0];
+    double t0 = 0; for (int p = 0; p < c0->nph; p++) t0 += c0->ph[p].h * c0->ph[p].dt;
+    bool same_batch = true;
+    for (int i = 1; i < n_cands; i++) {
+        const hsddp_handle* h = cands[i];
+        double t = 0; for (int p = 0; p < h->nph; p++) t += h->ph[p].h * h->ph[p].dt;
+        if (h->device != c0->device || h->ph[0].n != c0->ph[0].n || fabs(t - t0) > 1e-9) return HSDDP_EINVAL;
+        same_batch = same_batch && h->batch == c0->batch;
+    }
+    HIPCK(hipSetDevice(c0->device));
+    hsddp_ensemble* e = new hsddp_ensemble();
+    e->S = n_cands; e->device = c0->device; e->batch = same_batch ? c0->batch : 0;
+    e->c.assign(cands, cands + n_cands);
+    for (auto* h : e->c) { int wb = 0; for (int p = 0; p < h->nph && h->ph[p].model == HSDDP_MODEL_WB; p++) wb += h->ph[p].h; e->map_cap = std::max(e->map_cap, wb); }
+    e->map_cap = std::max(e->map_cap, 1);
+    for (auto* h : e->c) e->st_stride = std::max(e->st_stride, 4 * h->nph_cap);
+#define ENS_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); ens_free(e); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
+    ENS_CK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    ENS_CK(hipMalloc((void**)&e->d_st, n_cands * sizeof(ProbState*)));
+    ENS_CK(hipMalloc((void**)&e->d_ph, n_cands * sizeof(PhaseDev*)));
+    ENS_CK(hipMalloc((void**)&e->d_map, 2 * (size_t)n_cands * e->map_cap * sizeof(int)));
+    ENS_CK(hipMalloc((void**)&e->d_status, (size_t)n_cands * e->st_stride * sizeof(float)));
+    if (e->batch) { ENS_CK(hipMalloc((void**)&e->d_winner, e->batch * sizeof(int))); ENS_CK(hipMalloc((void**)&e->d_best, e->batch * sizeof(hsddp_info_t))); }
+    std::vector<const ProbState*> st; std::vector<const PhaseDev*> ph;
+    for (auto* h : e->c) { st.push_back(h->d_st); ph.push_back(h->d_ph); }
+    e->h_map.assign(2 * (size_t)n_cands * e->map_cap, 0); e->map_n.assign(n_cands, 0);
+    for (int i = 0; i < n_cands; i++) e->map_n[i] = ens_step_map(e->c[i], e->map_cap, &e->h_map[(size_t)i * e->map_cap], &e->h_map[((size_t)n_cands + i) * e->map_cap]);
+    e->h_status.assign((size_t)n_cands * e->st_stride, 0.f);
+    ENS_CK(hipMemcpy(e->d_st, st.data(), st.size() * sizeof(ProbState*), hipMemcpyHostToDevice));
+    ENS_CK(hipMemcpy(e->d_ph, ph.data(), ph.size() * sizeof(PhaseDev*), hipMemcpyHostToDevice));
+    ENS_CK(hipMemcpy(e->d_map, e->h_map.data(), e->h_map.size() * sizeof(int), hipMemcpyHostToDevice));
+#undef ENS_CK
+    *out = e; return HSDDP_OK;
+}
+
+void hsddp_ensemble_destroy(hsddp_ensemble_t* e) { ens_free(e); }
+
+int hsddp_ensemble_solve(hsddp_ensemble_t* e, const hsddp_option_t* opt, float max_cputime_ms, int concurrent) {
+    if (!e || !opt) return HSDDP_EINVAL;
+    std::vector<int> rc(e->S, HSDDP_OK);
+    if (!concurrent || e->S == 1) {
+        for (int i = 0; i < e->S; i++) rc[i] = hsddp_solve(e->c[i], opt, max_cputime_ms);
+    } else {
+        // one host thread per candidate, each on its handle's own stream (the handles share no host or device state: DESIGN 7)
+        std::vector<std::thread> th;
+        for (int i = 0; i < e->S; i++)
+            th.emplace_back([e, opt, max_cputime_ms, &rc, i]() {
+                hipError_t d = hipSetDevice(e->device);
+                rc[i] = d != hipSuccess ? HSDDP_ENODEV : hsddp_solve(e->c[i], opt, max_cputime_ms);
+            });
+        for (auto& t : th) t.join();
+    }
+    for (int r : rc) if (r) return r;
+    return HSDDP_OK;
+}
+
+int hsddp_ensemble_select(hsddp_ensemble_t* e, const hsddp_option_t* opt, int* winner, hsddp_info_t* best) {
+    if (!e || !opt || !winner) return HSDDP_EINVAL;
+    if (!e->batch) return HSDDP_EINVAL;
+    for (auto* h : e->c) if (h->batch != e->batch) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(e->device));
+    int rc = ens_sync_candidates(e); if (rc) return rc;
+    hipLaunchKernelGGL(k_ens_select, dim3((e->batch + 255) / 256), dim3(256), 0, e->stream, e->d_st, e->S, e->batch,
+                       opt->dynamics_feas_thresh, opt->tconstr_thresh, opt->pconstr_thresh, e->d_winner, best ? e->d_best : nullptr);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(winner, e->d_winner, e->batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    if (best) HIPCK(hipMemcpyAsync(best, e->d_best, e->batch * sizeof(hsddp_info_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCK(hipStreamSynchronize(e->stream));
+    return HSDDP_OK;
+}
+
+int hsddp_ensemble_export_mpc_commands(hsddp_ensemble_t* e, int n, const int* cand, const int* problem, int n_steps, double mpc_time, double dt,
+                                       const float* const* status_times, unsigned int* out, int dst_device) {
+    if (!e || n < 0 || (n > 0 && (!cand || !problem || !out)) || n_steps <= 0 || n_steps > e->map_cap) return HSDDP_EINVAL;
+    if (n == 0) return HSDDP_OK;
+    // the step maps (re-derived: a candidate's own hsddp_reconfigure may have moved its phases; uploaded only when they changed)
+    bool map_changed = false;
+    for (int i = 0; i < e->S; i++) {
+        std::vector<int> p(e->map_cap), k(e->map_cap);
+        const int m = ens_step_map(e->c[i], e->map_cap, p.data(), k.data());
+        int* hp = &e->h_map[(size_t)i * e->map_cap]; int* hk = &e->h_map[((size_t)e->S + i) * e->map_cap];
+        if (m != e->map_n[i] || memcmp(hp, p.data(), m * sizeof(int)) || memcmp(hk, k.data(), m * sizeof(int))) {
+            memcpy(hp, p.data(), m * sizeof(int)); memcpy(hk, k.data(), m * sizeof(int)); e->map_n[i] = m; map_changed = true;
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        if (cand[i] < 0 || cand[i] >= e->S || problem[i] < 0 || problem[i] >= e->c[cand[i]]->batch) return HSDDP_EINVAL;
+        if (e->map_n[cand[i]] < n_steps) return HSDDP_EINVAL;      // the first n_steps control knots are not all whole-body knots
+    }
+    HIPCK(hipSetDevice(e->device));
+    int rc = ens_sync_candidates(e); if (rc) return rc;
+    const size_t row = 1 + (size_t)n_steps * HSDDP_CMD_WORDS_PER_STEP;
+    // staging kept across calls (a warm tick makes no device allocation): grown on demand, freed by hsddp_ensemble_destroy
+    if (n > e->pairs_cap) {
+        HIPCK(hipStreamSynchronize(e->stream));
+        if (e->d_pairs) HIPCK(hipFree(e->d_pairs)); e->d_pairs = nullptr; e->pairs_cap = 0;
+        HIPCK(hipMalloc((void**)&e->d_pairs, 2 * (size_t)n * sizeof(int))); e->pairs_cap = n;
+    }
+    if (!dst_device && row * n > e->out_cap) {
+        HIPCK(hipStreamSynchronize(e->stream));
+        if (e->d_out) HIPCK(hipFree(e->d_out)); e->d_out = nullptr; e->out_cap = 0;
+        HIPCK(hipMalloc((void**)&e->d_out, row * n * sizeof(unsigned int))); e->out_cap = row * n;
+    }
+    e->h_pairs.resize(2 * (size_t)n);
+    memcpy(e->h_pairs.data(), cand, n * sizeof(int)); memcpy(e->h_pairs.data() + n, problem, n * sizeof(int));
+    HIPCK(hipMemcpyAsync(e->d_pairs, e->h_pairs.data(), 2 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    if (map_changed) HIPCK(hipMemcpyAsync(e->d_map, e->h_map.data(), e->h_map.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    if (status_times) {
+        std::fill(e->h_status.begin(), e->h_status.end(), 0.f);
+        for (int i = 0; i < e->S; i++) if (status_times[i]) memcpy(&e->h_status[(size_t)i * e->st_stride], status_times[i], (size_t)e->c[i]->nph * 4 * sizeof(float));
+        HIPCK(hipMemcpyAsync(e->d_status, e->h_status.data(), e->h_status.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    }
+    unsigned int* dst = dst_device ? out : e->d_out;
+    hipLaunchKernelGGL(k_ens_pack, dim3(n_steps, n), dim3(256), 0, e->stream, e->d_ph, e->d_map, e->d_map + (size_t)e->S * e->map_cap, e->map_cap,
+                       e->d_pairs, e->d_pairs + n, n_steps, mpc_time, dt, status_times ? e->d_status : nullptr, e->st_stride, dst);
+    HIPCK(hipGetLastError());
+    if (!dst_device) HIPCK(hipMemcpyAsync(out, e->d_out, row * n * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
+    HIPCK(hipStreamSynchronize(e->stream));
     return HSDDP_OK;
 }
 

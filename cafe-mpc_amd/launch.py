@@ -147,3 +147,71 @@ def gather_scalars(dist, values, device):
     out = [torch.empty_like(t) for _ in range(dist.get_world_size())]
     dist.all_gather(out, t)
     return np.concatenate([o.cpu().numpy() for o in out])
+
+
+# --------------------------------------------------------------------------------------------- schedule-candidate ensembles
+def shard_candidates(S, B, world, rank):
+    """The rank's share of an S-candidate x B-state ensemble: shard() of the candidate-major grid of S*B (candidate, state) units, cut into
+    per-candidate segments [(cand, first_state, count), ...] in grid order.  Ranks get equal work (within one unit) also when S < world, and
+    every segment is one schedule: one handle of `count` states drawn from the x0 stream at `first_state`."""
+    first, count = shard(S * B, world, rank)
+    segs, u, end = [], first, first + count
+    while u < end:
+        c, s = divmod(u, B)
+        n = min(B - s, end - u)
+        segs.append((c, s, n)); u += n
+    return segs
+
+
+def tagged_rows(segs, rows):
+    """Result rows of a rank's segments (concatenated in segment order) with the (cand, state) of every row appended: [n, 10]."""
+    tags = np.concatenate([np.stack([np.full(n, c), np.arange(s, s + n)], axis=1) for c, s, n in segs]) if segs else np.zeros((0, 2))
+    return np.hstack([np.asarray(rows, dtype=np.float64).reshape(-1, 8), tags.astype(np.float64)])
+
+
+def ensemble_rows(gathered, S, B):
+    """Gathered tagged rows -> [S, B, 8]; every (cand, state) exactly once."""
+    out = np.full((S, B, 8), np.nan)
+    seen = np.zeros((S, B), dtype=np.int64)
+    c, s = gathered[:, 8].astype(np.int64), gathered[:, 9].astype(np.int64)
+    out[c, s] = gathered[:, :8]
+    np.add.at(seen, (c, s), 1)
+    if not (seen == 1).all():
+        raise RuntimeError("gathered ensemble rows do not cover every (candidate, state) exactly once")
+    return out
+
+
+def owned_winners(S, B, world, rank, winner):
+    """The winners `rank` holds, in state order: [(state, segment index, problem inside the segment's handle), ...]."""
+    out = []
+    for i, (c, s, n) in enumerate(shard_candidates(S, B, world, rank)):
+        out += [(st, i, st - s) for st in range(s, s + n) if int(winner[st]) == c]
+    return sorted(out)
+
+
+def gather_policies(dist, S, B, winner, pack, row_words, device):
+    """Second gather of the ensemble path: every rank packs the winners it owns (pack(list of (segment, problem)) -> [k, row_words] int32
+    torch tensor on `device`, or a numpy array of 32-bit words), one padded all-gather, reassembled to [B, row_words] uint32 in state
+    order.  The per-rank counts follow from the winners every rank already has: no size exchange."""
+    import torch
+    world = 1 if dist is None else dist.get_world_size()
+    rank = 0 if dist is None else dist.get_rank()
+    owned = [owned_winners(S, B, world, r, winner) for r in range(world)]
+    mine = owned[rank]
+    rows = pack([(i, p) for _, i, p in mine])
+    rows = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(rows).view(np.int32))
+    rows = rows.to(device)
+    assert tuple(rows.shape) == (len(mine), row_words)
+    out = np.zeros((B, row_words), dtype=np.uint32)
+    if dist is None:
+        out[[st for st, _, _ in mine]] = rows.cpu().numpy().view(np.uint32)
+        return out
+    nmax = max(len(o) for o in owned)
+    pad = torch.zeros((max(nmax, 1), row_words), dtype=torch.int32, device=device)
+    pad[:len(mine)] = rows
+    parts = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(parts, pad)
+    for o, p in zip(owned, parts):
+        if o:
+            out[[st for st, _, _ in o]] = p[:len(o)].cpu().numpy().view(np.uint32)
+    return out

@@ -176,6 +176,26 @@ def wb_trot_problem(schedule=((1, 1, 1, 1), (0, 1, 1, 0), (1, 0, 0, 1), (0, 1, 1
     return phases
 
 
+TROT_TIMINGS = ((50, 50, 50, 50), (40, 60, 40, 60), (60, 40, 60, 40), (45, 55, 55, 45))
+
+
+def wb_trot_timing_candidates(total=200, **kw):
+    """Schedule candidates of a gait-selection tick: the trot of wb_trot_problem with four timings of its phases over the SAME total horizon
+    (the switching times as the decision, the idea of BarrelRollTO.cpp:70-81).  For totals other than 200 the knots are scaled
+    proportionally (largest remainders, every phase keeps at least one knot), so the sum stays `total`.  Returns one phase list per timing."""
+    out = []
+    for t in TROT_TIMINGS:
+        exact = [v * total / 200.0 for v in t]
+        h = [max(1, int(np.floor(x))) for x in exact]
+        order = sorted(range(4), key=lambda i: -(exact[i] - np.floor(exact[i])))
+        i = 0
+        while sum(h) < total:
+            h[order[i % 4]] += 1; i += 1
+        while sum(h) > total:
+            j = max(range(4), key=lambda i: h[i]); h[j] -= 1
+        out.append(wb_trot_problem(horizons=tuple(h), **kw))
+    return out
+
 def wb_stance_problem(horizon=50, dt=0.01, contact=(1, 1, 1, 1), ubar_mode="gravity_comp"):
     """Config 1 of BASELINE.json: WB, one phase N=50, constant stance reference."""
     h = horizon
