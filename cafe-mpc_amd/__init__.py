@@ -14,6 +14,7 @@ from . import problems  # noqa: F401
 from . import launch  # noqa: F401
 from . import ensemble  # noqa: F401
 from .ensemble import ScheduleEnsemble, select_rows  # noqa: F401
+from . import hkd_command  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
 HIP_LIB_PATH = _os.path.join(_HERE, "libhsddp_hip.so")

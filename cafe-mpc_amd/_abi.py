@@ -153,6 +153,23 @@ def bind_ensemble(lib):
     lib.hsddp_ensemble_export_mpc_commands.argtypes = [H, C.c_int, IP, IP, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
     return lib
 
+
+# include/hsddp_hkd.h: the HKD-MPC command export (libhsddp_hip.so only; EXPORTS above stay the ABI both libraries share)
+HKD_EXPORTS = ["hsddp_export_hkd_commands", "hsddp_export_hkd_command"]
+HKD_CMD_WORDS = 1954      # HSDDP_HKD_CMD_WORDS
+HKD_MAX_STEPS = 10        # HSDDP_HKD_MAX_STEPS
+
+
+def bind_hkd(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_hkd.h.  Raises if the library lacks any of them."""
+    missing = [s for s in HKD_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the HKD export entry points {missing}")
+    H = C.c_void_p
+    lib.hsddp_export_hkd_commands.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.hsddp_export_hkd_command.argtypes = [H, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    return lib
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -317,6 +334,50 @@ class Solver:
             seg = words[pos:pos + n_steps * w]; pos += n_steps * w
             out[name] = seg.view(np.float32 if kind == "f" else np.int32).reshape(n_steps, w).copy()
         return out
+
+    def _hkd_args(self, nb, n_steps, status_times, pf):
+        if not getattr(self, "_hkd_bound", False):
+            bind_hkd(self.lib); self._hkd_bound = True      # raises on a library without include/hsddp_hkd.h (the CPU checker)
+        st = None
+        if status_times is not None:
+            st = np.ascontiguousarray(status_times, dtype=np.float64); assert st.shape == (len(self.phases), 4)
+        pfa = None
+        if pf is not None:
+            pfa = np.ascontiguousarray(np.broadcast_to(np.asarray(pf, dtype=np.float32), (nb, 12)))
+        return st, pfa
+
+    def export_hkd_command(self, problem=0, n_steps=9, mpc_time=0.0, dt=0.01, status_times=None, pf=None):
+        """hkd_command_lcmt content (HKDMPC.cpp:207-297, include/hsddp_hkd.h) of one problem: a dict of decoded fields + the raw words.
+        status_times: n_phases x 4 contact durations (HKDProblemData describe()["status_durations"]); pf: the current footholds (12)."""
+        from . import hkd_command
+        st, pfa = self._hkd_args(1, n_steps, status_times, pf)
+        w = np.zeros(HKD_CMD_WORDS, dtype=np.uint32)
+        rc = self.lib.hsddp_export_hkd_command(self.h, problem, n_steps, float(mpc_time), float(dt), st.ctypes.data if st is not None else None,
+                                               pfa.ctypes.data if pfa is not None else None, w.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_export_hkd_command failed: {rc}")
+        return hkd_command.decode(w)
+
+    def export_hkd_commands(self, b0=0, nb=None, n_steps=9, mpc_time=0.0, dt=0.01, status_times=None, pf=None, out=None):
+        """Rows [nb, HKD_CMD_WORDS] (uint32) of problems b0 .. b0+nb-1 in one launch.  pf: [nb, 12] current footholds or None.  out: None (numpy
+        result), a contiguous torch tensor of nb x HKD_CMD_WORDS 32-bit elements on the handle's device, or a raw device address of that many
+        words (written in place and returned)."""
+        nb = self.batch - b0 if nb is None else nb
+        st, pfa = self._hkd_args(nb, n_steps, status_times, pf)
+        args = (self.h, b0, nb, n_steps, float(mpc_time), float(dt), st.ctypes.data if st is not None else None, pfa.ctypes.data if pfa is not None else None)
+        if out is None:
+            rows = np.zeros((nb, HKD_CMD_WORDS), dtype=np.uint32)
+            rc = self.lib.hsddp_export_hkd_commands(*args, rows.ctypes.data, 0)
+        elif isinstance(out, int):
+            rows = out
+            rc = self.lib.hsddp_export_hkd_commands(*args, out, 1)
+        else:
+            assert out.device.type == "cuda" and out.is_contiguous() and out.element_size() == 4 and out.numel() == nb * HKD_CMD_WORDS
+            rows = out
+            rc = self.lib.hsddp_export_hkd_commands(*args, out.data_ptr(), 1)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_export_hkd_commands failed: {rc}")
+        return rows
 
     def get_history(self, problem=0, cap=4096):
         """MultiPhaseDDP::get_solver_info(cost, dyn_feas, eqn_feas, ineq_feas) (MultiPhaseDDP.h:85): the four float history buffers."""

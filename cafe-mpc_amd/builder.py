@@ -370,23 +370,24 @@ class HKDProblemData:
         self.plan = F32(plan_duration); self.dt = F32(dt_sim); self.nsteps = int(nsteps_between_mpc); self.dt_mpc = F32(self.dt * F32(nsteps_between_mpc))
         ref.initialize(self.plan)
         self.start, self.end, self.h, self.contact, self.reach_end, self.has_td, self.shooting, self.uid = [], [], [], [], [], [], [], []
+        self.dur = []                                                          # contact_durations: status_dur at each phase's start (:27-38, 57, 63, 162-167)
         self._next_uid = 0
         self.ref_start = F32(0)                                                # QuadReference::get_start_time
         self.dup_td = 0                                                        # phases that would carry TWO TouchDownConstraint objects in the reference (see update)
         t = F32(0); start = F32(0)
-        c_prev = ref.contact_at(t)
+        c_prev = ref.contact_at(t); d_prev = ref.at(t)["status_dur"].copy()
         while _approx_leq(t, self.plan):                                       # HKDProblem.cpp:34-63
             c_cur = ref.contact_at(t)
             if (c_cur != c_prev).any() or (float(t) > float(self.plan) or _approx_eq(t, self.plan)):
                 end = t
-                self._push_phase(start, end, int(round(float(F32(end - start) / self.dt))), c_prev.copy(), shooting=1)      # reach_end: (c != c).any() = false (:51)
-                c_prev = c_cur; start = end
+                self._push_phase(start, end, int(round(float(F32(end - start) / self.dt))), c_prev.copy(), d_prev, shooting=1)      # reach_end: (c != c).any() = false (:51)
+                c_prev = c_cur; d_prev = ref.at(t)["status_dur"].copy(); start = end
             t = F32(t + self.dt)
         for i in range(len(self.h)):                                           # add_tconstr_one_phase for every phase at initialisation (:93)
             self.has_td[i] = bool(self._touchdown(i).any())
 
-    def _push_phase(self, start, end, h, contact, shooting):
-        self.start.append(F32(start)); self.end.append(F32(end)); self.h.append(h); self.contact.append(contact); self.reach_end.append(False)
+    def _push_phase(self, start, end, h, contact, dur, shooting):
+        self.start.append(F32(start)); self.end.append(F32(end)); self.h.append(h); self.contact.append(contact); self.reach_end.append(False); self.dur.append(np.asarray(dur, dtype=np.float64))
         self.has_td.append(False); self.shooting.append(shooting); self.uid.append(self._next_uid); self._next_uid += 1
 
     def _next_contact(self, i):                                                # add_tconstr_one_phase (:283-291)
@@ -415,7 +416,7 @@ class HKDProblemData:
             new_start = self.ref_start; new_end = F32(new_start + self.plan)
             self.start[0] = F32(self.start[0] + self.dt)                       # front end (:131-146)
             if _approx_leq(self.end[0], new_start):
-                for lst in (self.start, self.end, self.h, self.contact, self.reach_end, self.has_td, self.shooting, self.uid):
+                for lst in (self.start, self.end, self.h, self.contact, self.dur, self.reach_end, self.has_td, self.shooting, self.uid):
                     lst.pop(0)
             else:
                 popped[self.uid[0]] += 1; self.h[0] -= 1; self.start[0] = new_start
@@ -423,7 +424,8 @@ class HKDProblemData:
             change = bool((new_contact != self.contact[-1]).any())
             if change and self.reach_end[-1]:
                 nstart = self.end[-1]
-                self._push_phase(nstart, new_end, int(round(float(F32(new_end - nstart) / self.dt))), new_contact.copy(), shooting=0)      # no update_SS_config yet
+                self._push_phase(nstart, new_end, int(round(float(F32(new_end - nstart) / self.dt))), new_contact.copy(),
+                                 ref.at(F32(new_end - new_start))["status_dur"].copy(), shooting=0)      # no update_SS_config yet
                 popped[self.uid[-1]] = 0; pushed[self.uid[-1]] = 0
             else:
                 self.end[-1] = new_end; self.h[-1] += 1
@@ -469,7 +471,8 @@ class HKDProblemData:
             ph["Xbar"] = X0; ph["Ubar"] = np.zeros((h, 24)); ph["uid"] = self.uid[i]
             phases.append(ph)
         info = dict(start_times=[float(s) for s in self.start], end_times=[float(e) for e in self.end], horizons=list(self.h), contacts=[np.asarray(c).tolist() for c in self.contact],
-                    shooting=list(self.shooting), has_td=list(self.has_td), x0=phases[0]["Xbar"][0].copy())
+                    shooting=list(self.shooting), has_td=list(self.has_td), x0=phases[0]["Xbar"][0].copy(),
+                    status_durations=np.array(self.dur, dtype=np.float64).reshape(n, 4))
         return phases, info
 
 

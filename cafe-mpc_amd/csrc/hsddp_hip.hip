@@ -16,6 +16,7 @@
 #include <cmath>
 #include "hsddp.h"
 #include "hsddp_ensemble.h"
+#include "hsddp_hkd.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -24,6 +25,7 @@
 #include "hkd_knot.hpp"
 #include "sweep.hpp"
 #include "ensemble.hpp"
+#include "hkd_pack.hpp"
 
 using namespace hs;
 
@@ -622,6 +624,12 @@ struct hsddp_handle {
     unsigned long long* d_units = nullptr;   // knots processed by k_rollout / k_lq / k_sweep launches since the last reset (measurement)
     float* d_hist = nullptr; int hist_cap = 0;      // history buffers [batch][4][hist_cap]
     unsigned int* d_cmd = nullptr; size_t cmd_words = 0; int* d_cmd_map = nullptr; int cmd_steps = 0; float* d_cmd_status = nullptr;   // export staging (kept across calls)
+    // HKD command export staging (kept across calls, freed by hsddp_destroy): the map of the last call, status times (nph_cap x 4), pf_in rows,
+    // the rows of a host-destination export
+    HkdMap* d_hkd_map = nullptr; HkdMap h_hkd_map{}; bool hkd_map_valid = false;
+    double* d_hkd_status = nullptr; std::vector<double> h_hkd_status;
+    float* d_hkd_pf = nullptr; size_t hkd_pf_cap = 0;
+    unsigned int* d_hkd_out = nullptr; size_t hkd_out_cap = 0;
     ProbState* d_st = nullptr;
     double* d_x0 = nullptr;
     SlotArrays sa{};
@@ -713,6 +721,7 @@ void hsddp_destroy(hsddp_handle_t* h) {
     if (h->d_cmd) hipFree(h->d_cmd);
     if (h->d_cmd_map) hipFree(h->d_cmd_map);
     if (h->d_cmd_status) hipFree(h->d_cmd_status);
+    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out}; for (void* q : p) if (q) hipFree(q); }
     for (auto e : h->pool) hipEventDestroy(e);
     if (h->h_counters) hipHostFree(h->h_counters);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1472,6 +1481,78 @@ int hsddp_ensemble_export_mpc_commands(hsddp_ensemble_t* e, int n, const int* ca
     if (!dst_device) HIPCK(hipMemcpyAsync(out, e->d_out, row * n * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
     HIPCK(hipStreamSynchronize(e->stream));
     return HSDDP_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ HKD-MPC command export (hsddp_hkd.h)
+// the knot walk of publish_mpc_cmd (HKDMPC.cpp:250-258) and the foothold search of update_foot_placement (:207-240); false: window too short
+static bool hkd_map_of(const hsddp_handle* h, int n_steps, HkdMap& m) {
+    memset(&m, 0, sizeof(m));
+    for (int k = 0, s = 0, i = 0; k < n_steps; k++, s++) {
+        if (s >= h->ph[i].h) { s = 0; i++; }
+        if (i >= h->nph) return false;
+        m.ph[k] = i; m.k[k] = s;
+    }
+    for (int l = 0; l < 4; l++) m.fh[l] = -1;
+    for (int i = 0; i < h->nph - 1; i++) {
+        for (int l = 0; l < 4; l++)
+            if (m.fh[l] < 0 && h->ph[i].contact[l] == 0 && h->ph[i + 1].contact[l] == 1) m.fh[l] = i + 1;
+        if (i >= 4) break;
+    }
+    return true;
+}
+
+int hsddp_export_hkd_commands(hsddp_handle_t* h, int b0, int nb, int n_steps, double mpc_time, double dt,
+                              const double* status_times, const float* pf_in, unsigned int* out, int dst_device) {
+    if (!h || b0 < 0 || nb < 0 || b0 > h->batch || nb > h->batch - b0 || n_steps < 1 || n_steps > HSDDP_HKD_MAX_STEPS || (nb > 0 && !out)) return HSDDP_EINVAL;
+    for (int i = 0; i < h->nph; i++) if (h->ph[i].model != HSDDP_MODEL_HKD) return HSDDP_EINVAL;
+    HkdMap m;
+    if (!hkd_map_of(h, n_steps, m)) return HSDDP_EINVAL;
+    if (nb == 0) return HSDDP_OK;
+    HIPCK(hipSetDevice(h->device));
+    // staging kept in the handle (a warm MPC tick makes no device allocation): grown on demand, freed by hsddp_destroy
+    if (!h->d_hkd_map) HIPCK(hipMalloc((void**)&h->d_hkd_map, sizeof(HkdMap)));
+    if (!h->d_hkd_status) HIPCK(hipMalloc((void**)&h->d_hkd_status, (size_t)h->nph_cap * 4 * sizeof(double)));
+    if (pf_in && (size_t)nb * 12 > h->hkd_pf_cap) {
+        HIPCK(hipStreamSynchronize(h->stream));
+        if (h->d_hkd_pf) HIPCK(hipFree(h->d_hkd_pf)); h->d_hkd_pf = nullptr; h->hkd_pf_cap = 0;
+        HIPCK(hipMalloc((void**)&h->d_hkd_pf, (size_t)nb * 12 * sizeof(float))); h->hkd_pf_cap = (size_t)nb * 12;
+    }
+    const size_t words = (size_t)nb * HSDDP_HKD_CMD_WORDS;
+    if (!dst_device && words > h->hkd_out_cap) {
+        HIPCK(hipStreamSynchronize(h->stream));
+        if (h->d_hkd_out) HIPCK(hipFree(h->d_hkd_out)); h->d_hkd_out = nullptr; h->hkd_out_cap = 0;
+        HIPCK(hipMalloc((void**)&h->d_hkd_out, words * sizeof(unsigned int))); h->hkd_out_cap = words;
+    }
+    // the map and the status times are uploaded only when they changed (the host copies are the async sources: they outlive the call)
+    if (!h->hkd_map_valid || memcmp(&m, &h->h_hkd_map, sizeof(m))) {
+        HIPCK(hipStreamSynchronize(h->stream));
+        h->h_hkd_map = m; h->hkd_map_valid = true;
+        HIPCK(hipMemcpyAsync(h->d_hkd_map, &h->h_hkd_map, sizeof(HkdMap), hipMemcpyHostToDevice, h->stream));
+    }
+    if (status_times) {
+        const size_t n = (size_t)h->nph * 4;
+        if (h->h_hkd_status.size() != n || memcmp(h->h_hkd_status.data(), status_times, n * sizeof(double))) {
+            HIPCK(hipStreamSynchronize(h->stream));
+            h->h_hkd_status.assign(status_times, status_times + n);
+            HIPCK(hipMemcpyAsync(h->d_hkd_status, h->h_hkd_status.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        }
+    }
+    if (pf_in) HIPCK(hipMemcpyAsync(h->d_hkd_pf, pf_in, (size_t)nb * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    unsigned int* dst = dst_device ? out : h->d_hkd_out;
+    const int vec2 = ((uintptr_t)dst % 8) == 0;
+    hipLaunchKernelGGL(k_pack_hkd, dim3(nb), dim3(256), 0, h->stream, h->d_ph, h->d_hkd_map, b0, n_steps, mpc_time, dt,
+                       status_times ? h->d_hkd_status : nullptr, pf_in ? h->d_hkd_pf : nullptr, h->solve_ms, dst, vec2);
+    HIPCK(hipGetLastError());
+    if (!dst_device) HIPCK(hipMemcpyAsync(out, h->d_hkd_out, words * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    return HSDDP_OK;
+}
+
+int hsddp_export_hkd_command(hsddp_handle_t* h, int problem, int n_steps, double mpc_time, double dt, const double* status_times, const float* pf_in,
+                             unsigned int* out) {
+    if (!out) return HSDDP_EINVAL;
+    return hsddp_export_hkd_commands(h, problem, 1, n_steps, mpc_time, dt, status_times, pf_in, out, 0);
 }
 
 }  // extern "C"

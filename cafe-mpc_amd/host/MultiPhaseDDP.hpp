@@ -16,6 +16,7 @@
 #include <stdexcept>
 #include <cstring>
 #include "hsddp.h"
+#include "hsddp_hkd.h"
 
 namespace hsddp {
 
@@ -92,6 +93,20 @@ public:
         std::vector<unsigned int> words(1 + (size_t)n_steps * HSDDP_CMD_WORDS_PER_STEP);
         rc_ = hsddp_export_mpc_command(h_, problem, n_steps, mpc_time, dt, status_times, words.data());
         return words;
+    }
+    // update_foot_placement + publish_mpc_cmd (HKDMPC/HKDMPC.cpp:207-297) of an HKD window: the hkd_command_lcmt row of one problem
+    // (include/hsddp_hkd.h; the caller memcpys it into its lcm-gen struct).  status_times: n_phases x 4 contact durations
+    // (HkdProblemData::Row::dur), pf_in: the problem's current footholds (hkd_data_lcmt foot_placements), both optional.  libhsddp_hip.so only.
+    std::vector<unsigned int> export_hkd_command(int problem, int n_steps, double mpc_time, double dt, const double* status_times = nullptr,
+                                                 const float* pf_in = nullptr) {
+        std::vector<unsigned int> words(HSDDP_HKD_CMD_WORDS);
+        rc_ = hsddp_export_hkd_command(h_, problem, n_steps, mpc_time, dt, status_times, pf_in, words.data());
+        return words;
+    }
+    // the rows of problems [b0, b0+nb) in one launch into `out` (nb x HSDDP_HKD_CMD_WORDS words; device memory when dst_device = 1)
+    void export_hkd_commands(int b0, int nb, int n_steps, double mpc_time, double dt, const double* status_times, const float* pf_in,
+                             unsigned int* out, int dst_device = 0) {
+        rc_ = hsddp_export_hkd_commands(h_, b0, nb, n_steps, mpc_time, dt, status_times, pf_in, out, dst_device);
     }
     // receding-horizon step (MHPCProblem::update): phase `dphase` continues phase `sphase` of the previous window (sphase < 0: new phase)
     void warm_start_phase(int dphase, MultiPhaseDDP<T>* prev, int sphase, int popped_front) {

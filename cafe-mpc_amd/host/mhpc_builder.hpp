@@ -265,15 +265,16 @@ inline HkdConstraintParams load_hkd_constraint_params(const std::string& path) {
 // caller hands that to hsddp::MultiPhaseDDP::reconfigure and zeroes the window's first control (set_control_knot(0, 0), HKDProblem.cpp:220).
 class HkdProblemData {
 public:
-    struct Row { float start, end; int h; std::array<int, 4> contact; bool reach_end, has_td; int shooting, uid; };
+    // dur: contact_durations, the reference's status_dur at the phase's start (HKDProblem.cpp:27-38, 57, 63, 162-167)
+    struct Row { float start, end; int h; std::array<int, 4> contact; bool reach_end, has_td; int shooting, uid; std::array<double, 4> dur; };
     std::vector<Row> ph; float ref_start = 0; int dup_td = 0;
     HkdProblemData(QuadReference& r, const HkdConstraintParams& p, float plan_duration = 0.6f, float dt_sim = 0.01f, int nsteps_between_mpc = 2)
         : ref(r), cpar(p), plan(plan_duration), dt(dt_sim), nsteps(nsteps_between_mpc), dt_mpc(dt_sim * (float)nsteps_between_mpc) {
         ref.initialize(plan);
-        float t = 0, start = 0; auto c_prev = contact_at(t);
+        float t = 0, start = 0; auto c_prev = contact_at(t); auto d_prev = dur_at(t);
         while (approx_leq(t, plan)) {      // HKDProblem.cpp:34-63
             auto c_cur = contact_at(t);
-            if (c_cur != c_prev || t > plan || approx_eq(t, plan)) { push(start, t, (int)std::round((float)(t - start) / dt), c_prev, 1); c_prev = c_cur; start = t; }
+            if (c_cur != c_prev || t > plan || approx_eq(t, plan)) { push(start, t, (int)std::round((float)(t - start) / dt), c_prev, d_prev, 1); c_prev = c_cur; d_prev = dur_at(t); start = t; }
             t = t + dt;
         }
         for (size_t i = 0; i < ph.size(); i++) ph[i].has_td = touchdown(i);
@@ -287,7 +288,7 @@ public:
             if (approx_leq(ph.front().end, new_start)) ph.erase(ph.begin());
             else { popped[ph.front().uid]++; ph.front().h--; ph.front().start = new_start; }
             auto nc = contact_at(new_end - new_start); const bool change = nc != ph.back().contact;
-            if (change && ph.back().reach_end) { const float ns = ph.back().end; push(ns, new_end, (int)std::round((float)(new_end - ns) / dt), nc, 0); }
+            if (change && ph.back().reach_end) { const float ns = ph.back().end; push(ns, new_end, (int)std::round((float)(new_end - ns) / dt), nc, dur_at(new_end - new_start), 0); }
             else { ph.back().end = new_end; ph.back().h++; if (change) ph.back().reach_end = true; pushed[ph.back().uid]++; }
             if (ph.back().reach_end) { const bool td = touchdown(ph.size() - 1); if (td && ph.back().has_td) dup_td++; ph.back().has_td = ph.back().has_td || td; }
         }
@@ -328,7 +329,8 @@ public:
 private:
     QuadReference& ref; HkdConstraintParams cpar; float plan, dt; int nsteps; float dt_mpc; int next_uid = 0;
     std::array<int, 4> contact_at(float t) const { const QuadSample& s = ref.at(t); return {s.contact[0], s.contact[1], s.contact[2], s.contact[3]}; }
-    void push(float start, float end, int h, const std::array<int, 4>& c, int shooting) { ph.push_back(Row{start, end, h, c, false, false, shooting, next_uid++}); }
+    std::array<double, 4> dur_at(float t) const { const QuadSample& s = ref.at(t); return {s.status_dur[0], s.status_dur[1], s.status_dur[2], s.status_dur[3]}; }
+    void push(float start, float end, int h, const std::array<int, 4>& c, const std::array<double, 4>& d, int shooting) { ph.push_back(Row{start, end, h, c, false, false, shooting, next_uid++, d}); }
     std::array<int, 4> next_contact(size_t i) const { return i + 1 < ph.size() ? ph[i + 1].contact : contact_at(plan + dt_mpc); }
     bool touchdown(size_t i) const { const auto n = next_contact(i); for (int l = 0; l < 4; l++) if (ph[i].contact[l] == 0 && n[l] == 1) return true; return false; }
     static void hkd_state(const QuadSample& a, double* x) {      // HKDSinglePhaseReference::get_reference_at_t (HKDReference.cpp:23-61): [eul, pos, omega, v, qdummy]
