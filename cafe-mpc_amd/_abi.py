@@ -170,6 +170,32 @@ def bind_hkd(lib):
     lib.hsddp_export_hkd_command.argtypes = [H, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
 
+
+# include/hsddp_refs.h: per-problem tracking references (libhsddp_hip.so only)
+REFS_EXPORTS = ["hsddp_set_references", "hsddp_get_references"]
+REF_FIELDS = ("xr", "ur", "yr", "foot_pos", "foot_vel", "body_pos", "ref_contact")     # hsddp_refs_t order
+
+
+class Refs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in REF_FIELDS]
+
+
+def ref_widths(model):
+    """Row widths of the seven reference arrays of a phase of `model` (those of hsddp_phase_desc_t)."""
+    n, m, p = MODEL_DIMS[model]
+    return dict(xr=n, ur=m, yr=p, foot_pos=12, foot_vel=12, body_pos=3, ref_contact=4)
+
+
+def bind_refs(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_refs.h.  Raises if the library lacks any of them."""
+    missing = [s for s in REFS_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the per-problem reference entry points {missing}")
+    H = C.c_void_p
+    lib.hsddp_set_references.argtypes = [H, C.c_int, C.c_int, C.c_int, C.POINTER(Refs), C.c_int]
+    lib.hsddp_get_references.argtypes = [H, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
+    return lib
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -378,6 +404,52 @@ class Solver:
         if rc != 0:
             raise RuntimeError(f"hsddp_export_hkd_commands failed: {rc}")
         return rows
+
+    def _refs_bound(self):
+        if not getattr(self, "_refs_ok", False):
+            bind_refs(self.lib); self._refs_ok = True      # raises on a library without include/hsddp_refs.h (the CPU checker)
+
+    def set_references(self, phase, b0=0, **arrays):
+        """Per-problem tracking references of one phase (include/hsddp_refs.h) for problems b0 .. b0+nb-1.  Keywords: any of xr, ur, yr, foot_pos,
+        foot_vel, body_pos (float64) and ref_contact (int32), each [nb, h+1, width]; fields left out keep their values.  All numpy arrays (copied
+        through host staging) or all torch tensors on the handle's device (read in place)."""
+        self._refs_bound()
+        unknown = set(arrays) - set(REF_FIELDS)
+        if unknown or not arrays:
+            raise ValueError(f"set_references takes some of {REF_FIELDS}, got {sorted(arrays)}")
+        if not 0 <= phase < len(self.phases):
+            raise ValueError(f"phase {phase} out of range")
+        w, h1 = ref_widths(self.phases[phase]["desc"].model), self.horizons[phase] + 1
+        is_t = [type(a).__module__.startswith("torch") for a in arrays.values()]
+        if any(is_t) and not all(is_t):
+            raise ValueError("set_references: pass all numpy arrays or all torch tensors")
+        nb = next(iter(arrays.values())).shape[0]
+        refs, keep = Refs(), []
+        for name, a in arrays.items():
+            shape = (nb, h1, w[name])
+            if is_t[0]:
+                import torch
+                want = torch.int32 if name == "ref_contact" else torch.float64
+                if a.dtype != want or not a.is_contiguous() or a.device.type != "cuda" or tuple(a.shape) != shape:
+                    raise ValueError(f"{name}: need a contiguous {want} tensor of shape {shape} on the handle's device, got {a.dtype} "
+                                     f"{tuple(a.shape)} on {a.device} (contiguous={a.is_contiguous()})")
+                setattr(refs, name, a.data_ptr())
+            else:
+                a = np.ascontiguousarray(a, dtype=np.int32 if name == "ref_contact" else np.float64)
+                if a.shape != shape:
+                    raise ValueError(f"{name}: shape {a.shape}, need {shape}")
+                keep.append(a); setattr(refs, name, a.ctypes.data)
+        self._ck(self.lib.hsddp_set_references(self.h, phase, b0, nb, C.byref(refs), 1 if is_t[0] else 0), "set_references")
+
+    def get_references(self, phase, b0=0, nb=None):
+        """The references problems b0 .. b0+nb-1 of a phase track: dict of [nb, h+1, width] arrays (yr only where p > 0)."""
+        self._refs_bound()
+        nb = self.batch - b0 if nb is None else nb
+        w, h1 = ref_widths(self.phases[phase]["desc"].model), self.horizons[phase] + 1
+        out = {n: np.zeros((nb, h1, w[n]), dtype=np.int32 if n == "ref_contact" else np.float64) for n in REF_FIELDS if w[n] > 0}
+        self._ck(self.lib.hsddp_get_references(self.h, phase, b0, nb, *[out[n].ctypes.data if n in out else None for n in REF_FIELDS]),
+                 "get_references")
+        return out
 
     def get_history(self, problem=0, cap=4096):
         """MultiPhaseDDP::get_solver_info(cost, dyn_feas, eqn_feas, ineq_feas) (MultiPhaseDDP.h:85): the four float history buffers."""

@@ -67,9 +67,9 @@ HD double hkd_grf_row(const double* u, int f, int r, double mu) {
     const double fx = u[3 * f], fy = u[3 * f + 1], fz = u[3 * f + 2];
     return r == 0 ? fz : r == 1 ? -fx + mu * fz : r == 2 ? fx + mu * fz : r == 3 ? -fy + mu * fz : fy + mu * fz;
 }
-// sum_f,a d (c_f w_a) d of the foot-placement regulariser (HKDCost.cpp:4-19) at knot k
-HD double hkd_footreg(PhaseC& P, const double* x, int k) {
-    const double* fp = P.foot_pos + (size_t)k * 12; const double* bp = P.body_pos + (size_t)k * 3;
+// sum_f,a d (c_f w_a) d of the foot-placement regulariser (HKDCost.cpp:4-19) at knot k of problem b
+HD double hkd_footreg(PhaseC& P, const double* x, int b, int k) {
+    const double* fp = P.foot_pos + ref_row(P, b, k) * 12; const double* bp = P.body_pos + ref_row(P, b, k) * 3;
     double s = 0;
     for (int f = 0; f < 4; f++) for (int a = 0; a < 3; a++) { const double d = (x[12 + 3 * f + a] - x[3 + a]) - (fp[3 * f + a] - bp[a]); s += d * (P.contact[f] * P.w_foot_reg[a]) * d; }
     return s;
@@ -106,10 +106,11 @@ HD void hkd_rollout_knot(HkdLds& L, PhaseC& P, int b, int k, double eps, int reb
     })
     HS_PHASE(NT, if (tid == 0) {
         double lq = 0, lr = 0;
-        for (int i = 0; i < 24; i++) { const double d = L.x[i] - P.xr[(size_t)k * 24 + i]; lq += d * P.q[i] * d; }
-        for (int i = 0; i < 24; i++) { const double d = L.u[i] - P.ur[(size_t)k * 24 + i]; lr += d * P.r[i] * d; }
+        const size_t rw = ref_row(P, b, k);
+        for (int i = 0; i < 24; i++) { const double d = L.x[i] - P.xr[rw * 24 + i]; lq += d * P.q[i] * d; }
+        for (int i = 0; i < 24; i++) { const double d = L.u[i] - P.ur[rw * 24 + i]; lr += d * P.r[i] * d; }
         double l = 0.5 * lq; l += 0.5 * lr; l *= P.dt;
-        if (P.w_foot_reg[0] >= 0) { double t = .5 * hkd_footreg(P, L.x, k); t *= P.dt; l += t; }
+        if (P.w_foot_reg[0] >= 0) { double t = .5 * hkd_footreg(P, L.x, b, k); t *= P.dt; l += t; }
         if (wr) P.lbase[kk] = l;
         double ming = 0;
         if (P.ng > 0) {
@@ -135,9 +136,9 @@ HD void hkd_rollout_terminal(HkdLds& L, PhaseC& P, PhaseC* Pn, const ModelDev& m
         L.pf[3 * tid] = f.x; L.pf[3 * tid + 1] = f.y; L.pf[3 * tid + 2] = f.z;
     })
     HS_PHASE(NT, if (tid == 0) {
-        double s = 0; for (int i = 0; i < 24; i++) { const double d = L.x[i] - P.xr[(size_t)h * 24 + i]; s += d * P.qf[i] * d; }
+        double s = 0; const size_t rw = ref_row(P, b, h); for (int i = 0; i < 24; i++) { const double d = L.x[i] - P.xr[rw * 24 + i]; s += d * P.qf[i] * d; }
         double pb = 0.5 * s;
-        if (P.w_foot_reg[0] >= 0) pb += 10 * hkd_footreg(P, L.x, h);
+        if (P.w_foot_reg[0] >= 0) pb += 10 * hkd_footreg(P, L.x, b, h);
         if (wr) P.Phibase[b] = pb;
         double maxh = 0, c = 0; int i = 0;
         for (int f = 0; f < 4; f++) if (P.td[f] && P.nt > 0) {
@@ -220,14 +221,15 @@ HD void hkd_lq_knot(HkdLds& L, PhaseC& P, int b, int k, int reb_active) {
         rec_put(P, kk, P.oLuu + e, uu);
     } if (tid < 24) {
         const int i = tid;
-        double lx = dt * P.q[i] * (L.x[i] - P.xr[(size_t)k * 24 + i]);
+        const size_t rw = ref_row(P, b, k);
+        double lx = dt * P.q[i] * (L.x[i] - P.xr[rw * 24 + i]);
         if (fr != 0.0) {
-            const double* fp = P.foot_pos + (size_t)k * 12; const double* bp = P.body_pos + (size_t)k * 3;
+            const double* fp = P.foot_pos + rw * 12; const double* bp = P.body_pos + rw * 3;
             if (i >= 3 && i < 6) { for (int f = 0; f < 4; f++) lx -= dt * P.contact[f] * P.w_foot_reg[i - 3] * ((L.x[12 + 3 * f + i - 3] - L.x[i]) - (fp[3 * f + i - 3] - bp[i - 3])); }
             else if (i >= 12) { const int f = (i - 12) / 3, a = (i - 12) % 3; lx += dt * P.contact[f] * P.w_foot_reg[a] * ((L.x[i] - L.x[3 + a]) - (fp[3 * f + a] - bp[a])); }
         }
         rec_put(P, kk, P.oLx + i, lx);
-        double lu = dt * P.r[i] * (L.u[i] - P.ur[(size_t)k * 24 + i]);
+        double lu = dt * P.r[i] * (L.u[i] - P.ur[rw * 24 + i]);
         if (P.go_grf >= 0 && i < 12) {
             const int f = i / 3; int a2 = -1; for (int t = 0; t < P.nc; t++) if (P.feet[t] == f) a2 = t;
             if (a2 >= 0) for (int cc = 0; cc < 5; cc++) {
@@ -293,9 +295,10 @@ HD void hkd_lq_terminal(HkdLds& L, PhaseC& P, PhaseC* Pn, const ModelDev& md, in
         }
     } if (tid < 24) {
         const int i = tid;
-        double px = P.qf[i] * (L.x[i] - P.xr[(size_t)h * 24 + i]);
+        const size_t rw = ref_row(P, b, h);
+        double px = P.qf[i] * (L.x[i] - P.xr[rw * 24 + i]);
         if (fr != 0.0) {
-            const double* fp = P.foot_pos + (size_t)h * 12; const double* bp = P.body_pos + (size_t)h * 3;
+            const double* fp = P.foot_pos + rw * 12; const double* bp = P.body_pos + rw * 3;
             if (i >= 3 && i < 6) { for (int f = 0; f < 4; f++) px -= fr * P.contact[f] * P.w_foot_reg[i - 3] * ((L.x[12 + 3 * f + i - 3] - L.x[i]) - (fp[3 * f + i - 3] - bp[i - 3])); }
             else if (i >= 12) { const int f = (i - 12) / 3, a = (i - 12) % 3; px += fr * P.contact[f] * P.w_foot_reg[a] * ((L.x[i] - L.x[3 + a]) - (fp[3 * f + a] - bp[a])); }
         }

@@ -44,12 +44,14 @@ struct PhaseDev {
     int nt;                                           // terminal constraints (touchdown feet)
     int slot0;                                        // first global slot of this phase (slots = h+1 per phase)
     int nobj; unsigned long long obj_off, obj_sz;     // constraint objects in the order the reference adds their ReB cost (constraint_objects): first constraint / count of object o in bits [8o, 8o+8)
-    // reference arrays shared by the batch: (h+1) x width
+    // reference arrays, rows of `width` elements: shared by the batch ((h+1) rows, ref_pb = 0) or per problem ([batch][h+1] rows, ref_pb = h+1,
+    // hsddp_set_references).  The row of problem b at knot k is b * ref_pb + k (ref_row).
     const HS_GLOBAL double *xr, *ur, *yr, *foot_pos, *foot_vel, *body_pos;
     const HS_GLOBAL int* ref_contact;
     // whole-body phases: the references of knot k in ONE record of 80 doubles (one base pointer for the rollout knot's first reads):
     // [0,36) xr | [36,48) ur | [48,60) foot_vel | [60,64) ref_contact as doubles | [64,76) foot_pos - body_pos | [76,80) pad
     const HS_GLOBAL double* rref;
+    int ref_pb;                                       // reference rows per problem: 0 (shared, what setup_phase leaves) or h+1
     // trajectories
     HS_GLOBAL double *X, *Xbar, *Xsim, *Defect, *Defect_bar, *dX, *G;           // (h+1) x n
     HS_GLOBAL double *U, *Ubar, *dU, *Qu;                                        // h x m
@@ -76,6 +78,9 @@ struct PhaseDev {
 template <class PD> HD void rec_put(PD& P, size_t kk, int off, double v) {
     if (P.rec32 != nullptr) P.rec32[kk * P.rs + off] = (float)v; else P.rec[kk * P.rs + off] = v;
 }
+
+// reference row (PhaseDev::ref_pb) of problem b at knot k (32-bit product: hsddp_set_references refuses batch x (h+1) >= 2^31)
+template <class PD> HD size_t ref_row(PD& P, int b, int k) { return (unsigned)(b * P.ref_pb + k); }
 
 // how device code sees a descriptor: constant memory (scalar loads, values survive memory clobbers)
 using PhaseC = const HS_CONST PhaseDev;

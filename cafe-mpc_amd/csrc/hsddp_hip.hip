@@ -17,6 +17,7 @@
 #include "hsddp.h"
 #include "hsddp_ensemble.h"
 #include "hsddp_hkd.h"
+#include "hsddp_refs.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -26,6 +27,7 @@
 #include "sweep.hpp"
 #include "ensemble.hpp"
 #include "hkd_pack.hpp"
+#include "refs.hpp"
 
 using namespace hs;
 
@@ -630,6 +632,10 @@ struct hsddp_handle {
     double* d_hkd_status = nullptr; std::vector<double> h_hkd_status;
     float* d_hkd_pf = nullptr; size_t hkd_pf_cap = 0;
     unsigned int* d_hkd_out = nullptr; size_t hkd_out_cap = 0;
+    // per-problem references (hsddp_refs.h): one arena, bump-allocated by the first hsddp_set_references of a phase and emptied by
+    // hsddp_reconfigure (the new window's phases are shared again); staging for host sources.  Both grow on demand, freed by hsddp_destroy.
+    char* d_refs = nullptr; size_t refs_cap = 0, refs_used = 0;
+    char* d_refs_stage = nullptr; size_t refs_stage_cap = 0;
     ProbState* d_st = nullptr;
     double* d_x0 = nullptr;
     SlotArrays sa{};
@@ -721,7 +727,7 @@ void hsddp_destroy(hsddp_handle_t* h) {
     if (h->d_cmd) hipFree(h->d_cmd);
     if (h->d_cmd_map) hipFree(h->d_cmd_map);
     if (h->d_cmd_status) hipFree(h->d_cmd_status);
-    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out}; for (void* q : p) if (q) hipFree(q); }
+    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out, h->d_refs, h->d_refs_stage}; for (void* q : p) if (q) hipFree(q); }
     for (auto e : h->pool) hipEventDestroy(e);
     if (h->h_counters) hipHostFree(h->h_counters);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -895,6 +901,7 @@ int hsddp_reconfigure(hsddp_handle_t* h, int n_phases, const hsddp_phase_desc_t*
     h->probe_ok = true; for (int i = 0; i < n_phases; i++) if (!phases[i].shooting && phases[i].model != HSDDP_MODEL_WB) h->probe_ok = false;
     h->has_hkd = false; for (int i = 0; i < n_phases; i++) if (phases[i].model == HSDDP_MODEL_HKD) h->has_hkd = true;
     h->cache_valid = false;
+    h->refs_used = 0;                                                                   // every phase of the new window reads its descriptor's references
     if (h->d_cmd_status) { hipFree(h->d_cmd_status); h->d_cmd_status = nullptr; }      // sized by the phase count
     HIPCK(hipGetLastError());
     return HSDDP_OK;
@@ -1553,6 +1560,129 @@ int hsddp_export_hkd_command(hsddp_handle_t* h, int problem, int n_steps, double
                              unsigned int* out) {
     if (!out) return HSDDP_EINVAL;
     return hsddp_export_hkd_commands(h, problem, 1, n_steps, mpc_time, dt, status_times, pf_in, out, 0);
+}
+
+
+// ------------------------------------------------------------------------------------------------ per-problem references (hsddp_refs.h)
+// widths of the seven raw arrays and the whole-body record of a phase (RefsPack segment order); 0: the phase keeps no such segment
+static void refs_widths(const PhaseDev& P, int w[RS_COUNT]) {
+    w[RS_XR] = P.n; w[RS_UR] = P.m; w[RS_YR] = P.p; w[RS_FP] = 12; w[RS_FV] = 12; w[RS_BP] = 3; w[RS_RC] = 4; w[RS_RREF] = P.model == HSDDP_MODEL_WB ? 80 : 0;
+}
+static bool refs_args_ok(const hsddp_handle* h, int phase, int b0, int nb) {
+    return h && phase >= 0 && phase < h->nph && nb > 0 && b0 >= 0 && b0 <= h->batch - nb;
+}
+static size_t refs_round(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+int hsddp_set_references(hsddp_handle_t* h, int phase, int b0, int nb, const hsddp_refs_t* refs, int src_device) {
+    if (!refs_args_ok(h, phase, b0, nb) || !refs) return HSDDP_EINVAL;
+    if (refs->yr && h->ph[phase].p == 0) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(h->device));
+    int w[RS_COUNT]; refs_widths(h->ph[phase], w);
+    const size_t B = h->batch, h1 = h->ph[phase].h + 1;
+    const bool first = h->ph[phase].ref_pb == 0;
+    if (B * h1 >= ((size_t)1 << 31)) return HSDDP_ENOTSUP;      // reference rows are indexed in 32 bits (ref_row)
+    if (first) {
+        // arena space of the phase's per-problem storage; growing moves the phases already switched (their pointers are rebased)
+        size_t need = 0;
+        for (int s = 0; s < RS_COUNT; s++) if (w[s]) need += refs_round(B * h1 * w[s] * (s == RS_RC ? sizeof(int) : sizeof(double)));
+        if (h->refs_used + need > h->refs_cap) {
+            const size_t cap = (h->refs_used + need) + (h->refs_used + need) / 4;
+            char* nbase = nullptr;
+            HIPCK(hipMalloc((void**)&nbase, cap));
+            if (h->refs_used) HIPCK(hipMemcpyAsync(nbase, h->d_refs, h->refs_used, hipMemcpyDeviceToDevice, h->stream));
+            HIPCK(hipStreamSynchronize(h->stream));
+            char* obase = h->d_refs;
+            auto mv = [&](const void* p) { return (const char*)p - obase + nbase; };
+            for (int i = 0; i < h->nph; i++) {
+                PhaseDev& Q = h->ph[i];
+                if (Q.ref_pb == 0) continue;
+                Q.xr = (const double*)mv(Q.xr); Q.ur = (const double*)mv(Q.ur); Q.foot_pos = (const double*)mv(Q.foot_pos);
+                Q.foot_vel = (const double*)mv(Q.foot_vel); Q.body_pos = (const double*)mv(Q.body_pos); Q.ref_contact = (const int*)mv(Q.ref_contact);
+                if (Q.p) Q.yr = (const double*)mv(Q.yr);
+                if (Q.model == HSDDP_MODEL_WB) Q.rref = (const double*)mv(Q.rref);
+            }
+            if (obase) HIPCK(hipFree(obase));
+            h->d_refs = nbase; h->refs_cap = cap;
+        }
+    }
+    const PhaseDev& P = h->ph[phase];
+    PhaseDev N = P;
+    RefsPack R{};
+    for (int s = 0; s < RS_COUNT; s++) R.w[s] = w[s];
+    const double* cur[RS_COUNT - 1] = {P.xr, P.ur, P.yr, P.foot_pos, P.foot_vel, P.body_pos, (const double*)P.ref_contact};
+    for (int s = 0; s < RS_COUNT - 1; s++) R.cur[s] = cur[s];
+    if (first) {
+        char* p = h->d_refs + h->refs_used;
+        double* seg[RS_COUNT] = {};
+        for (int s = 0; s < RS_COUNT; s++) if (w[s]) { seg[s] = (double*)p; p += refs_round(B * h1 * w[s] * (s == RS_RC ? sizeof(int) : sizeof(double))); }
+        h->refs_used = p - h->d_refs;
+        N.xr = seg[RS_XR]; N.ur = seg[RS_UR]; N.foot_pos = seg[RS_FP]; N.foot_vel = seg[RS_FV]; N.body_pos = seg[RS_BP]; N.ref_contact = (const int*)seg[RS_RC];
+        if (w[RS_YR]) N.yr = seg[RS_YR];
+        if (w[RS_RREF]) N.rref = seg[RS_RREF];
+        N.ref_pb = (int)h1;
+    }
+    R.dst[RS_XR] = (double*)N.xr; R.dst[RS_UR] = (double*)N.ur; R.dst[RS_YR] = w[RS_YR] ? (double*)N.yr : nullptr; R.dst[RS_FP] = (double*)N.foot_pos;
+    R.dst[RS_FV] = (double*)N.foot_vel; R.dst[RS_BP] = (double*)N.body_pos; R.dst[RS_RC] = (double*)N.ref_contact; R.dst[RS_RREF] = w[RS_RREF] ? (double*)N.rref : nullptr;
+    // sources: the caller's device arrays, or host arrays staged in one device buffer
+    const void* src[RS_COUNT - 1] = {refs->xr, refs->ur, refs->yr, refs->foot_pos, refs->foot_vel, refs->body_pos, refs->ref_contact};
+    auto src_bytes = [&](int s) { return (size_t)nb * h1 * w[s] * (s == RS_RC ? sizeof(int) : sizeof(double)); };
+    if (src_device) {
+        for (int s = 0; s < RS_COUNT - 1; s++) R.src[s] = (const double*)src[s];
+    } else {
+        size_t total = 0;
+        for (int s = 0; s < RS_COUNT - 1; s++) if (src[s]) total += refs_round(src_bytes(s));
+        if (total > h->refs_stage_cap) {
+            HIPCK(hipStreamSynchronize(h->stream));
+            if (h->d_refs_stage) HIPCK(hipFree(h->d_refs_stage)); h->d_refs_stage = nullptr; h->refs_stage_cap = 0;
+            HIPCK(hipMalloc((void**)&h->d_refs_stage, total)); h->refs_stage_cap = total;
+        }
+        char* p = h->d_refs_stage;
+        for (int s = 0; s < RS_COUNT - 1; s++) if (src[s]) {
+            HIPCK(hipMemcpyAsync(p, src[s], src_bytes(s), hipMemcpyHostToDevice, h->stream));
+            R.src[s] = (const double*)p; p += refs_round(src_bytes(s));
+        }
+    }
+    R.h1 = (int)h1; R.cur_pb = P.ref_pb; R.b0 = b0; R.nb = nb;
+    // problems written: the whole batch on the first call (the shared rows fill the rest), the range afterwards; split so that every flat
+    // index of a launch fits 32 bits
+    const int p_lo = first ? 0 : b0, p_hi = first ? (int)B : b0 + nb;
+    const int chunk = (int)std::max<size_t>(1, ((size_t)1 << 31) / (h1 * 80));
+    for (int p0 = p_lo; p0 < p_hi; p0 += chunk) {
+        R.p0 = p0; R.np = std::min(chunk, p_hi - p0);
+        const size_t most = (size_t)R.np * h1 * 80;
+        const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((most + 1023) / 1024, 1), 16384);
+        hipLaunchKernelGGL(k_pack_refs, dim3(blocks, RS_COUNT), dim3(256), 0, h->stream, R);
+        HIPCK(hipGetLastError());
+    }
+    h->ph[phase] = N;
+    HIPCK(hipMemcpyAsync(h->d_ph, h->ph.data(), sizeof(PhaseDev) * h->nph, hipMemcpyHostToDevice, h->stream));
+    std::vector<PhaseDev> sst = h->ph; for (auto& q : sst) q.shooting = 0;
+    HIPCK(hipMemcpyAsync(h->d_ph_ss, sst.data(), sizeof(PhaseDev) * h->nph, hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));      // (sst is the source of the last copy)
+    return HSDDP_OK;
+}
+
+int hsddp_get_references(hsddp_handle_t* h, int phase, int b0, int nb, double* xr, double* ur, double* yr, double* foot_pos, double* foot_vel,
+                         double* body_pos, int* ref_contact) {
+    if (!refs_args_ok(h, phase, b0, nb)) return HSDDP_EINVAL;
+    const PhaseDev& P = h->ph[phase];
+    if (yr && P.p == 0) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(h->device));
+    HIPCK(hipStreamSynchronize(h->stream));
+    int w[RS_COUNT]; refs_widths(P, w);
+    const size_t h1 = P.h + 1;
+    const void* cur[RS_COUNT - 1] = {P.xr, P.ur, P.yr, P.foot_pos, P.foot_vel, P.body_pos, P.ref_contact};
+    void* dst[RS_COUNT - 1] = {xr, ur, yr, foot_pos, foot_vel, body_pos, ref_contact};
+    for (int s = 0; s < RS_COUNT - 1; s++) {
+        if (!dst[s]) continue;
+        const size_t row = h1 * w[s] * (s == RS_RC ? sizeof(int) : sizeof(double));      // one problem's block
+        if (P.ref_pb) HIPCK(hipMemcpy(dst[s], (const char*)cur[s] + (size_t)b0 * row, (size_t)nb * row, hipMemcpyDeviceToHost));
+        else {
+            HIPCK(hipMemcpy(dst[s], cur[s], row, hipMemcpyDeviceToHost));
+            for (int i = 1; i < nb; i++) memcpy((char*)dst[s] + (size_t)i * row, dst[s], row);
+        }
+    }
+    return HSDDP_OK;
 }
 
 }  // extern "C"

@@ -65,7 +65,7 @@ HD void srb_rollout_knot(SrbLds& L, PhaseC& P, int b, int k, double eps, int reb
         const double u = P.Ubar[ku + tid] + eps * P.dU[ku + tid] + s;
         L.u[tid] = u; if (wr) P.U[ku + tid] = u;
     })
-    HS_PHASE(NT, if (tid == 0) srb_xdot<double>(L.x, L.u, P.foot_pos + (size_t)k * 12, P.ref_contact + (size_t)k * 4, L.xd);)
+    HS_PHASE(NT, if (tid == 0) srb_xdot<double>(L.x, L.u, P.foot_pos + ref_row(P, b, k) * 12, P.ref_contact + ref_row(P, b, k) * 4, L.xd);)
     HS_PHASE(NT, if (tid < 12) {
         const double xs = L.x[tid] + L.xd[tid] * P.dt;
         if (wr) P.Xsim[kx + 12 + tid] = xs;
@@ -77,8 +77,9 @@ HD void srb_rollout_knot(SrbLds& L, PhaseC& P, int b, int k, double eps, int reb
     })
     HS_PHASE(NT, if (tid == 0) {
         double lq = 0, lr = 0;
-        for (int i = 0; i < 12; i++) { const double d = L.x[i] - P.xr[(size_t)k * 12 + i]; lq += d * P.q[i] * d; }
-        for (int i = 0; i < 12; i++) { const double d = L.u[i] - P.ur[(size_t)k * 12 + i]; lr += d * P.r[i] * d; }
+        const size_t rw = ref_row(P, b, k);
+        for (int i = 0; i < 12; i++) { const double d = L.x[i] - P.xr[rw * 12 + i]; lq += d * P.q[i] * d; }
+        for (int i = 0; i < 12; i++) { const double d = L.u[i] - P.ur[rw * 12 + i]; lr += d * P.r[i] * d; }
         double l = 0.5 * lq; l += 0.5 * lr; l *= P.dt;
         if (wr) P.lbase[kk] = l;
         double ming = 0;
@@ -101,7 +102,7 @@ HD void srb_rollout_terminal(SrbLds& L, PhaseC& P, PhaseC* Pn, int b, double eps
     const size_t kx = ((size_t)b * (h + 1) + h) * 12;
     HS_PHASE(NT, if (tid < 12) { const double x = ss ? P.Xsim[kx + tid] : P.Xbar[kx + tid] + eps * P.dX[kx + tid]; L.x[tid] = x; if (wr) P.X[kx + tid] = x; })
     HS_PHASE(NT, if (tid == 0) {
-        double s = 0; for (int i = 0; i < 12; i++) { const double d = L.x[i] - P.xr[(size_t)h * 12 + i]; s += d * P.qf[i] * d; }
+        double s = 0; const size_t rw = ref_row(P, b, h); for (int i = 0; i < 12; i++) { const double d = L.x[i] - P.xr[rw * 12 + i]; s += d * P.qf[i] * d; }
         const double Phi = 0.5 * s;
         if (wr) { P.Phibase[b] = Phi; P.Phi[b] = Phi; }
         so.cost[slot] = Phi; so.ming[slot] = 0.0; so.maxh[slot] = 0.0; so.dsq[slot] = 0.0;
@@ -126,7 +127,7 @@ HD void srb_lq_knot(SrbLds& L, PhaseC& P, int b, int k, int reb_active) {
     HS_PHASE(NT, if (tid < 24) {   // lane d: column d of [df/dx | df/du]
         Dual xs[12], us[12], out[12];
         for (int i = 0; i < 12; i++) { xs[i] = Dual(L.x[i], (tid == i) ? 1.0 : 0.0); us[i] = Dual(L.u[i], (tid == 12 + i) ? 1.0 : 0.0); }
-        srb_xdot<Dual>(xs, us, P.foot_pos + (size_t)k * 12, P.ref_contact + (size_t)k * 4, out);
+        srb_xdot<Dual>(xs, us, P.foot_pos + ref_row(P, b, k) * 12, P.ref_contact + ref_row(P, b, k) * 4, out);
         for (int i = 0; i < 12; i++) L.AB[i + 12 * tid] = out[i].d * dt + ((tid == i) ? 1.0 : 0.0);
     } if (tid == 32) {
         double bd = 0, bdd = 0;
@@ -144,9 +145,9 @@ HD void srb_lq_knot(SrbLds& L, PhaseC& P, int b, int k, int reb_active) {
         if (r == c) { qd = dt * P.q[r]; rd = dt * P.r[r]; if (r == 2) qd += dt * L.bdd; }
         rec_put(P, kk, P.oLxx + e, qd); rec_put(P, kk, P.oLuu + e, rd);
     } if (tid < 12) {
-        double lx = dt * P.q[tid] * (L.x[tid] - P.xr[(size_t)k * 12 + tid]); if (tid == 2) lx += dt * L.bd;
+        double lx = dt * P.q[tid] * (L.x[tid] - P.xr[ref_row(P, b, k) * 12 + tid]); if (tid == 2) lx += dt * L.bd;
         rec_put(P, kk, P.oLx + tid, lx);
-        rec_put(P, kk, P.oLu + tid, dt * P.r[tid] * (L.u[tid] - P.ur[(size_t)k * 12 + tid]));
+        rec_put(P, kk, P.oLu + tid, dt * P.r[tid] * (L.u[tid] - P.ur[ref_row(P, b, k) * 12 + tid]));
     })
 }
 
@@ -155,7 +156,7 @@ template <int NT>
 HD void srb_lq_terminal(SrbLds& L, PhaseC& P, PhaseC* Pn, int b) {
     const int h = P.h;
     const size_t kx = ((size_t)b * (h + 1) + h) * 12;
-    HS_PHASE(NT, if (tid < 12) P.Phix[(size_t)b * 12 + tid] = P.qf[tid] * (P.X[kx + tid] - P.xr[(size_t)h * 12 + tid]);
+    HS_PHASE(NT, if (tid < 12) P.Phix[(size_t)b * 12 + tid] = P.qf[tid] * (P.X[kx + tid] - P.xr[ref_row(P, b, h) * 12 + tid]);
              for (int e = tid; e < 144; e += NT) { P.Phixx[(size_t)b * 144 + e] = (e % 12 == e / 12) ? P.qf[e % 12] : 0.0; if (Pn != nullptr) P.Px[(size_t)b * 144 + e] = (e % 12 == e / 12) ? 1.0 : 0.0; })
     (void)L;
 }

@@ -581,7 +581,7 @@ HD void wb_rollout_knot(WbCore& L, PhaseC& P, const ModelDev& md, int b, int k, 
         // addresses are picked per lane, idle lanes read a valid dummy
         const int g = tid < 36 ? 0 : tid < 48 ? 1 : tid < 60 ? 2 : 3, i = tid < 36 ? tid : tid < 48 ? tid - 36 : tid < 60 ? tid - 48 : 0;
         const double* pa = g == 0 ? P.Xbar + kx + i : (g == 1 && !ss) ? P.KdX + ku + i : P.Xbar + kx; const double* pb = P.dX + kx + (g == 0 ? i : 0);
-        const double* rr = P.rref + (size_t)k * 80;          // the knot's references: one record, lane tid takes entry tid (+ the relative foot position)
+        const double* rr = P.rref + ref_row(P, b, k) * 80;          // the knot's references: one record, lane tid takes entry tid (+ the relative foot position)
         const double* pc = rr + tid;
         const double* pd = g == 0 ? P.Xbar + kx + (ss ? 0 : 36) + i : g == 1 ? P.Ubar + ku + i : rr + 64 + i;
         const double* pe = g == 0 ? P.dX + kx + (ss ? 0 : 36) + i : g == 1 ? P.dU + ku + i : rr;
@@ -710,11 +710,11 @@ HD void wb_rollout_knot(WbCore& L, PhaseC& P, const ModelDev& md, int b, int k, 
 }
 
 // terminal cost without AL (tracking + foot-place reg (x1) + touchdown-velocity penalty). MHPCCost.cpp:67-87,255-268
-HD double wb_terminal_cost_base(PhaseC& P, const WbCore& L) {
-    const int h = P.h;
-    double s = 0; for (int i = 0; i < 36; i++) { double d = L.x[i] - P.xr[(size_t)h * 36 + i]; s += d * P.qf[i] * d; }
+HD double wb_terminal_cost_base(PhaseC& P, const WbCore& L, int b) {
+    const int h = P.h; const size_t rw = ref_row(P, b, h);
+    double s = 0; for (int i = 0; i < 36; i++) { double d = L.x[i] - P.xr[rw * 36 + i]; s += d * P.qf[i] * d; }
     double Phi = 0.5 * s;
-    const int* rc = P.ref_contact + (size_t)h * 4; const double* fp = P.foot_pos + (size_t)h * 12; const double* bp = P.body_pos + (size_t)h * 3;
+    const int* rc = P.ref_contact + rw * 4; const double* fp = P.foot_pos + rw * 12; const double* bp = P.body_pos + rw * 3;
     double l2 = 0, l5 = 0;
     for (int f = 0; f < 4; f++) {
         if (rc[f] > 0 && P.w_foot_reg[0] >= 0) { double t = 0; for (int a = 0; a < 3; a++) { double d = (L.fpos[3 * f + a] - L.x[a]) - (fp[3 * f + a] - bp[a]); t += d * P.w_foot_reg[a] * d; } l2 += 0.5 * t; }
@@ -735,7 +735,7 @@ HD void wb_rollout_terminal(WbCore& L, PhaseC& P, PhaseC* Pn, const ModelDev& md
     const bool impact = (Pn != nullptr) && P.has_impact;
     wb_terms<NT>(L, md, impact);
     HS_PHASE(NT, if (tid == 0) {
-        double pb = wb_terminal_cost_base(P, L); if (wr) P.Phibase[b] = pb;
+        double pb = wb_terminal_cost_base(P, L, b); if (wr) P.Phibase[b] = pb;
         double maxh = 0, c = 0; int i = 0;
         for (int f = 0; f < 4; f++) if (P.td[f] && P.nt > 0) {
             double hh = L.fpos[3 * f + 2] - P.ground_height; if (wr) P.th[(size_t)b * P.nt + i] = hh; maxh = fmax(maxh, fabs(hh));
@@ -770,14 +770,15 @@ HD void wb_rollout_terminal(WbCore& L, PhaseC& P, PhaseC* Pn, const ModelDev& md
 // coalesced copy LDS -> global
 template <int NT> HD void store_block(double* dst, const double* src, int n) { HS_PHASE_L(NT, for (int i = tid; i < n; i += NT) dst[i] = src[i];) }
 
-// References of knot k for the cost partials, fetched with the state so that no later phase waits on HBM:
+// References of knot k of problem b for the cost partials, fetched with the state so that no later phase waits on HBM:
 //   tmp[0,36) xr | tmp[36,48) ur | red[0,12) foot_pos | red[12,24) foot_vel | red[24,27) body_pos | red[28,32) ref_contact
-HD void wb_cost_prefetch(WbCore& L, PhaseC& P, int k, int tid) {
-    if (tid < 36) L.tmp[tid] = P.xr[(size_t)k * 36 + tid];
-    else if (tid < 48) L.tmp[tid] = P.ur[(size_t)k * 12 + tid - 36];
-    if (tid < 12) { L.red[tid] = P.foot_pos[(size_t)k * 12 + tid]; L.red[12 + tid] = P.foot_vel[(size_t)k * 12 + tid]; }
-    else if (tid < 15) L.red[12 + tid] = P.body_pos[(size_t)k * 3 + tid - 12];
-    else if (tid < 19) L.red[13 + tid] = (double)P.ref_contact[(size_t)k * 4 + tid - 15];
+HD void wb_cost_prefetch(WbCore& L, PhaseC& P, int b, int k, int tid) {
+    const size_t rw = ref_row(P, b, k);
+    if (tid < 36) L.tmp[tid] = P.xr[rw * 36 + tid];
+    else if (tid < 48) L.tmp[tid] = P.ur[rw * 12 + tid - 36];
+    if (tid < 12) { L.red[tid] = P.foot_pos[rw * 12 + tid]; L.red[12 + tid] = P.foot_vel[rw * 12 + tid]; }
+    else if (tid < 15) L.red[12 + tid] = P.body_pos[rw * 3 + tid - 12];
+    else if (tid < 19) L.red[13 + tid] = (double)P.ref_contact[rw * 4 + tid - 15];
 }
 // foot-cost Jacobian blocks of the knot: JP (position-type rows, base-translation and velocity columns zero),
 // JW (velocity-type rows [d vel/dq | J]), with per-row weights (dt folded in) and residuals.  `terminal` selects the
@@ -913,15 +914,15 @@ template <int NT>
 HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int reb_active, bool cached = false) {
     WbCore& L = S.c; WbDeriv& D = S.d;
     const int h = P.h; const double dt = P.dt;
-    const size_t kx = ((size_t)b * (h + 1) + k) * 36, ku = ((size_t)b * h + k) * 12, kk = (size_t)b * h + k;
+    const size_t kx = ((size_t)b * (h + 1) + k) * 36, ku = ((size_t)b * h + k) * 12, kk = (size_t)b * h + k, rw = ref_row(P, b, k);
     // the barrier derivative tables only need g, delta, eps of the rollout: their global loads are issued together with x, u
     LQ_STAMP0()
     HS_PHASE(NT,
         // ---- every global read of the knot first (one exposed HBM round trip), the LDS stores afterwards
         const double vx = (tid < 36) ? P.X[kx + tid] : 0.0, vu = (tid < 12) ? P.U[ku + tid] : 0.0;
-        const double vt = (tid < 36) ? P.xr[(size_t)k * 36 + tid] : (tid < 48) ? P.ur[(size_t)k * 12 + tid - 36] : 0.0;
-        const double vf = (tid < 12) ? P.foot_pos[(size_t)k * 12 + tid] : (tid < 15) ? P.body_pos[(size_t)k * 3 + tid - 12] : (tid < 19) ? (double)P.ref_contact[(size_t)k * 4 + tid - 15] : 0.0;
-        const double vv = (tid < 12) ? P.foot_vel[(size_t)k * 12 + tid] : 0.0;
+        const double vt = (tid < 36) ? P.xr[rw * 36 + tid] : (tid < 48) ? P.ur[rw * 12 + tid - 36] : 0.0;
+        const double vf = (tid < 12) ? P.foot_pos[rw * 12 + tid] : (tid < 15) ? P.body_pos[rw * 3 + tid - 12] : (tid < 19) ? (double)P.ref_contact[rw * 4 + tid - 15] : 0.0;
+        const double vv = (tid < 12) ? P.foot_vel[rw * 12 + tid] : 0.0;
         const double vw = (tid < 36) ? P.q[tid] : (tid < 48) ? P.r[tid - 36] : 0.0;
         double gr[2], dr[2], er[2];
         _Pragma("unroll") for (int q = 0; q < 2; q++) { const int c = q * NT + tid; const size_t gi = kk * P.ng + c; const bool in = c < P.ng; gr[q] = in ? P.g[gi] : 1.0; dr[q] = in ? P.delta[gi] : 1.0; er[q] = in ? P.eps[gi] : 0.0; }
@@ -1193,7 +1194,7 @@ HD void wb_lq_terminal(WbLqLds& S, PhaseC& P, PhaseC* Pn, const ModelDev& md, in
     const int h = P.h;
     const size_t kx = ((size_t)b * (h + 1) + h) * 36;
     HS_PHASE(NT, if (tid < 36) L.x[tid] = P.X[kx + tid]; if (tid < 18) { L.acc[tid] = 0.0; L.tau[tid] = 0.0; } if (tid < 12) L.fext[tid] = 0.0;
-             wb_cost_prefetch(L, P, h, tid);)
+             wb_cost_prefetch(L, P, b, h, tid);)
     wb_terms<NT>(L, md, true);
     // d(J v)/dq with psi_kin at (q, v): kinematic lanes only
     wb_dpass<NT>(L, D, md, 0.0, 1.0, 1.0, 0.0, true);

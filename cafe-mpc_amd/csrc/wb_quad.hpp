@@ -242,7 +242,7 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     // references and barrier parameters fetched with the state (one exposed round trip for all of them) and dead before the contact solve's
     // register peak; what needs the dynamics (defect, foot costs, friction pyramid) reads later, ahead of the contact solve (see below).
     const double dt = P.dt;
-    const HS_GLOBAL double* rr = P.rref + (size_t)k * 80;
+    const HS_GLOBAL double* rr = P.rref + ref_row(P, b, k) * 80;
     const size_t gk = kk * P.ng;
     const S zero = S(0.0);
     const S w0 = Q::legc(1.0, 0.0, 0.0, 0.0);      // the replicated base entries are counted once

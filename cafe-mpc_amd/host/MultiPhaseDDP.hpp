@@ -17,6 +17,7 @@
 #include <cstring>
 #include "hsddp.h"
 #include "hsddp_hkd.h"
+#include "hsddp_refs.h"
 
 namespace hsddp {
 
@@ -107,6 +108,16 @@ public:
     void export_hkd_commands(int b0, int nb, int n_steps, double mpc_time, double dt, const double* status_times, const float* pf_in,
                              unsigned int* out, int dst_device = 0) {
         rc_ = hsddp_export_hkd_commands(h_, b0, nb, n_steps, mpc_time, dt, status_times, pf_in, out, dst_device);
+    }
+    // per-problem tracking references of one phase (include/hsddp_refs.h): problems [b0, b0+nb) take `refs` (each [nb][h+1][width], NULL fields
+    // keep their values; device memory when src_device = 1).  hsddp_reconfigure returns the window to the shared references: call again after it.
+    void set_references(int phase, int b0, int nb, const hsddp_refs_t& refs, int src_device = 0) {
+        rc_ = hsddp_set_references(h_, phase, b0, nb, &refs, src_device);
+    }
+    // the references problems [b0, b0+nb) of a phase track, into host arrays of the same layout (NULL skips a field)
+    void get_references(int phase, int b0, int nb, double* xr, double* ur, double* yr, double* foot_pos, double* foot_vel, double* body_pos,
+                        int* ref_contact) {
+        rc_ = hsddp_get_references(h_, phase, b0, nb, xr, ur, yr, foot_pos, foot_vel, body_pos, ref_contact);
     }
     // receding-horizon step (MHPCProblem::update): phase `dphase` continues phase `sphase` of the previous window (sphase < 0: new phase)
     void warm_start_phase(int dphase, MultiPhaseDDP<T>* prev, int sphase, int popped_front) {

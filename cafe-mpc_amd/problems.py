@@ -503,3 +503,67 @@ def hkd_ddp_setting(**kw):
                 AL_active=1, ReB_active=1, MS=1)
     base.update(kw)
     return mhpc_ddp_setting(**base)
+
+
+# --------------------------------------------------------------------------------------------- per-problem references (include/hsddp_refs.h)
+_REF_POINTERS = ("xr", "ur", "yr", "foot_pos", "foot_vel", "body_pos", "ref_contact")
+
+
+def _structure_bytes(d):
+    """The descriptor's bytes with its reference pointers cleared: model, horizon, dt, contacts, weights, limits, constraint parameters."""
+    c = PhaseDesc.from_buffer_copy(d)
+    for name in _REF_POINTERS:
+        setattr(c, name, None)
+    return C.string_at(C.addressof(c), C.sizeof(c))
+
+
+def stack_references(phase_lists):
+    """Per-phase references of B phase lists that differ only in their references, stacked for Solver.set_references: a list (one entry per
+    phase) of dicts {name: [B, h+1, width]}.  Raises ValueError if the lists differ in phase count, model, horizon, dt, contacts or cost and
+    constraint structure (every descriptor field except the reference pointers)."""
+    if not phase_lists:
+        raise ValueError("stack_references: no phase lists")
+    first = phase_lists[0]
+    for j, pl in enumerate(phase_lists):
+        if len(pl) != len(first):
+            raise ValueError(f"phase list {j} has {len(pl)} phases, list 0 has {len(first)}")
+        for i, (a, b) in enumerate(zip(first, pl)):
+            if _structure_bytes(a["desc"]) != _structure_bytes(b["desc"]):
+                raise ValueError(f"phase {i} of list {j} differs from list 0 in more than its references")
+    out = []
+    for i, p in enumerate(first):
+        n, m, py = MODEL_DIMS[p["desc"].model]
+        names = [k for k in _REF_POINTERS if k != "yr" or py > 0]
+        out.append({k: np.stack([pl[i]["bufs"][k] for pl in phase_lists]) for k in names})
+    return out
+
+
+def translate_references(phases, dx, dy):
+    """A copy of `phases` moved by (dx, dy) in the world x-y plane: the references and the nominal state Xbar.  Moved entries:
+    whole body and SRB: xr[:, 0:2]; HKD: xr[:, 3:5] and the foothold entries xr[:, 12+3l : 14+3l] of the knots where leg l is in reference
+    contact (a swing leg holds joint angles there); every model: foot_pos x, y of each foot and body_pos x, y.  Xbar moves like xr (the HKD
+    footholds by the same ref_contact rows)."""
+    out = []
+    for p in phases:
+        d = PhaseDesc.from_buffer_copy(p["desc"])
+        bufs = {k: v.copy() for k, v in p["bufs"].items()}
+        xbar = np.array(p["Xbar"], dtype=np.float64, copy=True)
+        shift = np.array([dx, dy], dtype=np.float64)
+        if d.model == MODEL_HKD:
+            rc = bufs["ref_contact"]
+            for a in (bufs["xr"], xbar):
+                a[:, 3:5] += shift
+                for l in range(4):
+                    st = rc[:, l] > 0
+                    a[st, 12 + 3 * l:14 + 3 * l] += shift
+        else:
+            bufs["xr"][:, 0:2] += shift
+            xbar[:, 0:2] += shift
+        for l in range(4):
+            bufs["foot_pos"][:, 3 * l:3 * l + 2] += shift
+        bufs["body_pos"][:, 0:2] += shift
+        for k, v in bufs.items():
+            setattr(d, k, v.ctypes.data_as(IP if k == "ref_contact" else DP))
+        q = dict(p); q.update(desc=d, bufs=bufs, Xbar=xbar)
+        out.append(q)
+    return out
