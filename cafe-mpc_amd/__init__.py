@@ -15,6 +15,8 @@ from . import launch  # noqa: F401
 from . import ensemble  # noqa: F401
 from .ensemble import ScheduleEnsemble, select_rows  # noqa: F401
 from . import hkd_command  # noqa: F401
+from . import sim  # noqa: F401
+from .sim import Simulation  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
 HIP_LIB_PATH = _os.path.join(_HERE, "libhsddp_hip.so")

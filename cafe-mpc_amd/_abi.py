@@ -196,6 +196,39 @@ def bind_refs(lib):
     lib.hsddp_get_references.argtypes = [H, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
     return lib
 
+
+# include/hsddp_sim.h: closed-loop rollouts of the solved policy from perturbed initial states (libhsddp_hip.so only)
+SIM_EXPORTS = ["hsddp_sim_create", "hsddp_sim_run", "hsddp_sim_get_rows", "hsddp_sim_get_traj", "hsddp_sim_device_final",
+               "hsddp_sim_get_kernel_time_ms", "hsddp_sim_destroy"]
+
+
+class SimRow(C.Structure):
+    """hsddp_sim_row_t"""
+    _fields_ = [("dev_q", C.c_double), ("dev_v", C.c_double), ("min_height", C.c_double), ("max_torque", C.c_double),
+                ("first_bad", C.c_int), ("pad", C.c_int)]
+
+
+SIM_ROW_DTYPE = np.dtype([("dev_q", "<f8"), ("dev_v", "<f8"), ("min_height", "<f8"), ("max_torque", "<f8"), ("first_bad", "<i4"), ("pad", "<i4")])
+
+
+def bind_sim(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_sim.h.  Raises if the library lacks any of them."""
+    missing = [s for s in SIM_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the simulation entry points {missing}")
+    H = C.c_void_p
+    lib.hsddp_sim_create.argtypes = [H, C.c_int, C.c_int, C.c_int, C.POINTER(H)]
+    lib.hsddp_sim_run.argtypes = [H, C.c_void_p, C.c_int]
+    lib.hsddp_sim_get_rows.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.hsddp_sim_get_traj.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.hsddp_sim_device_final.argtypes = [H]
+    lib.hsddp_sim_device_final.restype = C.c_void_p
+    lib.hsddp_sim_get_kernel_time_ms.argtypes = [H, C.POINTER(C.c_float)]
+    lib.hsddp_sim_destroy.argtypes = [H]
+    lib.hsddp_sim_destroy.restype = None
+    return lib
+
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -450,6 +483,14 @@ class Solver:
         self._ck(self.lib.hsddp_get_references(self.h, phase, b0, nb, *[out[n].ctypes.data if n in out else None for n in REF_FIELDS]),
                  "get_references")
         return out
+
+    def simulate(self, x0, n_steps, keep_traj=False):
+        """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)
+        over the first n_steps whole-body control knots (include/hsddp_sim.h): dict with rows (structured array [batch, R] of dev_q, dev_v,
+        min_height, max_torque, first_bad), x_final [batch, R, 36] and, with keep_traj, X [batch, R, n_steps + 1, 36] and U [batch, R, n_steps, 12].
+        sim.Simulation keeps the device object across calls."""
+        from . import sim
+        return sim.simulate(self, x0, n_steps, keep_traj)
 
     def get_history(self, problem=0, cap=4096):
         """MultiPhaseDDP::get_solver_info(cost, dyn_feas, eqn_feas, ineq_feas) (MultiPhaseDDP.h:85): the four float history buffers."""

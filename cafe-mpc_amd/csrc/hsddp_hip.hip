@@ -18,6 +18,7 @@
 #include "hsddp_ensemble.h"
 #include "hsddp_hkd.h"
 #include "hsddp_refs.h"
+#include "hsddp_sim.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -28,6 +29,7 @@
 #include "ensemble.hpp"
 #include "hkd_pack.hpp"
 #include "refs.hpp"
+#include "wb_sim.hpp"
 
 using namespace hs;
 
@@ -649,6 +651,7 @@ struct hsddp_handle {
     hipStream_t stream = nullptr;
     float solve_ms = 0;
     bool cache_valid = false;         // every problem has been rolled out since its trajectories were last set from outside: P.kc matches X, U
+    int window_gen = 0;               // counts hsddp_reconfigure calls: objects that hold a map of the window (hsddp_sim.h) notice that it moved
     // kernel timing
     std::vector<std::string> kname; std::vector<double> kms; std::vector<long long> kcnt;
     struct Ev { hipEvent_t a, b; int id; };
@@ -897,7 +900,7 @@ int hsddp_reconfigure(hsddp_handle_t* h, int n_phases, const hsddp_phase_desc_t*
         if (!h->gen_allocs.empty()) { for (void* p : h->gen_allocs) hipFree(p); h->gen_allocs.clear(); }      // storage of hsddp_create: first tick only
         h->cur_arena = g;
     }
-    h->ph = np; h->nph = n_phases; h->nslots = (int)sp.size();
+    h->ph = np; h->nph = n_phases; h->nslots = (int)sp.size(); h->window_gen++;
     h->probe_ok = true; for (int i = 0; i < n_phases; i++) if (!phases[i].shooting && phases[i].model != HSDDP_MODEL_WB) h->probe_ok = false;
     h->has_hkd = false; for (int i = 0; i < n_phases; i++) if (phases[i].model == HSDDP_MODEL_HKD) h->has_hkd = true;
     h->cache_valid = false;
@@ -1682,6 +1685,113 @@ int hsddp_get_references(hsddp_handle_t* h, int phase, int b0, int nb, double* x
             for (int i = 1; i < nb; i++) memcpy((char*)dst[s] + (size_t)i * row, dst[s], row);
         }
     }
+    return HSDDP_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ closed-loop policy simulation (hsddp_sim.h)
+}  // extern "C"
+struct hsddp_sim {
+    hsddp_handle* h = nullptr;
+    int R = 0, n_steps = 0, keep = 0, gen = 0;
+    int* d_map = nullptr;                                  // [3][n_steps] step -> phase, knot, reset map behind the step (wb_sim.hpp)
+    double *d_x0 = nullptr, *d_final = nullptr, *d_rows = nullptr, *d_X = nullptr, *d_U = nullptr;      // [B R] x 36 / 36 / SIM_ROW / (n_steps+1) 36 / n_steps 12
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
+};
+static void sim_free(hsddp_sim* s) {
+    if (!s) return;
+    hipSetDevice(s->h->device);
+    if (s->h->stream) hipStreamSynchronize(s->h->stream);
+    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U};
+    for (void* q : p) if (q) hipFree(q);
+    if (s->ev0) hipEventDestroy(s->ev0);
+    if (s->ev1) hipEventDestroy(s->ev1);
+    delete s;
+}
+static bool sim_range_ok(const hsddp_sim* s, int b0, int nb) { return s && nb > 0 && b0 >= 0 && b0 <= s->h->batch - nb; }
+
+extern "C" {
+
+int hsddp_sim_create(hsddp_handle_t* h, int n_samples, int n_steps, int keep_traj, hsddp_sim_t** out) {
+    if (!h || !out || n_samples <= 0 || n_steps <= 0) return HSDDP_EINVAL;
+    // step -> (phase, knot) over the leading whole-body control knots, as hsddp_export_mpc_command walks them; the reset map of a phase is applied
+    // behind its last knot when the window goes on
+    std::vector<int> map(3 * (size_t)n_steps, 0);
+    int n = 0;
+    for (int i = 0; i < h->nph && n < n_steps; i++) {
+        if (h->ph[i].model != HSDDP_MODEL_WB) break;
+        for (int k = 0; k < h->ph[i].h && n < n_steps; k++, n++) {
+            map[n] = i; map[n_steps + n] = k;
+            map[2 * (size_t)n_steps + n] = (k == h->ph[i].h - 1 && n + 1 < n_steps && h->ph[i].has_impact) ? 1 : 0;
+        }
+    }
+    if (n < n_steps) return HSDDP_EINVAL;
+    const size_t total = (size_t)h->batch * n_samples;
+    if (total >= ((size_t)1 << 31)) return HSDDP_ENOTSUP;      // quads are indexed in 32 bits
+    HIPCK(hipSetDevice(h->device));
+    hsddp_sim* s = new hsddp_sim();
+    s->h = h; s->R = n_samples; s->n_steps = n_steps; s->keep = keep_traj ? 1 : 0; s->gen = h->window_gen;
+#define SIM_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); sim_free(s); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
+    SIM_CK(hipMalloc((void**)&s->d_map, map.size() * sizeof(int)));
+    SIM_CK(hipMalloc((void**)&s->d_x0, total * 36 * 8));
+    SIM_CK(hipMalloc((void**)&s->d_final, total * 36 * 8));
+    SIM_CK(hipMalloc((void**)&s->d_rows, total * SIM_ROW * 8));
+    if (s->keep) { SIM_CK(hipMalloc((void**)&s->d_X, total * (n_steps + 1) * 36 * 8)); SIM_CK(hipMalloc((void**)&s->d_U, total * n_steps * 12 * 8)); }
+    SIM_CK(hipEventCreate(&s->ev0)); SIM_CK(hipEventCreate(&s->ev1));
+    SIM_CK(hipMemcpy(s->d_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+    SIM_CK(hipMemset(s->d_final, 0, total * 36 * 8)); SIM_CK(hipMemset(s->d_rows, 0, total * SIM_ROW * 8));
+#undef SIM_CK
+    *out = s; return HSDDP_OK;
+}
+
+void hsddp_sim_destroy(hsddp_sim_t* s) { sim_free(s); }
+
+int hsddp_sim_run(hsddp_sim_t* s, const double* x0, int src_device) {
+    if (!s || !x0) return HSDDP_EINVAL;
+    hsddp_handle* h = s->h;
+    if (s->gen != h->window_gen) return HSDDP_EINVAL;      // hsddp_reconfigure moved the window: the step map is that of the old one
+    HIPCK(hipSetDevice(h->device));
+    const size_t total = (size_t)h->batch * s->R;
+    if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipEventRecord(s->ev0, h->stream));
+    hipLaunchKernelGGL(k_sim_quad, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
+                       src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(s->ev1, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    s->timed = true;
+    return HSDDP_OK;
+}
+
+int hsddp_sim_get_rows(hsddp_sim_t* s, int b0, int nb, hsddp_sim_row_t* rows, double* x_final) {
+    if (!sim_range_ok(s, b0, nb) || !rows) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(s->h->device));
+    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R;
+    std::vector<double> r(cnt * SIM_ROW);
+    HIPCK(hipMemcpy(r.data(), s->d_rows + off * SIM_ROW, r.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < cnt; i++) {
+        const double* q = &r[i * SIM_ROW];
+        rows[i].dev_q = q[0]; rows[i].dev_v = q[1]; rows[i].min_height = q[2]; rows[i].max_torque = q[3]; rows[i].first_bad = (int)q[4]; rows[i].pad = 0;
+    }
+    if (x_final) HIPCK(hipMemcpy(x_final, s->d_final + off * 36, cnt * 36 * 8, hipMemcpyDeviceToHost));
+    return HSDDP_OK;
+}
+
+int hsddp_sim_get_traj(hsddp_sim_t* s, int b0, int nb, double* X, double* U) {
+    if (!sim_range_ok(s, b0, nb) || !s->keep) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(s->h->device));
+    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R, sx = (size_t)(s->n_steps + 1) * 36, su = (size_t)s->n_steps * 12;
+    if (X) HIPCK(hipMemcpy(X, s->d_X + off * sx, cnt * sx * 8, hipMemcpyDeviceToHost));
+    if (U) HIPCK(hipMemcpy(U, s->d_U + off * su, cnt * su * 8, hipMemcpyDeviceToHost));
+    return HSDDP_OK;
+}
+
+const double* hsddp_sim_device_final(hsddp_sim_t* s) { return s ? s->d_final : nullptr; }
+
+int hsddp_sim_get_kernel_time_ms(hsddp_sim_t* s, float* ms) {
+    if (!s || !ms || !s->timed) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(s->h->device));
+    HIPCK(hipEventElapsedTime(ms, s->ev0, s->ev1));
     return HSDDP_OK;
 }
 

@@ -1,0 +1,531 @@
+// Closed-loop rollout of a solved whole-body policy from perturbed initial states, on LANE QUADS (include/hsddp_sim.h).
+//
+// One quad of lanes per (problem, sample), lane = leg as in wb_quad.hpp.  The quad keeps the state in registers and walks the first
+// n_steps control knots of the handle in a loop:
+//     u = Ubar_k + K_k (x - Xbar_k) ;  x <- x + dt (v, qdd(x, u))          (the knot step of the rollout: WBM.cpp:17-57, 368-424)
+//     at the end of a phase, if the window goes on:  v <- v+ of the impact on the feet that touch down   (WBM.cpp:178-206, 427-456)
+// which is what the single-shooting chain of hsddp_hybrid_rollout(eps = 0, MS = 0) computes from the same initial state - without the costs,
+// defects and constraint values, without a write to the handle, and for R samples per problem.  No barrier; LDS only as a lane-private parking
+// place of the loop-carried values across the contact solve.
+//
+// The sixteen quads of a wave are consecutive (problem, sample) pairs, sample fastest: with R a multiple of 16 a wave holds sixteen samples
+// of ONE problem, and Xbar, Ubar and the 432 gains of a knot are the same addresses in every quad (each line is touched once per wave).
+//
+// wbs_contact_dynamics is the state -> (qdd, lambda) part of wbq_rollout_knot (wb_quad.hpp: composite inertias, bias forces, foot Jacobian,
+// block factor, block contact solve) COPIED here on purpose: sharing it would mean editing wbq_rollout_knot, and k_rollout_quad has to keep
+// compiling to exactly what it compiles to now.  About 300 lines are duplicated; a change to the dynamics there has to be made here too
+// (tests/test_sim_host.py and tests/test_sim_gpu.py hold the two against the oracle and against each other).  The copy takes the contact set,
+// the mode and the Gram damping as wave-uniform arguments, because the impact is the same solve in another mode (wb_kkt_direct, wb_knot.hpp):
+//     mode 0 (forwardDynamics):  y = L^-1 (tau - h), lam = G^-1 (-X^T y - gam), qdd = L^-T (y + X lam), damping 1e-12
+//     mode 1 (impulseDynamics):  contact set = the feet that touch down, lam = G^-1 (-Jc v), v+ = v + L^-T X lam, damping 0
+// (Jc v of a foot is its velocity, which the bias pass leaves behind anyway; y = 0, so no product with L^T is needed.)
+#pragma once
+#include "wb_quad.hpp"
+
+namespace hs {
+
+#ifdef HS_HOST_EMU
+inline int wbs_uniform(int v) { return v; }
+#else
+HD int wbs_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }      // a value every lane of the wave holds alike: into a scalar register
+#endif
+#ifndef SIM_PREFETCH
+// SIM_PREFETCH 1: the next knot's Xbar / Ubar / K rows (they do not depend on the state) are fetched ahead of the current knot's contact solve
+// instead of at the head of their own knot.  Measured on the MI355X, config 3, 4 096 problems x 16 samples x 200 steps, before the loop-carried
+// values were parked in LDS: 49.0 ms against 13.5 ms - the 129 doubles held across the contact solve pushed the kernel from 304 to 1 344 bytes of
+// scratch per lane, and the spill traffic costs far more than the exposed round trip of loads that mostly hit the L2 (a build that reads one
+// gain per torque instead of 108 put that round trip at 1.9 ms of the 13.5).  With the parking it is still 1 064 bytes (make resources).  Off.
+#define SIM_PREFETCH 0
+#endif
+#ifndef HS_HOST_EMU
+// QD whose lane index is laundered through an empty asm at every use: nothing derived from it (leg signs, link inertias, selection masks) is
+// loop-invariant to the compiler, which would otherwise compute all of it once in front of the step loop and hold it in registers across the
+// whole knot (HS_PHASE does the same with tid, hs_common.hpp)
+struct QS : QD {
+    static HD int lane() { int l = threadIdx.x & 3; asm volatile("" : "+v"(l)); return l; }
+    static HD S legc(double a, double b, double c, double d) { const int l = lane(); return l == 0 ? a : l == 1 ? b : l == 2 ? c : d; }
+    template <class PT> static HD S ld(PT p, size_t off, int stride) { return p[off + (size_t)(lane() * stride)]; }
+    template <class PT> static HD void st(PT p, size_t off, int stride, S x) { p[off + (size_t)(lane() * stride)] = x; }
+    template <class PT> static HD void st0(PT p, size_t off, S x) { if (lane() == 0) p[off] = x; }
+};
+#endif
+template <class Q, class S> HD S wbs_abs(const S& a) { return Q::sel(Q::gt(S(0.0), a), -a, a); }
+template <class Q, class S> HD S wbs_max(const S& a, const S& b) { return Q::sel(Q::gt(b, a), b, a); }
+template <class Q, class S> HD S wbs_qmax(const S& a) { return -Q::vmin(-a); }      // maximum over the four lanes of the quad
+
+// Contact dynamics of one state on a lane quad.  cmask: bit l = leg l is in the contact set; mode, damping, bg_alpha: see the head of the file
+// (all four wave-uniform).  out_b (6, replicated) / out_l (the lane's leg): mode 0 the accelerations qdd, mode 1 the velocities after the impact.
+template <class Q, class S = typename Q::S>
+HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double damping, double bg_alpha, const S (&qb)[6], const S (&vb)[6], const S (&ql)[3],
+                             const S (&vl_)[3], const S (&ul)[3], S (&out_b)[6], V3<S>& out_l) {
+    const S zero = S(0.0);
+    const double m0 = mode == 0 ? 1.0 : 0.0, m1 = 1.0 - m0;      // (1.0 * x is x: mode 0 is the arithmetic of wbq_rollout_knot)
+    const S sx = Q::legc(1.0, 1.0, -1.0, -1.0), sy = Q::legc(1.0, -1.0, 1.0, -1.0);
+    const double cps = md.cpsi_dyn, sps = md.spsi_dyn;      // every term of the rollout is a Pinocchio-equivalent one (quirk xii)
+    Base3<S> T; S ca, sa, ch, sh, ck, sk;
+    {   // the three base angles: lane l < 3 evaluates angle 3 + l (lane 3 repeats the last), the quad reads the results
+        const S ang = Q::legc(1, 0, 0, 0) * qb[3] + Q::legc(0, 1, 0, 0) * qb[4] + Q::legc(0, 0, 1, 1) * qb[5];
+        S sb, cb_; Q::sincos(ang, sb, cb_);
+        T.s3 = Q::template get<0>(sb); T.c3 = Q::template get<0>(cb_); T.s4 = Q::template get<1>(sb); T.c4 = Q::template get<1>(cb_); T.s5 = Q::template get<2>(sb); T.c5 = Q::template get<2>(cb_);
+    }
+    Q::sincos(ql[0], sa, ca); Q::sincos(ql[1], sh, ch); Q::sincos(ql[2], sk, ck);
+    const V3<S> pa = {sx * 0.19, sy * 0.049, S(0.0)}, ph = {S(0.0), sy * 0.062, S(0.0)}, pk = {S(0.0), S(0.0), S(-0.209)};
+
+    // ---- composite inertias, leg -> trunk (frames: K shank, H thigh, A abad, B trunk; v_H = Ry(qk) v_K, v_A = Rz(psi) Ry(qh) v_H, v_B = Rx(qa) v_A)
+    const RBI<S> IK = rbi_link<S>(0.064, zero, zero, S(-0.061), S(0.000245), zero, zero, S(0.000248), zero, S(0.000006));
+    RBI<S> IH = rbi_link<S>(0.634, zero, sy * 0.016, S(-0.02), S(0.001983), sy * 0.000245, S(0.000013), S(0.002103), sy * 0.0000015, S(0.000408));
+    IH = rbi_add(IH, rbi_shift(IK.m, rot<1>(ck, sk, IK.h), sym_rot<1>(ck, sk, IK.I), pk));
+    RBI<S> IA = rbi_link<S>(0.54, zero, sy * 0.036, zero, S(0.000381), sy * 0.000058, S(0.00000045), S(0.000560), sy * 0.00000095, S(0.000444));
+    IA = rbi_add(IA, rbi_shift(IH.m, rot<2>(S(cps), S(sps), rot<1>(ch, sh, IH.h)), sym_rot<2>(S(cps), S(sps), sym_rot<1>(ch, sh, IH.I)), ph));
+    const RBI<S> IBl = rbi_shift(IA.m, rot<0>(ca, sa, IA.h), sym_rot<0>(ca, sa, IA.I), pa);
+    // whole robot about the trunk origin: trunk + the four legs (sums over the quad)
+    RBI<S> IT;
+    IT.m = Q::sum(IBl.m) + 3.3; IT.h = {Q::sum(IBl.h.x), Q::sum(IBl.h.y), Q::sum(IBl.h.z)};
+    IT.I = {Q::sum(IBl.I.xx) + 0.011253, Q::sum(IBl.I.xy), Q::sum(IBl.I.xz), Q::sum(IBl.I.yy) + 0.036203, Q::sum(IBl.I.yz), Q::sum(IBl.I.zz) + 0.042673};
+    // ---- mass-matrix blocks of the leg: D (3x3, joints abad / hip / knee) and Ct[c][j] = M(base joint c, leg joint j)
+    S Ct[6][3], d_aa, d_ha, d_hh, d_ka, d_kh, d_kk;
+    {
+        // knee: unit acceleration about y of K
+        V3<S> n = {IK.I.xy, IK.I.yy, IK.I.yz}, f = {IK.h.z, zero, -IK.h.x};
+        d_kk = n.y;
+        f = rot<1>(ck, sk, f); n = rot<1>(ck, sk, n); force_shift(pk, n, f);                              // -> H
+        d_kh = n.y;
+        f = rot<2>(S(cps), S(sps), rot<1>(ch, sh, f)); n = rot<2>(S(cps), S(sps), rot<1>(ch, sh, n)); force_shift(ph, n, f);      // -> A
+        d_ka = n.x;
+        f = rot<0>(ca, sa, f); n = rot<0>(ca, sa, n); force_shift(pa, n, f);                              // -> B
+        S t[6]; base_walk(T, f, n, t);
+        _Pragma("unroll") for (int c = 0; c < 6; c++) Ct[c][2] = t[c];
+    }
+    {
+        V3<S> n = {IH.I.xy, IH.I.yy, IH.I.yz}, f = {IH.h.z, zero, -IH.h.x};                               // hip: about y of H
+        d_hh = n.y;
+        f = rot<2>(S(cps), S(sps), rot<1>(ch, sh, f)); n = rot<2>(S(cps), S(sps), rot<1>(ch, sh, n)); force_shift(ph, n, f);
+        d_ha = n.x;
+        f = rot<0>(ca, sa, f); n = rot<0>(ca, sa, n); force_shift(pa, n, f);
+        S t[6]; base_walk(T, f, n, t);
+        _Pragma("unroll") for (int c = 0; c < 6; c++) Ct[c][1] = t[c];
+    }
+    {
+        V3<S> n = {IA.I.xx, IA.I.xy, IA.I.xz}, f = {zero, -IA.h.z, IA.h.y};                               // abad: about x of A
+        d_aa = n.x;
+        f = rot<0>(ca, sa, f); n = rot<0>(ca, sa, n); force_shift(pa, n, f);
+        S t[6]; base_walk(T, f, n, t);
+        _Pragma("unroll") for (int c = 0; c < 6; c++) Ct[c][0] = t[c];
+    }
+    // ---- base block B (6x6, replicated): unit accelerations of the base joints seen in trunk axes, force of the WHOLE robot, walked back
+    S Bm[21];
+    {
+        V3<S> acc[6][2];      // [c][0] angular, [c][1] linear
+        const V3<S> z3 = {zero, zero, zero};
+        const V3<S> ex = {S(1.0), zero, zero}, ey = {zero, S(1.0), zero}, ez = {zero, zero, S(1.0)};
+        auto w2b = [&](const V3<S>& w) { return rotT<0>(T.c5, T.s5, rotT<1>(T.c4, T.s4, rotT<2>(T.c3, T.s3, w))); };
+        acc[0][0] = z3; acc[0][1] = w2b(ex); acc[1][0] = z3; acc[1][1] = w2b(ey); acc[2][0] = z3; acc[2][1] = w2b(ez);
+        acc[3][0] = rotT<0>(T.c5, T.s5, rotT<1>(T.c4, T.s4, ez)); acc[3][1] = z3;
+        acc[4][0] = rotT<0>(T.c5, T.s5, ey); acc[4][1] = z3;
+        acc[5][0] = ex; acc[5][1] = z3;
+        _Pragma("unroll")
+        for (int c = 0; c < 6; c++) {
+            V3<S> n, f; rbi_apply(IT, acc[c][0], acc[c][1], n, f);
+            S t[6]; base_walk(T, f, n, t);
+            _Pragma("unroll") for (int i = c; i < 6; i++) Bm[tri(i, c)] = t[i];
+        }
+    }
+    // ---- bias forces: one Newton-Euler pass down and up the leg with the knot's velocities, zero acceleration, gravity as a base acceleration
+    S hl[3], hb[6]; V3<S> fpos, fvel, jdv;
+    V3<S> rB;      // foot relative to the trunk origin, trunk axes (for the Jacobian below)
+    V3<S> dA, dH;  // foot relative to the abad origin (trunk axes after Rx: see below) / hip origin, A axes
+    {
+        V3<S> om = {zero, zero, zero}, aa = om, vl = {vb[0], vb[1], vb[2]}, al = {zero, zero, S(GRAV)};
+        auto revj = [&](auto AXT, const S& c, const S& s, const S& qd, V3<S>& om_, V3<S>& vl_2, V3<S>& aa_, V3<S>& al_) {
+            constexpr int AX = decltype(AXT)::value;
+            V3<S> o = rotT<AX>(c, s, om_), v = rotT<AX>(c, s, vl_2), a2 = rotT<AX>(c, s, aa_), a1 = rotT<AX>(c, s, al_);
+            if (AX == 0) { o.x = o.x + qd; a2.y = a2.y + o.z * qd; a2.z = a2.z - o.y * qd; a1.y = a1.y + v.z * qd; a1.z = a1.z - v.y * qd; }
+            if (AX == 1) { o.y = o.y + qd; a2.x = a2.x - o.z * qd; a2.z = a2.z + o.x * qd; a1.x = a1.x - v.z * qd; a1.z = a1.z + v.x * qd; }
+            if (AX == 2) { o.z = o.z + qd; a2.x = a2.x + o.y * qd; a2.y = a2.y - o.x * qd; a1.x = a1.x + v.y * qd; a1.y = a1.y - v.x * qd; }
+            om_ = o; vl_2 = v; aa_ = a2; al_ = a1;
+        };
+        using A0 = IC<0>; using A1 = IC<1>; using A2 = IC<2>;
+        revj(A2{}, T.c3, T.s3, vb[3], om, vl, aa, al); revj(A1{}, T.c4, T.s4, vb[4], om, vl, aa, al); revj(A0{}, T.c5, T.s5, vb[5], om, vl, aa, al);
+        // force of a link: I a + v x* I v with the link's inertia about its origin
+        auto link_force = [&](const RBI<S>& I, const V3<S>& o, const V3<S>& v, const V3<S>& a2, const V3<S>& a1, V3<S>& n, V3<S>& f) {
+            const V3<S> hl_ = scale(I.m, v) + cross(o, I.h);                 // linear momentum  m v + om x h
+            const V3<S> ha = symmul(I.I, o) + cross(I.h, v);                 // angular momentum about the origin
+            rbi_apply(I, a2, a1, n, f);
+            f = f + cross(o, hl_);
+            n = n + cross(o, ha) + cross(v, hl_);
+        };
+        // trunk (own link only; its wrench joins the legs' in the quad sum, so only lane 0's copy is counted)
+        const RBI<S> Itr = rbi_link<S>(3.3, zero, zero, zero, S(0.011253), zero, zero, S(0.036203), zero, S(0.042673));
+        V3<S> nb, fb; link_force(Itr, om, vl, aa, al, nb, fb);
+        const S l0 = Q::legc(1.0, 0.0, 0.0, 0.0);
+        nb = scale(l0, nb); fb = scale(l0, fb);
+        // down the leg
+        V3<S> o1 = om, a1 = aa, v1 = vl + cross(om, pa), l1 = al + cross(aa, pa);
+        revj(A0{}, ca, sa, vl_[0], o1, v1, a1, l1);
+        const RBI<S> Iab = rbi_link<S>(0.54, zero, sy * 0.036, zero, S(0.000381), sy * 0.000058, S(0.00000045), S(0.000560), sy * 0.00000095, S(0.000444));
+        V3<S> n1, f1; link_force(Iab, o1, v1, a1, l1, n1, f1);
+        V3<S> o2 = o1, a2 = a1, v2 = v1 + cross(o1, ph), l2 = l1 + cross(a1, ph);
+        o2 = rotT<2>(S(cps), S(sps), o2); v2 = rotT<2>(S(cps), S(sps), v2); a2 = rotT<2>(S(cps), S(sps), a2); l2 = rotT<2>(S(cps), S(sps), l2);
+        revj(A1{}, ch, sh, vl_[1], o2, v2, a2, l2);
+        const RBI<S> Ith = rbi_link<S>(0.634, zero, sy * 0.016, S(-0.02), S(0.001983), sy * 0.000245, S(0.000013), S(0.002103), sy * 0.0000015, S(0.000408));
+        V3<S> n2, f2; link_force(Ith, o2, v2, a2, l2, n2, f2);
+        V3<S> o3 = o2, a3 = a2, v3 = v2 + cross(o2, pk), l3 = l2 + cross(a2, pk);
+        revj(A1{}, ck, sk, vl_[2], o3, v3, a3, l3);
+        V3<S> n3, f3; link_force(IK, o3, v3, a3, l3, n3, f3);
+        // foot point (0, 0, -0.195) in K: velocity, classical acceleration, position
+        const V3<S> rf = {zero, zero, S(-0.195)};
+        const V3<S> vp = v3 + cross(o3, rf), ap = l3 + cross(a3, rf) + cross(o3, vp);
+        auto up = [&](V3<S> w) {      // K -> world
+            w = rot<1>(ck, sk, w); w = rot<1>(ch, sh, w); w = rot<2>(S(cps), S(sps), w); w = rot<0>(ca, sa, w);
+            w = rot<0>(T.c5, T.s5, w); w = rot<1>(T.c4, T.s4, w); w = rot<2>(T.c3, T.s3, w); return w;
+        };
+        fvel = up(vp); jdv = up(ap); jdv.z = jdv.z - GRAV;
+        const V3<S> rK = rot<1>(ck, sk, rf);                            // foot relative to the knee origin, H axes
+        const V3<S> rH = pk + rK;                                       // ... relative to the hip origin, H axes
+        dH = rot<2>(S(cps), S(sps), rot<1>(ch, sh, rH));                // ... relative to the hip origin, A axes
+        const V3<S> rA = ph + dH;                                       // ... relative to the abad origin, A axes
+        dA = rot<0>(ca, sa, rA);                                        // ... relative to the abad origin, trunk axes
+        rB = pa + dA;
+        const V3<S> rW = rot<2>(T.c3, T.s3, rot<1>(T.c4, T.s4, rot<0>(T.c5, T.s5, rB)));
+        fpos = V3<S>{qb[0], qb[1], qb[2]} + rW;
+        // back up the leg
+        hl[2] = n3.y;
+        V3<S> fu = rot<1>(ck, sk, f3), nu = rot<1>(ck, sk, n3);
+        f2 = f2 + fu; n2 = n2 + nu + cross(pk, fu);
+        hl[1] = n2.y;
+        fu = rot<2>(S(cps), S(sps), rot<1>(ch, sh, f2)); nu = rot<2>(S(cps), S(sps), rot<1>(ch, sh, n2));
+        f1 = f1 + fu; n1 = n1 + nu + cross(ph, fu);
+        hl[0] = n1.x;
+        fu = rot<0>(ca, sa, f1); nu = rot<0>(ca, sa, n1);
+        fb = fb + fu; nb = nb + nu + cross(pa, fu);
+        fb = {Q::sum(fb.x), Q::sum(fb.y), Q::sum(fb.z)}; nb = {Q::sum(nb.x), Q::sum(nb.y), Q::sum(nb.z)};
+        base_walk(T, fb, nb, hb);
+    }
+    // ---- foot Jacobian of the leg, world axes: Ja (3 x 3 over abad, hip, knee), Jb (3 x 6 over the base joints) - geometric form axis x arm
+    const S cl = Q::legc((cmask & 1) ? 1.0 : 0.0, (cmask & 2) ? 1.0 : 0.0, (cmask & 4) ? 1.0 : 0.0, (cmask & 8) ? 1.0 : 0.0);      // contact flag of the lane's leg
+    M33<S> Ja; S Jb[3][6];
+    {
+        auto b2w = [&](const V3<S>& w) { return rot<2>(T.c3, T.s3, rot<1>(T.c4, T.s4, rot<0>(T.c5, T.s5, w))); };
+        const V3<S> ex = {S(1.0), zero, zero}, ey = {zero, S(1.0), zero}, ez = {zero, zero, S(1.0)};
+        const V3<S> jk = b2w(rot<0>(ca, sa, rot<2>(S(cps), S(sps), rot<1>(ch, sh, cross(ey, rot<1>(ck, sk, V3<S>{zero, zero, S(-0.195)}))))));     // knee axis y (H axes) x arm from the knee
+        const V3<S> jh = b2w(rot<0>(ca, sa, cross(rot<2>(S(cps), S(sps), ey), dH)));                                                              // hip axis: Rz(psi) e_y in A axes
+        const V3<S> ja = b2w(cross(ex, dA));                                                                                                       // abad axis x of the trunk
+        Ja.r[0] = {ja.x, jh.x, jk.x}; Ja.r[1] = {ja.y, jh.y, jk.y}; Ja.r[2] = {ja.z, jh.z, jk.z};
+        const V3<S> rW = b2w(rB);
+        const V3<S> a3 = ez, a4 = rot<2>(T.c3, T.s3, ey), a5 = rot<2>(T.c3, T.s3, rot<1>(T.c4, T.s4, ex));
+        const V3<S> j3 = cross(a3, rW), j4 = cross(a4, rW), j5 = cross(a5, rW);
+        Jb[0][0] = S(1.0); Jb[0][1] = zero; Jb[0][2] = zero; Jb[1][0] = zero; Jb[1][1] = S(1.0); Jb[1][2] = zero; Jb[2][0] = zero; Jb[2][1] = zero; Jb[2][2] = S(1.0);
+        Jb[0][3] = j3.x; Jb[1][3] = j3.y; Jb[2][3] = j3.z; Jb[0][4] = j4.x; Jb[1][4] = j4.y; Jb[2][4] = j4.z; Jb[0][5] = j5.x; Jb[1][5] = j5.y; Jb[2][5] = j5.z;
+    }
+    // ---- contact solve, block form.  L = [ blockdiag(L_l) 0 ; E  L_S ],  E_l = Ct L_l^-T (6 x 3),  S = B - sum_l E_l E_l^T
+    const Chol3<S> Ll = chol3<Q, S>(d_aa, d_ha, d_hh, d_ka, d_kh, d_kk);
+    S E[6][3];
+    _Pragma("unroll")
+    for (int c = 0; c < 6; c++) {      // row c of E: E L^T = Ct  ->  forward substitution along the row
+        E[c][0] = Ct[c][0] * Ll.r0; E[c][1] = (Ct[c][1] - E[c][0] * Ll.l10) * Ll.r1; E[c][2] = (Ct[c][2] - E[c][0] * Ll.l20 - E[c][1] * Ll.l21) * Ll.r2;
+    }
+    S LS[21], rdS[6];
+    _Pragma("unroll")
+    for (int i = 0; i < 6; i++) _Pragma("unroll") for (int j = 0; j <= i; j++) LS[tri(i, j)] = Bm[tri(i, j)] - Q::sum(E[i][0] * E[j][0] + E[i][1] * E[j][1] + E[i][2] * E[j][2]);
+    chol6<Q, S>(LS, rdS);
+    // y = L^-1 (tau - h): leg part in the lane, base part replicated (mode 1: no bias, y = 0)
+    const V3<S> yl = fwd3(Ll, V3<S>{m0 * (ul[0] - hl[0]), m0 * (ul[1] - hl[1]), m0 * (ul[2] - hl[2])});
+    S yb[6];
+    _Pragma("unroll") for (int c = 0; c < 6; c++) yb[c] = -(m0 * hb[c]) - Q::sum(E[c][0] * yl.x + E[c][1] * yl.y + E[c][2] * yl.z);
+    fwd6(LS, rdS, yb);
+    // X = L^-1 Jc^T for the lane's foot (zero for a swing leg): Xt (3 leg rows x 3 force directions), Xb (6 base rows x 3)
+    M33<S> Xt; S Xb[6][3];      // Xt.r[d] = column d (force direction d) as a 3-vector over the leg rows ; Xb[c][d]
+    _Pragma("unroll")
+    for (int d = 0; d < 3; d++) {
+        const V3<S> xt = scale(cl, fwd3(Ll, Ja.r[d]));      // L_l^-1 (row d of Ja)^T
+        Xt.r[d] = xt;
+        S w[6];
+        _Pragma("unroll") for (int c = 0; c < 6; c++) w[c] = cl * Jb[d][c] - (E[c][0] * xt.x + E[c][1] * xt.y + E[c][2] * xt.z);
+        fwd6(LS, rdS, w);
+        _Pragma("unroll") for (int c = 0; c < 6; c++) Xb[c][d] = w[c];
+    }
+    // Gram matrix G = X^T X in 3 x 3 blocks: lane f holds block row f (blocks g <= f), a swing leg's diagonal block is the identity
+    // (its multiplier is zero); right-hand side  -X^T y - gam,  gam = Jdot v + 2 alpha J v (WBM.cpp:392-408)
+    M33<S> G[4];
+    auto xb_of = [&](auto JT, int c, int d) { constexpr int J = decltype(JT)::value; return Q::template get<J>(Xb[c][d]); };
+    using J0 = IC<0>; using J1 = IC<1>; using J2 = IC<2>; using J3 = IC<3>;
+    auto gram_block = [&](auto JT, M33<S>& Gb) {
+        S o[6][3];
+        _Pragma("unroll") for (int c = 0; c < 6; c++) _Pragma("unroll") for (int d = 0; d < 3; d++) o[c][d] = xb_of(JT, c, d);
+        _Pragma("unroll")
+        for (int r = 0; r < 3; r++) {
+            S e[3];
+            _Pragma("unroll") for (int d = 0; d < 3; d++) { S s = Xb[0][r] * o[0][d]; _Pragma("unroll") for (int c = 1; c < 6; c++) s = s + Xb[c][r] * o[c][d]; e[d] = s; }
+            Gb.r[r] = {e[0], e[1], e[2]};
+        }
+    };
+    gram_block(J0{}, G[0]); gram_block(J1{}, G[1]); gram_block(J2{}, G[2]); gram_block(J3{}, G[3]);
+    // the lane's own diagonal block: + Xt^T Xt + damping (contact) / identity (swing)
+    M33<S> Gd;
+    {
+        const S dg = 1.0 - cl;      // (the damping enters at the factorisation)
+        _Pragma("unroll")
+        for (int r = 0; r < 3; r++) {
+            const S e0 = dot3(Xt.r[r], Xt.r[0]), e1 = dot3(Xt.r[r], Xt.r[1]), e2 = dot3(Xt.r[r], Xt.r[2]);
+            Gd.r[r] = {e0 + (r == 0 ? dg : zero), e1 + (r == 1 ? dg : zero), e2 + (r == 2 ? dg : zero)};
+        }
+        // added to G[own lane]: by selects on the lane's leg
+        const S m0 = Q::legc(1, 0, 0, 0), m1 = Q::legc(0, 1, 0, 0), m2 = Q::legc(0, 0, 1, 0), m3 = Q::legc(0, 0, 0, 1);
+        _Pragma("unroll")
+        for (int r = 0; r < 3; r++) {
+            G[0].r[r] = G[0].r[r] + scale(m0, Gd.r[r]); G[1].r[r] = G[1].r[r] + scale(m1, Gd.r[r]);
+            G[2].r[r] = G[2].r[r] + scale(m2, Gd.r[r]); G[3].r[r] = G[3].r[r] + scale(m3, Gd.r[r]);
+        }
+    }
+    V3<S> rhs;
+    {
+        S xy[3];
+        _Pragma("unroll") for (int d = 0; d < 3; d++) { S s = dot3(Xt.r[d], yl); _Pragma("unroll") for (int c = 0; c < 6; c++) s = s + Xb[c][d] * yb[c]; xy[d] = s; }
+        // mode 0: gam = Jdot v + 2 alpha J v (WBM.cpp:392-408) ; mode 1: the right-hand side is -Jc v, and J v of a foot is its velocity
+        const double a2 = 2.0 * bg_alpha;
+        const V3<S> gam = {m0 * (jdv.x + a2 * fvel.x) + m1 * fvel.x, m0 * (jdv.y + a2 * fvel.y) + m1 * fvel.y, m0 * (jdv.z + a2 * fvel.z) + m1 * fvel.z};
+        rhs = {cl * (-xy[0] - gam.x), cl * (-xy[1] - gam.y), cl * (-xy[2] - gam.z)};
+    }
+    // block Cholesky of G over the quad: block column kc is finished by lane kc (its diagonal block), then lanes f > kc form L_f,kc.
+    // Lane f keeps its block row Lg[0..f]; blocks right of the diagonal are never used.
+    M33<S> Lg[4]; Chol3<S> Ld;      // Lg[g]: block (own lane, g) of the factor, g < own lane ; Ld: the own diagonal block's factor
+    {
+        const S lane = Q::legc(0, 1, 2, 3);
+        auto bcast33 = [&](auto JT, const M33<S>& A) { constexpr int J = decltype(JT)::value; M33<S> o; _Pragma("unroll") for (int r = 0; r < 3; r++) o.r[r] = {Q::template get<J>(A.r[r].x), Q::template get<J>(A.r[r].y), Q::template get<J>(A.r[r].z)}; return o; };
+        auto bcastL = [&](auto JT, const Chol3<S>& A) { constexpr int J = decltype(JT)::value; Chol3<S> o; o.l10 = Q::template get<J>(A.l10); o.l20 = Q::template get<J>(A.l20); o.l21 = Q::template get<J>(A.l21); o.r0 = Q::template get<J>(A.r0); o.r1 = Q::template get<J>(A.r1); o.r2 = Q::template get<J>(A.r2); return o; };
+        // A <- A - P Q^T (3x3 blocks, rows)
+        auto sub_abt = [&](M33<S>& A, const M33<S>& Pm, const M33<S>& Qm) { _Pragma("unroll") for (int r = 0; r < 3; r++) A.r[r] = A.r[r] - V3<S>{dot3(Pm.r[r], Qm.r[0]), dot3(Pm.r[r], Qm.r[1]), dot3(Pm.r[r], Qm.r[2])}; };
+        // rows of A <- (rows of A) L^-T : solve x L^T = a per row
+        auto right_solve = [&](M33<S>& A, const Chol3<S>& Lk) { _Pragma("unroll") for (int r = 0; r < 3; r++) { V3<S> a = A.r[r], x; x.x = a.x * Lk.r0; x.y = (a.y - x.x * Lk.l10) * Lk.r1; x.z = (a.z - x.x * Lk.l20 - x.y * Lk.l21) * Lk.r2; A.r[r] = x; } };
+        // own diagonal block = G[own]: picked by selects (each lane needs ITS block at ITS step; every lane runs every step)
+        const S dmp = cl * damping;
+        auto own_diag = [&](const M33<S>& Gk) { return chol3<Q, S>(Gk.r[0].x + dmp, Gk.r[1].x, Gk.r[1].y + dmp, Gk.r[2].x, Gk.r[2].y, Gk.r[2].z + dmp); };
+        // step 0: lane 0's diagonal block is final
+        Chol3<S> L0 = own_diag(G[0]);                       // meaningful in lane 0
+        const Chol3<S> L00 = bcastL(J0{}, L0);
+        Lg[0] = G[0]; right_solve(Lg[0], L00);              // lanes 1..3: L_f0 (lane 0's own copy is not used)
+        // step 1
+        const M33<S> L10 = bcast33(J1{}, Lg[0]);
+        M33<S> A1 = G[1]; sub_abt(A1, Lg[0], L10);          // lanes >= 1: G_f1 - L_f0 L_10^T
+        Chol3<S> L1 = own_diag(A1);                         // meaningful in lane 1
+        const Chol3<S> L11 = bcastL(J1{}, L1);
+        Lg[1] = A1; right_solve(Lg[1], L11);                // lanes 2..3: L_f1
+        // step 2
+        const M33<S> L20 = bcast33(J2{}, Lg[0]), L21 = bcast33(J2{}, Lg[1]);
+        M33<S> A2 = G[2]; sub_abt(A2, Lg[0], L20); sub_abt(A2, Lg[1], L21);
+        Chol3<S> L2 = own_diag(A2);                         // meaningful in lane 2
+        const Chol3<S> L22 = bcastL(J2{}, L2);
+        Lg[2] = A2; right_solve(Lg[2], L22);                // lane 3: L_32
+        // step 3
+        M33<S> A3 = G[3]; sub_abt(A3, Lg[0], Lg[0]); sub_abt(A3, Lg[1], Lg[1]); sub_abt(A3, Lg[2], Lg[2]);      // lane 3: G_33 - sum L_3g L_3g^T
+        Chol3<S> L3 = own_diag(A3);                         // meaningful in lane 3
+        // every lane keeps its own diagonal factor
+        const typename Q::B is0 = Q::gt(S(0.5), lane), is1 = Q::gt(S(1.5), lane), is2 = Q::gt(S(2.5), lane);
+        auto pick = [&](const S& a0, const S& a1, const S& a2, const S& a3) { return Q::sel(is0, a0, Q::sel(is1, a1, Q::sel(is2, a2, a3))); };
+        Ld.l10 = pick(L0.l10, L1.l10, L2.l10, L3.l10); Ld.l20 = pick(L0.l20, L1.l20, L2.l20, L3.l20); Ld.l21 = pick(L0.l21, L1.l21, L2.l21, L3.l21);
+        Ld.r0 = pick(L0.r0, L1.r0, L2.r0, L3.r0); Ld.r1 = pick(L0.r1, L1.r1, L2.r1, L3.r1); Ld.r2 = pick(L0.r2, L1.r2, L2.r2, L3.r2);
+        // lam = G^-1 rhs: forward over block rows 0..3, backward 3..0.  z_f lives in lane f.
+        V3<S> z = rhs;
+        auto bc3 = [&](auto JT, const V3<S>& w) { constexpr int J = decltype(JT)::value; return V3<S>{Q::template get<J>(w.x), Q::template get<J>(w.y), Q::template get<J>(w.z)}; };
+        V3<S> z0 = fwd3(Ld, z);                                               // valid in lane 0
+        const V3<S> Z0 = bc3(J0{}, z0);
+        V3<S> t1 = z - m33_mul(Lg[0], Z0); V3<S> z1 = fwd3(Ld, t1);            // valid in lane 1
+        const V3<S> Z1 = bc3(J1{}, z1);
+        V3<S> t2 = t1 - m33_mul(Lg[1], Z1); V3<S> z2 = fwd3(Ld, t2);           // valid in lane 2
+        const V3<S> Z2 = bc3(J2{}, z2);
+        V3<S> t3 = t2 - m33_mul(Lg[2], Z2); V3<S> z3 = fwd3(Ld, t3);           // valid in lane 3
+        z = {pick(z0.x, z1.x, z2.x, z3.x), pick(z0.y, z1.y, z2.y, z3.y), pick(z0.z, z1.z, z2.z, z3.z)};
+        // backward: lam_3 = L_33^-T z_3 ; lam_k = L_kk^-T (z_k - sum_{f>k} L_fk^T lam_f) - the product L_fk^T lam_f is formed in lane f and read by lane k
+        V3<S> lam3 = bwd3(Ld, z);                                             // valid in lane 3
+        const V3<S> w32 = bc3(J3{}, m33_mulT(Lg[2], lam3)), w31 = bc3(J3{}, m33_mulT(Lg[1], lam3)), w30 = bc3(J3{}, m33_mulT(Lg[0], lam3));
+        V3<S> lam2 = bwd3(Ld, z - w32);                                       // valid in lane 2
+        const V3<S> w21 = bc3(J2{}, m33_mulT(Lg[1], lam2)), w20 = bc3(J2{}, m33_mulT(Lg[0], lam2));
+        V3<S> lam1 = bwd3(Ld, z - w31 - w21);                                 // valid in lane 1
+        const V3<S> w10 = bc3(J1{}, m33_mulT(Lg[0], lam1));
+        V3<S> lam0 = bwd3(Ld, z - w30 - w20 - w10);                           // valid in lane 0
+        rhs = {pick(lam0.x, lam1.x, lam2.x, lam3.x), pick(lam0.y, lam1.y, lam2.y, lam3.y), pick(lam0.z, lam1.z, lam2.z, lam3.z)};
+    }
+    const V3<S> lam = scale(cl, rhs);      // contact force of the lane's foot (world axes); zero for a swing leg
+    // qdd = L^-T (y + X lam): base part replicated, leg part in the lane
+    S qddb[6]; V3<S> qddl;
+    {
+        _Pragma("unroll") for (int c = 0; c < 6; c++) qddb[c] = yb[c] + Q::sum(Xb[c][0] * lam.x + Xb[c][1] * lam.y + Xb[c][2] * lam.z);
+        bwd6(LS, rdS, qddb);
+        V3<S> zl = yl + V3<S>{Xt.r[0].x * lam.x + Xt.r[1].x * lam.y + Xt.r[2].x * lam.z, Xt.r[0].y * lam.x + Xt.r[1].y * lam.y + Xt.r[2].y * lam.z, Xt.r[0].z * lam.x + Xt.r[1].z * lam.y + Xt.r[2].z * lam.z};
+        S et[3];
+        _Pragma("unroll") for (int j = 0; j < 3; j++) { S s = E[0][j] * qddb[0]; _Pragma("unroll") for (int c = 1; c < 6; c++) s = s + E[c][j] * qddb[c]; et[j] = s; }
+        qddl = bwd3(Ll, zl - V3<S>{et[0], et[1], et[2]});
+    }
+    // mode 1: the velocities after the impact, v + L^-T X lam
+    _Pragma("unroll") for (int c = 0; c < 6; c++) out_b[c] = qddb[c] + m1 * vb[c];
+    out_l = {qddl.x + m1 * vl_[0], qddl.y + m1 * vl_[1], qddl.z + m1 * vl_[2]};
+}
+
+// per-sample summary of a window, as the kernel leaves it (doubles; hsddp_sim_get_rows turns first_bad into an int)
+constexpr int SIM_PARK = 24;     // doubles a lane parks in LDS across the contact solve (wbs_walk)
+constexpr int SIM_ROW = 5;      // dev_q | dev_v | min_height | max_torque | first_bad
+
+// The window of one (problem b, sample) pair, quad index g = b * R + sample, walked by a lane quad.
+//   map: [3][n_steps] step -> phase, knot of the phase, 1 if the phase's reset map is applied behind the step (last knot of a phase with a touchdown,
+//        and the window goes on), as hsddp_sim_create lays it out
+//   x0: [B R][36]; xfinal: [B R][36]; rows: [B R][SIM_ROW]; trajX: [B R][n_steps + 1][36] or null; trajU: [B R][n_steps][12] or null
+//   stash: SIM_PARK x 64 doubles of LDS of the wave (device only)
+// A quad whose new state fails the rollout's divergence test (squared norm above 1e12 or NaN, wb_quad.hpp / SinglePhase.cpp:205) keeps the state it
+// had BEFORE that step and records nothing further, but goes on executing: the cross-lane steps need all four lanes, and the other quads of the
+// wave must not notice.  Trajectory entries behind first_bad repeat the kept state (controls: what the policy asks for there).
+template <class Q>
+HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, int b, size_t g, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU,
+                 double* stash = nullptr) {
+    using S = typename Q::S;
+    const S zero = S(0.0), one = S(1.0);
+    const S w0 = Q::legc(1.0, 0.0, 0.0, 0.0);      // the replicated base entries are counted once
+    S qb[6], vb[6], ql[3], vl[3];
+    _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::ld(x0, g * 36 + i, 0); vb[i] = Q::ld(x0, g * 36 + 18 + i, 0); }
+    _Pragma("unroll") for (int j = 0; j < 3; j++) { ql[j] = Q::ld(x0, g * 36 + 6 + j, 3); vl[j] = Q::ld(x0, g * 36 + 24 + j, 3); }
+    S alive = one, first_bad = S(-1.0);
+    S dq = zero, dv = zero, umax = zero, hmin = qb[2];      // (per-lane maxima over the base and the lane's leg: joined over the quad at the end)
+    // deviation of the state from row `kx` of a phase's Xbar: base part replicated, the lane's leg
+    auto deviation = [&](PhaseC& P, size_t kx, S (&eb)[6], S (&wb)[6], S (&el)[3], S (&wl)[3]) {
+        _Pragma("unroll") for (int i = 0; i < 6; i++) { eb[i] = qb[i] - Q::ld(P.Xbar, kx + i, 0); wb[i] = vb[i] - Q::ld(P.Xbar, kx + 18 + i, 0); }
+        _Pragma("unroll") for (int j = 0; j < 3; j++) { el[j] = ql[j] - Q::ld(P.Xbar, kx + 6 + j, 3); wl[j] = vl[j] - Q::ld(P.Xbar, kx + 24 + j, 3); }
+    };
+    auto record = [&](const S (&eb)[6], const S (&wb)[6], const S (&el)[3], const S (&wl)[3]) {
+        const typename Q::B on = Q::gt(alive, S(0.5));
+        S mq = zero, mv = zero;
+        _Pragma("unroll") for (int i = 0; i < 6; i++) { mq = wbs_max<Q, S>(mq, wbs_abs<Q, S>(eb[i])); mv = wbs_max<Q, S>(mv, wbs_abs<Q, S>(wb[i])); }
+        _Pragma("unroll") for (int j = 0; j < 3; j++) { mq = wbs_max<Q, S>(mq, wbs_abs<Q, S>(el[j])); mv = wbs_max<Q, S>(mv, wbs_abs<Q, S>(wl[j])); }
+        dq = Q::sel(on, wbs_max<Q, S>(dq, mq), dq); dv = Q::sel(on, wbs_max<Q, S>(dv, mv), dv);
+        hmin = Q::sel(on, Q::min(hmin, qb[2]), hmin);
+    };
+    auto store_state = [&](size_t o) {
+        _Pragma("unroll") for (int i = 0; i < 6; i++) { Q::st0(trajX, o + i, qb[i]); Q::st0(trajX, o + 18 + i, vb[i]); }
+        _Pragma("unroll") for (int j = 0; j < 3; j++) { Q::st(trajX, o + 6 + j, 3, ql[j]); Q::st(trajX, o + 24 + j, 3, vl[j]); }
+    };
+    // What the loop carries - the state (18 doubles) and the summaries (6) - is not needed while the contact solve is at its register peak, and
+    // k_rollout_quad's dynamics alone take 478 of the 512 registers: the compiler spilled 76 registers to scratch to carry them.  The lane parks
+    // them in a column of LDS of its own around the call instead (24 x 64 doubles = 12 KB per wave; lane-private, so no barrier): 304 -> 52 B of
+    // scratch per lane, 13.6 -> 11.0 ms at config 3 x 16 samples x 200 steps.  The empty asm keeps the compiler from forwarding the registers.
+#ifdef HS_HOST_EMU
+    auto park = [](bool) {};
+#else
+    auto park = [&](bool out) {
+        S* const c = stash + threadIdx.x;
+        S* v[24] = {&qb[0], &qb[1], &qb[2], &qb[3], &qb[4], &qb[5], &vb[0], &vb[1], &vb[2], &vb[3], &vb[4], &vb[5], &ql[0], &ql[1], &ql[2], &vl[0], &vl[1], &vl[2],
+                    &dq, &dv, &umax, &hmin, &alive, &first_bad};
+        if (out) { _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; }
+        else { asm volatile("" ::: "memory"); _Pragma("unroll") for (int i = 0; i < 24; i++) *v[i] = c[64 * i]; }
+    };
+#endif
+    // the rows of a knot the feedback reads: Xbar (base q, base v, leg q, leg v), Ubar and the lane's three rows of K
+    S Xr[18], Ur[3], Kr[3][36];
+    auto fetch = [&](PhaseC& P, size_t kx, size_t ku, size_t kg) {
+        _Pragma("unroll") for (int i = 0; i < 6; i++) { Xr[i] = Q::ld(P.Xbar, kx + i, 0); Xr[6 + i] = Q::ld(P.Xbar, kx + 18 + i, 0); }
+        _Pragma("unroll") for (int j = 0; j < 3; j++) { Xr[12 + j] = Q::ld(P.Xbar, kx + 6 + j, 3); Xr[15 + j] = Q::ld(P.Xbar, kx + 24 + j, 3); Ur[j] = Q::ld(P.Ubar, ku + j, 3); }
+        _Pragma("unroll") for (int j = 0; j < 3; j++) _Pragma("unroll") for (int c = 0; c < 36; c++) Kr[j][c] = Q::ld(P.K, kg + j + 12 * c, 3);
+    };
+    int pi = 0, k = 0;
+    _Pragma("nounroll")
+    for (int s = 0; s < n_steps; s++) {
+        pi = wbs_uniform(map[s]); k = wbs_uniform(map[n_steps + s]);
+        const int reset = wbs_uniform(map[2 * n_steps + s]);
+        PhaseC& P = ph[pi];
+        const int h = P.h;
+        const size_t kx = ((size_t)b * (h + 1) + k) * 36, ku = ((size_t)b * h + k) * 12, kg = ((size_t)b * h + k) * 432;
+        // ---- feedback: the lane forms the three torques of its leg, rows 3 lane .. 3 lane + 2 of K (12 x 36, column-major) times x - xbar.  The
+        // base part of x - xbar is in every lane already, the other legs' parts come by quad broadcasts.
+        S ul[3];
+        {
+#if SIM_PREFETCH
+            if (s == 0) fetch(P, kx, ku, kg);      // (later knots: fetched ahead of the previous knot's contact solve, below)
+#else
+            fetch(P, kx, ku, kg);
+#endif
+            S eb[6], wb[6], el[3], wl[3];
+            _Pragma("unroll") for (int i = 0; i < 6; i++) { eb[i] = qb[i] - Xr[i]; wb[i] = vb[i] - Xr[6 + i]; }
+            _Pragma("unroll") for (int j = 0; j < 3; j++) { el[j] = ql[j] - Xr[12 + j]; wl[j] = vl[j] - Xr[15 + j]; }
+            record(eb, wb, el, wl);
+            S dx[36];
+            _Pragma("unroll") for (int i = 0; i < 6; i++) { dx[i] = eb[i]; dx[18 + i] = wb[i]; }
+            _Pragma("unroll") for (int j = 0; j < 3; j++) {
+                dx[6 + j] = Q::template get<0>(el[j]); dx[9 + j] = Q::template get<1>(el[j]); dx[12 + j] = Q::template get<2>(el[j]); dx[15 + j] = Q::template get<3>(el[j]);
+                dx[24 + j] = Q::template get<0>(wl[j]); dx[27 + j] = Q::template get<1>(wl[j]); dx[30 + j] = Q::template get<2>(wl[j]); dx[33 + j] = Q::template get<3>(wl[j]);
+            }
+            S um = zero;
+            _Pragma("unroll")
+            for (int j = 0; j < 3; j++) {
+                S acc = Kr[j][0] * dx[0];
+                _Pragma("unroll") for (int c = 1; c < 36; c++) acc = acc + Kr[j][c] * dx[c];
+                ul[j] = Ur[j] + acc;
+                um = wbs_max<Q, S>(um, wbs_abs<Q, S>(ul[j]));
+            }
+            umax = Q::sel(Q::gt(alive, S(0.5)), wbs_max<Q, S>(umax, um), umax);
+        }
+#if SIM_PREFETCH
+        if (s + 1 < n_steps) {      // the next knot's rows do not depend on the state: their loads go out before the contact solve of this one
+            const int pn = wbs_uniform(map[s + 1]), kn = wbs_uniform(map[n_steps + s + 1]);
+            PhaseC& N = ph[pn];
+            fetch(N, ((size_t)b * (N.h + 1) + kn) * 36, ((size_t)b * N.h + kn) * 12, ((size_t)b * N.h + kn) * 432);
+        }
+#endif
+        if (trajX != nullptr) store_state((g * (size_t)(n_steps + 1) + s) * 36);
+        if (trajU != nullptr) { _Pragma("unroll") for (int j = 0; j < 3; j++) Q::st(trajU, (g * (size_t)n_steps + s) * 12 + j, 3, ul[j]); }
+        // ---- the step, and behind the last knot of a phase with a touchdown the impact: ONE call site of the dynamics, the phase boundary is a
+        // uniform branch of the loop
+        const int cm_dyn = (P.contact[0] > 0 ? 1 : 0) | (P.contact[1] > 0 ? 2 : 0) | (P.contact[2] > 0 ? 4 : 0) | (P.contact[3] > 0 ? 8 : 0);
+        const int cm_td = (P.td[0] ? 1 : 0) | (P.td[1] ? 2 : 0) | (P.td[2] ? 4 : 0) | (P.td[3] ? 8 : 0);
+        const double dt = P.dt, alpha = P.bg_alpha;
+        _Pragma("nounroll")
+        for (int mode = 0; mode <= reset; mode++) {
+            S ob[6]; V3<S> ol;
+            park(true);
+            wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol);
+            park(false);
+            if (mode == 0) {      // forward Euler (WBM.cpp:25-26), then the divergence test on the new state
+                S xb[6], yb[6], xl[3], yl[3], nsq = zero;
+                _Pragma("unroll") for (int i = 0; i < 6; i++) { xb[i] = qb[i] + vb[i] * dt; yb[i] = vb[i] + ob[i] * dt; nsq = nsq + w0 * (xb[i] * xb[i] + yb[i] * yb[i]); }
+                const S o3[3] = {ol.x, ol.y, ol.z};
+                _Pragma("unroll") for (int j = 0; j < 3; j++) { xl[j] = ql[j] + vl[j] * dt; yl[j] = vl[j] + o3[j] * dt; nsq = nsq + (xl[j] * xl[j] + yl[j] * yl[j]); }
+                nsq = Q::sum(nsq);
+                // good <=> !(nsq > 1e12) && nsq == nsq   (below 1e12 adding one always gives a larger number; a NaN compares false)
+                const S good = Q::sel(Q::gt(nsq, S(1e12)), zero, one) * Q::sel(Q::gt(nsq + 1.0, nsq), one, zero);
+                first_bad = Q::sel(Q::gt(alive * (one - good), S(0.5)), S((double)s), first_bad);
+                alive = alive * good;
+                const typename Q::B on = Q::gt(alive, S(0.5));
+                _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::sel(on, xb[i], qb[i]); vb[i] = Q::sel(on, yb[i], vb[i]); }
+                _Pragma("unroll") for (int j = 0; j < 3; j++) { ql[j] = Q::sel(on, xl[j], ql[j]); vl[j] = Q::sel(on, yl[j], vl[j]); }
+            } else {              // reset map: positions stay, velocities jump
+                const typename Q::B on = Q::gt(alive, S(0.5));
+                const S o3[3] = {ol.x, ol.y, ol.z};
+                _Pragma("unroll") for (int i = 0; i < 6; i++) vb[i] = Q::sel(on, ob[i], vb[i]);
+                _Pragma("unroll") for (int j = 0; j < 3; j++) vl[j] = Q::sel(on, o3[j], vl[j]);
+            }
+        }
+    }
+    {   // the state behind the last step, against the knot that follows it
+        PhaseC& P = ph[pi];
+        S eb[6], wb[6], el[3], wl[3];
+        deviation(P, ((size_t)b * (P.h + 1) + k + 1) * 36, eb, wb, el, wl);
+        record(eb, wb, el, wl);
+    }
+    if (trajX != nullptr) store_state((g * (size_t)(n_steps + 1) + n_steps) * 36);
+    _Pragma("unroll") for (int i = 0; i < 6; i++) { Q::st0(xfinal, g * 36 + i, qb[i]); Q::st0(xfinal, g * 36 + 18 + i, vb[i]); }
+    _Pragma("unroll") for (int j = 0; j < 3; j++) { Q::st(xfinal, g * 36 + 6 + j, 3, ql[j]); Q::st(xfinal, g * 36 + 24 + j, 3, vl[j]); }
+    Q::st0(rows, g * SIM_ROW, wbs_qmax<Q, S>(dq)); Q::st0(rows, g * SIM_ROW + 1, wbs_qmax<Q, S>(dv)); Q::st0(rows, g * SIM_ROW + 2, hmin);
+    Q::st0(rows, g * SIM_ROW + 3, wbs_qmax<Q, S>(umax)); Q::st0(rows, g * SIM_ROW + 4, first_bad);
+}
+
+#ifndef HS_HOST_EMU
+// grid = ceil(B R / 16) waves of sixteen quads.  The loop is sequential in the knots, so a launch has B R / 16 waves whatever the window length.
+#ifndef SIM_WPE
+#define SIM_WPE 1      // waves per SIMD the kernel is compiled for (as k_rollout_quad: up to 512 registers)
+#endif
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))
+k_sim_quad(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU) {
+    __shared__ double stash[SIM_PARK * 64];      // lane t parks in column t (wbs_walk)
+    const int g = blockIdx.x * 16 + (threadIdx.x >> 2);
+    if (g >= total) return;      // (a quad leaves or stays as a whole)
+    wbs_walk<QS>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash);
+}
+#endif
+
+}  // namespace hs

@@ -18,6 +18,7 @@
 #include "hsddp.h"
 #include "hsddp_hkd.h"
 #include "hsddp_refs.h"
+#include "hsddp_sim.h"
 
 namespace hsddp {
 
@@ -31,6 +32,43 @@ inline HSDDP_OPTION default_option() {   // HSDDP_CompoundTypes.h:15-36 defaults
     o.merit_rho = 1e4; o.merit_scale = 0.2; o.merit_offset = 10; o.AL_active = 1; o.ReB_active = 1; o.smooth_active = 0; o.MS = 1; o.nsteps_per_node = 1;
     return o;
 }
+
+// Closed-loop rollouts of a solved policy (include/hsddp_sim.h): one device object on a solver's handle, kept across MPC ticks (run() makes no
+// device allocation).  Stale after MultiPhaseDDP::reconfigure (run() then fails with HSDDP_EINVAL: make a new one); destroy it before the solver.
+struct SimResult {
+    std::vector<hsddp_sim_row_t> rows;      // batch x n_samples
+    std::vector<double> x_final;            // batch x n_samples x 36
+    std::vector<double> X, U;               // keep_traj: batch x n_samples x (n_steps + 1) x 36, batch x n_samples x n_steps x 12
+};
+class Simulation {
+public:
+    Simulation(hsddp_handle_t* h, int batch, int n_samples, int n_steps, bool keep_traj = false) : batch_(batch), R_(n_samples), n_(n_steps), keep_(keep_traj) {
+        rc_ = hsddp_sim_create(h, n_samples, n_steps, keep_traj ? 1 : 0, &s_);
+        if (rc_ != HSDDP_OK) s_ = nullptr;
+    }
+    ~Simulation() { if (s_) hsddp_sim_destroy(s_); }
+    Simulation(const Simulation&) = delete;
+    Simulation& operator=(const Simulation&) = delete;
+    // x0: batch x n_samples x 36 (host memory, or device memory with src_device = 1)
+    bool run(const double* x0, int src_device = 0) { rc_ = s_ ? hsddp_sim_run(s_, x0, src_device) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    SimResult result() {
+        SimResult r;
+        if (!s_) return r;
+        const size_t cnt = (size_t)batch_ * R_;
+        r.rows.resize(cnt); r.x_final.resize(cnt * 36);
+        rc_ = hsddp_sim_get_rows(s_, 0, batch_, r.rows.data(), r.x_final.data());
+        if (rc_ == HSDDP_OK && keep_) {
+            r.X.resize(cnt * (size_t)(n_ + 1) * 36); r.U.resize(cnt * (size_t)n_ * 12);
+            rc_ = hsddp_sim_get_traj(s_, 0, batch_, r.X.data(), r.U.data());
+        }
+        return r;
+    }
+    const double* device_final() { return s_ ? hsddp_sim_device_final(s_) : nullptr; }      // batch x n_samples x 36 on the device
+    int last_error() const { return rc_; }
+private:
+    hsddp_sim_t* s_ = nullptr;
+    int batch_, R_, n_, rc_ = 0; bool keep_;
+};
 
 template <typename T = double>
 class MultiPhaseDDP {
@@ -118,6 +156,16 @@ public:
     void get_references(int phase, int b0, int nb, double* xr, double* ur, double* yr, double* foot_pos, double* foot_vel, double* body_pos,
                         int* ref_contact) {
         rc_ = hsddp_get_references(h_, phase, b0, nb, xr, ur, yr, foot_pos, foot_vel, body_pos, ref_contact);
+    }
+    // one-off closed-loop rollouts of the current policy, u = Ubar + K (x - Xbar), from n_samples initial states per problem over the first
+    // n_steps whole-body control knots (x0: batch x n_samples x 36) - what the controller side of the reference does one state at a time
+    // (MHPC/MHPC-Trajopt/test/testTrajOptInLoop.cpp).  An MPC loop keeps a hsddp::Simulation instead.  libhsddp_hip.so only.
+    SimResult simulate(const T* x0, int n_samples, int n_steps, bool keep_traj = false, int src_device = 0) {
+        Simulation sim(h_, batch_, n_samples, n_steps, keep_traj);
+        SimResult r;
+        if (sim.last_error() == HSDDP_OK && sim.run(x0, src_device)) r = sim.result();
+        rc_ = sim.last_error();
+        return r;
     }
     // receding-horizon step (MHPCProblem::update): phase `dphase` continues phase `sphase` of the previous window (sphase < 0: new phase)
     void warm_start_phase(int dphase, MultiPhaseDDP<T>* prev, int sphase, int popped_front) {

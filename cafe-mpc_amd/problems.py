@@ -88,6 +88,27 @@ def wb_ensemble_x0(batch, seed, first=0):
     return out
 
 
+def perturbed_states(x, n_samples, sigma_q, sigma_v, seed, first=0):
+    """Initial states of a closed-loop simulation (Solver.simulate): x [B, n] -> [B, n_samples, n], Gaussian perturbations around each given
+    state with standard deviation sigma_q on the position half and sigma_v on the velocity half (scalars, or one value per coordinate).
+    Sample 0 of every problem is the state itself.  Box-Muller on SplitMix64: (problem b, sample r >= 1) draws its n normal numbers from stream
+    position 2 n ((first + b) (n_samples - 1) + r - 1), so any shard reproduces its own slice and a sample does not depend on the batch."""
+    x = np.atleast_2d(np.asarray(x, dtype=np.float64))
+    B, n = x.shape
+    if n_samples <= 0 or n % 2:
+        raise ValueError(f"perturbed_states: n_samples={n_samples}, state dimension {n}")
+    sig = np.concatenate([np.broadcast_to(np.asarray(sigma_q, dtype=np.float64), (n // 2,)), np.broadcast_to(np.asarray(sigma_v, dtype=np.float64), (n // 2,))])
+    out = np.repeat(x[:, None, :], n_samples, axis=1)
+    rng = SplitMix64(seed)
+    rng.skip(2 * n * first * (n_samples - 1))
+    for b in range(B):
+        for r in range(1, n_samples):
+            u = np.array([rng.next() for _ in range(2 * n)])
+            z = np.sqrt(-2.0 * np.log(1.0 - u[:n])) * np.cos(2.0 * np.pi * u[n:])      # 1 - u is in (0, 1]
+            out[b, r] += sig * z
+    return out
+
+
 def _set(arr, vals):
     for i, v in enumerate(vals):
         arr[i] = v
