@@ -229,6 +229,36 @@ def bind_sim(lib):
     return lib
 
 
+# include/hsddp_mc.h: disturbed runs of a simulation object (libhsddp_hip.so only)
+MC_EXPORTS = ["hsddp_mc_run", "hsddp_mc_get_extra"]
+
+
+class McDist(C.Structure):
+    """hsddp_mc_dist_t"""
+    _fields_ = [("seed", C.c_ulonglong), ("sigma_u", C.c_double), ("sigma_q", C.c_double), ("sigma_v", C.c_double), ("u_max", C.c_double),
+                ("fall_height", C.c_double), ("kick_step", C.c_int), ("first_problem", C.c_int)]
+
+
+class McExtra(C.Structure):
+    """hsddp_mc_extra_t"""
+    _fields_ = [("first_fall", C.c_int), ("n_sat", C.c_int)]
+
+
+MC_EXTRA_DTYPE = np.dtype([("first_fall", "<i4"), ("n_sat", "<i4")])
+
+
+def bind_mc(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_mc.h (and of hsddp_sim.h, which they work on).  Raises if the library lacks any."""
+    missing = [s for s in MC_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the disturbed-simulation entry points {missing}")
+    bind_sim(lib)
+    H = C.c_void_p
+    lib.hsddp_mc_run.argtypes = [H, C.c_void_p, C.c_int, C.POINTER(McDist), C.c_void_p, C.c_int]
+    lib.hsddp_mc_get_extra.argtypes = [H, C.c_int, C.c_int, C.c_void_p]
+    return lib
+
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -484,13 +514,14 @@ class Solver:
                  "get_references")
         return out
 
-    def simulate(self, x0, n_steps, keep_traj=False):
+    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None):
         """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)
         over the first n_steps whole-body control knots (include/hsddp_sim.h): dict with rows (structured array [batch, R] of dev_q, dev_v,
         min_height, max_torque, first_bad), x_final [batch, R, 36] and, with keep_traj, X [batch, R, n_steps + 1, 36] and U [batch, R, n_steps, 12].
-        sim.Simulation keeps the device object across calls."""
+        sim.Simulation keeps the device object across calls.  dist (sim.Disturbance) / kick [batch, R, 36]: a disturbed run (include/hsddp_mc.h),
+        which also returns extra (structured array [batch, R] of first_fall, n_sat)."""
         from . import sim
-        return sim.simulate(self, x0, n_steps, keep_traj)
+        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick)
 
     def get_history(self, problem=0, cap=4096):
         """MultiPhaseDDP::get_solver_info(cost, dyn_feas, eqn_feas, ineq_feas) (MultiPhaseDDP.h:85): the four float history buffers."""

@@ -19,6 +19,7 @@
 #include "hsddp_hkd.h"
 #include "hsddp_refs.h"
 #include "hsddp_sim.h"
+#include "hsddp_mc.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -1697,12 +1698,15 @@ struct hsddp_sim {
     int* d_map = nullptr;                                  // [3][n_steps] step -> phase, knot, reset map behind the step (wb_sim.hpp)
     double *d_x0 = nullptr, *d_final = nullptr, *d_rows = nullptr, *d_X = nullptr, *d_U = nullptr;      // [B R] x 36 / 36 / SIM_ROW / (n_steps+1) 36 / n_steps 12
     hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
+    // disturbed runs (hsddp_mc.h): allocated at the first one.  last_mc: 0 the last run was plain, 1 disturbed, 2 hsddp_mc_run with every switch off
+    double *d_extra = nullptr, *d_kick = nullptr; WbsMcArgs* d_mc = nullptr;      // [B R][2] first_fall | n_sat ; staging of a host kick ; the switches
+    int last_mc = 0;
 };
 static void sim_free(hsddp_sim* s) {
     if (!s) return;
     hipSetDevice(s->h->device);
     if (s->h->stream) hipStreamSynchronize(s->h->stream);
-    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U};
+    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc};
     for (void* q : p) if (q) hipFree(q);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -1746,20 +1750,75 @@ int hsddp_sim_create(hsddp_handle_t* h, int n_samples, int n_steps, int keep_tra
 
 void hsddp_sim_destroy(hsddp_sim_t* s) { sim_free(s); }
 
+// the one launch path of a run: the plain kernel, or (mc) the disturbed one with the switches that are already on the device at s->d_mc
+static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, bool noise = false) {
+    hsddp_handle* h = s->h;
+    const size_t total = (size_t)h->batch * s->R;
+    if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipEventRecord(s->ev0, h->stream));
+    if (!mc)
+        hipLaunchKernelGGL(k_sim_quad, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
+                           src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U);
+    else
+        hipLaunchKernelGGL(noise ? k_sim_quad_mc : k_sim_quad_mc0, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
+                           src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, (const WbsMcArgs*)s->d_mc);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(s->ev1, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    s->timed = true;
+    return HSDDP_OK;
+}
+
 int hsddp_sim_run(hsddp_sim_t* s, const double* x0, int src_device) {
     if (!s || !x0) return HSDDP_EINVAL;
     hsddp_handle* h = s->h;
     if (s->gen != h->window_gen) return HSDDP_EINVAL;      // hsddp_reconfigure moved the window: the step map is that of the old one
     HIPCK(hipSetDevice(h->device));
+    const int rc = sim_launch(s, x0, src_device, false);
+    if (rc == HSDDP_OK) s->last_mc = 0;
+    return rc;
+}
+
+int hsddp_mc_run(hsddp_sim_t* s, const double* x0, int x0_device, const hsddp_mc_dist_t* d, const double* kick, int kick_device) {
+    if (!s || !x0 || !d) return HSDDP_EINVAL;
+    hsddp_handle* h = s->h;
+    if (s->gen != h->window_gen) return HSDDP_EINVAL;
+    auto sigma_ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    if (!sigma_ok(d->sigma_u) || !sigma_ok(d->sigma_q) || !sigma_ok(d->sigma_v) || !std::isfinite(d->u_max) || !std::isfinite(d->fall_height) || d->first_problem < 0) return HSDDP_EINVAL;
+    if (kick && (d->kick_step < 0 || d->kick_step >= s->n_steps)) return HSDDP_EINVAL;
+    if (s->n_steps > 65536 || s->R > 65536) return HSDDP_EINVAL;      // the generator numbers samples and steps in 16 bits each
+    HIPCK(hipSetDevice(h->device));
+    if (!kick && d->sigma_u == 0.0 && d->sigma_q == 0.0 && d->sigma_v == 0.0 && d->u_max <= 0.0 && d->fall_height <= 0.0) {      // nothing switched on: the plain kernel
+        const int rc = sim_launch(s, x0, x0_device, false);
+        if (rc == HSDDP_OK) s->last_mc = 2;
+        return rc;
+    }
     const size_t total = (size_t)h->batch * s->R;
-    if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCK(hipEventRecord(s->ev0, h->stream));
-    hipLaunchKernelGGL(k_sim_quad, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
-                       src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U);
-    HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(s->ev1, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));
-    s->timed = true;
+#define MC_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
+    if (!s->d_extra) MC_CK(hipMalloc((void**)&s->d_extra, total * 2 * 8));
+    if (!s->d_mc) MC_CK(hipMalloc((void**)&s->d_mc, sizeof(WbsMcArgs)));
+    if (kick && !kick_device && !s->d_kick) MC_CK(hipMalloc((void**)&s->d_kick, total * 36 * 8));
+#undef MC_CK
+    if (kick && !kick_device) HIPCK(hipMemcpyAsync(s->d_kick, kick, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
+    WbsMcArgs a;
+    a.seed = d->seed; a.first_problem = (unsigned long long)d->first_problem;
+    a.su = d->sigma_u; a.sq = d->sigma_q; a.sv = d->sigma_v; a.umax = d->u_max; a.fall = d->fall_height;
+    a.kick_step = kick ? d->kick_step : -1; a.R = s->R;
+    a.kick = kick ? (kick_device ? kick : s->d_kick) : nullptr; a.extra = s->d_extra;
+    HIPCK(hipMemcpyAsync(s->d_mc, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));      // (pageable source: staged before the call returns)
+    const int rc = sim_launch(s, x0, x0_device, true, d->sigma_u > 0.0 || d->sigma_q > 0.0 || d->sigma_v > 0.0);      // (without noise: the walk compiled without the generator)
+    if (rc == HSDDP_OK) s->last_mc = 1;
+    return rc;
+}
+
+int hsddp_mc_get_extra(hsddp_sim_t* s, int b0, int nb, hsddp_mc_extra_t* out) {
+    if (!sim_range_ok(s, b0, nb) || !out || s->last_mc == 0) return HSDDP_EINVAL;
+    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R;
+    if (s->last_mc == 2) { for (size_t i = 0; i < cnt; i++) { out[i].first_fall = -1; out[i].n_sat = 0; } return HSDDP_OK; }
+    HIPCK(hipSetDevice(s->h->device));
+    std::vector<double> r(cnt * 2);
+    HIPCK(hipMemcpy(r.data(), s->d_extra + off * 2, r.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < cnt; i++) { out[i].first_fall = (int)r[2 * i]; out[i].n_sat = (int)r[2 * i + 1]; }
     return HSDDP_OK;
 }
 

@@ -373,9 +373,61 @@ constexpr int SIM_ROW = 5;      // dev_q | dev_v | min_height | max_torque | fir
 // A quad whose new state fails the rollout's divergence test (squared norm above 1e12 or NaN, wb_quad.hpp / SinglePhase.cpp:205) keeps the state it
 // had BEFORE that step and records nothing further, but goes on executing: the cross-lane steps need all four lanes, and the other quads of the
 // wave must not notice.  Trajectory entries behind first_bad repeat the kept state (controls: what the policy asks for there).
-template <class Q>
+//
+// Disturbances (include/hsddp_mc.h): the policy D, empty for the plain walk.  WbsMc points at the switches of a disturbed run; every `if constexpr
+// (D::MC)` below is its code, and with WbsPlain none of it exists: k_sim_quad compiles to what it compiled to before the policy was there.
+struct WbsMcArgs {
+    unsigned long long seed, first_problem;      // the generator's key; global index of problem 0 of the handle
+    double su, sq, sv, umax, fall;              // sigma_u, sigma_q, sigma_v (0: off), u_max, fall_height (<= 0: off)
+    int kick_step, R;                           // step of the push (-1: none); samples per problem
+    const double* kick; double* extra;          // [B R][36] or null; [B R][2] first_fall | n_sat
+};
+// NOISE 0: the walk of a run whose three sigmas are zero, compiled without the generator.  Measured (MI355X, config 3 x 16 samples x 200 steps, plain
+// run 9.88 ms): with the generator compiled in and branched over, a run with only u_max set took 11.74 ms - the register allocation of the whole
+// loop pays for code that does not run; without it 9.83 ms.  So the host picks the instantiation, and every other switch stays a run-time branch.
+struct WbsPlain { static constexpr int MC = 0, NOISE = 0; };
+template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_; const WbsMcArgs* a; };
+constexpr int SIM_PARK_MC = SIM_PARK + 2;       // ... and n_sat, first_fall
+
+// The generator (sim.mc_normals is its definition): draw(n) is output n >= 1 of SplitMix64(seed), whose state is the counter seed + n G; the normal of
+// coordinate c of (global problem, sample, step) is Box-Muller on draws n0 + 1 and n0 + 2, n0 = 2 (((problem 65536 + sample) 65536 + step) 48 + c).
+constexpr unsigned long long WBS_MC_G = 0x9E3779B97F4A7C15ull;
+HD double wbs_mc_unit(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
+    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
+}
+HD double wbs_mc_draw(unsigned long long seed, unsigned long long n) { return wbs_mc_unit(seed + n * WBS_MC_G); }
+// three normals per lane: coordinates c, c + 1, c + 2 of the (problem, sample, step) numbered `base`; c is the lane's own (a small integer in a double)
+HD void wbs_mc_normal3_lane(unsigned long long seed, unsigned long long base, int c, double (&z)[3]) {
+    unsigned long long st = seed + (2ull * (base * 48ull + (unsigned long long)c)) * WBS_MC_G;
+    _Pragma("unroll")
+    for (int j = 0; j < 3; j++) {
+        const double u1 = wbs_mc_unit(st + WBS_MC_G), u2 = wbs_mc_unit(st + 2ull * WBS_MC_G);
+        st += 2ull * WBS_MC_G;
+        // (1 - u1 is in (0, 1].)  On the device cos(2 pi u2) is cospi(2 u2) of the device library: the same number without the rounding of 2 pi u2 and
+        // without cos's argument reduction - 19.9 -> 18.3 ms with all three sigmas on (same measurement as above)
+#ifdef HS_HOST_EMU
+        z[j] = sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
+#else
+        z[j] = sqrt(-2.0 * log(1.0 - u1)) * cospi(2.0 * u2);
+#endif
+    }
+}
+#ifdef HS_HOST_EMU
+inline void wbs_mc_normal3(unsigned long long seed, unsigned long long base, const Q4& c, Q4 (&z)[3]) {
+    for (int l = 0; l < 4; l++) { double t[3]; wbs_mc_normal3_lane(seed, base, (int)c.v[l], t); for (int j = 0; j < 3; j++) z[j].v[l] = t[j]; }
+}
+inline const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { return p; }
+#else
+HD void wbs_mc_normal3(unsigned long long seed, unsigned long long base, const double& c, double (&z)[3]) { wbs_mc_normal3_lane(seed, base, (int)c, z); }
+// the switches are read again at every step from a pointer the compiler cannot see through: held in scalar registers across the contact solve
+// they were spilled (as kernel arguments by value: 94 scalar registers in scratch)
+HD const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { asm volatile("" : "+s"(p)); return p; }
+#endif
+
+template <class Q, class D = WbsPlain>
 HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, int b, size_t g, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU,
-                 double* stash = nullptr) {
+                 double* stash = nullptr, const D& dist = D()) {
     using S = typename Q::S;
     const S zero = S(0.0), one = S(1.0);
     const S w0 = Q::legc(1.0, 0.0, 0.0, 0.0);      // the replicated base entries are counted once
@@ -383,6 +435,7 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
     _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::ld(x0, g * 36 + i, 0); vb[i] = Q::ld(x0, g * 36 + 18 + i, 0); }
     _Pragma("unroll") for (int j = 0; j < 3; j++) { ql[j] = Q::ld(x0, g * 36 + 6 + j, 3); vl[j] = Q::ld(x0, g * 36 + 24 + j, 3); }
     S alive = one, first_bad = S(-1.0);
+    S nsat = zero, ffall = S(-1.0);             // (disturbed walk only) saturated torques of the lane's leg; first step below fall_height
     S dq = zero, dv = zero, umax = zero, hmin = qb[2];      // (per-lane maxima over the base and the lane's leg: joined over the quad at the end)
     // deviation of the state from row `kx` of a phase's Xbar: base part replicated, the lane's leg
     auto deviation = [&](PhaseC& P, size_t kx, S (&eb)[6], S (&wb)[6], S (&el)[3], S (&wl)[3]) {
@@ -412,8 +465,8 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         S* const c = stash + threadIdx.x;
         S* v[24] = {&qb[0], &qb[1], &qb[2], &qb[3], &qb[4], &qb[5], &vb[0], &vb[1], &vb[2], &vb[3], &vb[4], &vb[5], &ql[0], &ql[1], &ql[2], &vl[0], &vl[1], &vl[2],
                     &dq, &dv, &umax, &hmin, &alive, &first_bad};
-        if (out) { _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; }
-        else { asm volatile("" ::: "memory"); _Pragma("unroll") for (int i = 0; i < 24; i++) *v[i] = c[64 * i]; }
+        if (out) { _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; if constexpr (D::MC) { c[64 * 24] = nsat; c[64 * 25] = ffall; } }
+        else { asm volatile("" ::: "memory"); _Pragma("unroll") for (int i = 0; i < 24; i++) *v[i] = c[64 * i]; if constexpr (D::MC) { nsat = c[64 * 24]; ffall = c[64 * 25]; } }
     };
 #endif
     // the rows of a knot the feedback reads: Xbar (base q, base v, leg q, leg v), Ubar and the lane's three rows of K
@@ -431,6 +484,30 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         PhaseC& P = ph[pi];
         const int h = P.h;
         const size_t kx = ((size_t)b * (h + 1) + k) * 36, ku = ((size_t)b * h + k) * 12, kg = ((size_t)b * h + k) * 432;
+        // ---- disturbed walk: the push, then the noise of this step - drawn here and consumed by the feedback below, so that nothing of it lives
+        // across the contact solve.  Every switch is a wave-uniform branch.  The twelve base entries of the estimate error are the same in the
+        // four lanes: lane l draws three of them (positions 0..2, 3..5, velocities 0..2, 3..5) and the quad reads them by broadcasts (every lane
+        // drawing all twelve: 24.8 ms against 19.9 ms, same measurement).
+        WbsMcArgs mc; S nz_b[3], nz_q[3], nz_v[3], nz_u[3];
+        if constexpr (D::MC) {
+            mc = *wbs_mc_fresh(dist.a);
+            if (s == mc.kick_step) {
+                const typename Q::B on = Q::gt(alive, S(0.5));
+                _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::sel(on, qb[i] + Q::ld(mc.kick, g * 36 + i, 0), qb[i]); vb[i] = Q::sel(on, vb[i] + Q::ld(mc.kick, g * 36 + 18 + i, 0), vb[i]); }
+                _Pragma("unroll") for (int j = 0; j < 3; j++) { ql[j] = Q::sel(on, ql[j] + Q::ld(mc.kick, g * 36 + 6 + j, 3), ql[j]); vl[j] = Q::sel(on, vl[j] + Q::ld(mc.kick, g * 36 + 24 + j, 3), vl[j]); }
+            }
+            if constexpr (D::NOISE) {
+                const unsigned long long base = ((mc.first_problem + (unsigned long long)b) * 65536ull + (unsigned long long)(g - (size_t)b * (size_t)mc.R)) * 65536ull + (unsigned long long)s;
+                if (mc.sq > 0.0 || mc.sv > 0.0) {
+                    wbs_mc_normal3(mc.seed, base, Q::legc(12.0, 15.0, 30.0, 33.0), nz_b);
+                    const S sg = Q::legc(mc.sq, mc.sq, mc.sv, mc.sv);
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) nz_b[j] = sg * nz_b[j];
+                }
+                if (mc.sq > 0.0) { wbs_mc_normal3(mc.seed, base, Q::legc(18.0, 21.0, 24.0, 27.0), nz_q); _Pragma("unroll") for (int j = 0; j < 3; j++) nz_q[j] = mc.sq * nz_q[j]; }
+                if (mc.sv > 0.0) { wbs_mc_normal3(mc.seed, base, Q::legc(36.0, 39.0, 42.0, 45.0), nz_v); _Pragma("unroll") for (int j = 0; j < 3; j++) nz_v[j] = mc.sv * nz_v[j]; }
+                if (mc.su > 0.0) { wbs_mc_normal3(mc.seed, base, Q::legc(0.0, 3.0, 6.0, 9.0), nz_u); _Pragma("unroll") for (int j = 0; j < 3; j++) nz_u[j] = mc.su * nz_u[j]; }
+            }
+        }
         // ---- feedback: the lane forms the three torques of its leg, rows 3 lane .. 3 lane + 2 of K (12 x 36, column-major) times x - xbar.  The
         // base part of x - xbar is in every lane already, the other legs' parts come by quad broadcasts.
         S ul[3];
@@ -444,6 +521,15 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
             _Pragma("unroll") for (int i = 0; i < 6; i++) { eb[i] = qb[i] - Xr[i]; wb[i] = vb[i] - Xr[6 + i]; }
             _Pragma("unroll") for (int j = 0; j < 3; j++) { el[j] = ql[j] - Xr[12 + j]; wl[j] = vl[j] - Xr[15 + j]; }
             record(eb, wb, el, wl);
+            if constexpr (D::MC) {      // the fall test on the recorded state; then the policy sees the estimate x + e
+                if (mc.fall > 0.0) ffall = Q::sel(Q::gt(alive * Q::sel(Q::gt(zero, ffall), one, zero) * Q::sel(Q::gt(S(mc.fall), qb[2]), one, zero), S(0.5)), S((double)s), ffall);
+                if (D::NOISE && mc.sq > 0.0) {
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) { eb[j] = eb[j] + Q::template get<0>(nz_b[j]); eb[3 + j] = eb[3 + j] + Q::template get<1>(nz_b[j]); el[j] = el[j] + nz_q[j]; }
+                }
+                if (D::NOISE && mc.sv > 0.0) {
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) { wb[j] = wb[j] + Q::template get<2>(nz_b[j]); wb[3 + j] = wb[3 + j] + Q::template get<3>(nz_b[j]); wl[j] = wl[j] + nz_v[j]; }
+                }
+            }
             S dx[36];
             _Pragma("unroll") for (int i = 0; i < 6; i++) { dx[i] = eb[i]; dx[18 + i] = wb[i]; }
             _Pragma("unroll") for (int j = 0; j < 3; j++) {
@@ -456,6 +542,14 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                 S acc = Kr[j][0] * dx[0];
                 _Pragma("unroll") for (int c = 1; c < 36; c++) acc = acc + Kr[j][c] * dx[c];
                 ul[j] = Ur[j] + acc;
+                if constexpr (D::MC) {      // the actuator: noise on the commanded torque, then the limit
+                    if (D::NOISE && mc.su > 0.0) ul[j] = ul[j] + nz_u[j];
+                    if (mc.umax > 0.0) {
+                        const S lim = S(mc.umax);
+                        nsat = nsat + Q::sel(Q::gt(alive * Q::sel(Q::gt(wbs_abs<Q, S>(ul[j]), lim), one, zero), S(0.5)), one, zero);
+                        ul[j] = Q::sel(Q::gt(ul[j], lim), lim, Q::sel(Q::gt(-lim, ul[j]), -lim, ul[j]));
+                    }
+                }
                 um = wbs_max<Q, S>(um, wbs_abs<Q, S>(ul[j]));
             }
             umax = Q::sel(Q::gt(alive, S(0.5)), wbs_max<Q, S>(umax, um), umax);
@@ -507,6 +601,11 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         deviation(P, ((size_t)b * (P.h + 1) + k + 1) * 36, eb, wb, el, wl);
         record(eb, wb, el, wl);
     }
+    if constexpr (D::MC) {      // the final state takes the fall test with index n_steps
+        const WbsMcArgs mc = *wbs_mc_fresh(dist.a);
+        if (mc.fall > 0.0) ffall = Q::sel(Q::gt(alive * Q::sel(Q::gt(zero, ffall), one, zero) * Q::sel(Q::gt(S(mc.fall), qb[2]), one, zero), S(0.5)), S((double)n_steps), ffall);
+        Q::st0(mc.extra, g * 2, ffall); Q::st0(mc.extra, g * 2 + 1, Q::sum(nsat));
+    }
     if (trajX != nullptr) store_state((g * (size_t)(n_steps + 1) + n_steps) * 36);
     _Pragma("unroll") for (int i = 0; i < 6; i++) { Q::st0(xfinal, g * 36 + i, qb[i]); Q::st0(xfinal, g * 36 + 18 + i, vb[i]); }
     _Pragma("unroll") for (int j = 0; j < 3; j++) { Q::st(xfinal, g * 36 + 6 + j, 3, ql[j]); Q::st(xfinal, g * 36 + 24 + j, 3, vl[j]); }
@@ -526,6 +625,20 @@ k_sim_quad(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_
     if (g >= total) return;      // (a quad leaves or stays as a whole)
     wbs_walk<QS>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash);
 }
+// The disturbed walk (hsddp_mc_run): the same program with the WbsMc policy; mc points at the run's switches in device memory.  k_sim_quad_mc
+// draws noise, k_sim_quad_mc0 is the walk of a run without any (see WbsMc).
+#define WBS_MC_KERNEL(NAME, NOISE)                                                                                                                                             \
+    __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))                                                                               \
+    NAME(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU, \
+         const WbsMcArgs* mc) {                                                                                                                                                \
+        __shared__ double stash[SIM_PARK_MC * 64];                                                                                                                             \
+        const int g = blockIdx.x * 16 + (threadIdx.x >> 2);                                                                                                                    \
+        if (g >= total) return;                                                                                                                                                \
+        wbs_walk<QS, WbsMc<NOISE>>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, WbsMc<NOISE>{mc});                         \
+    }
+WBS_MC_KERNEL(k_sim_quad_mc, 1)
+WBS_MC_KERNEL(k_sim_quad_mc0, 0)
+#undef WBS_MC_KERNEL
 #endif
 
 }  // namespace hs

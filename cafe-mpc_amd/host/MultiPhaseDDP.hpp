@@ -19,6 +19,7 @@
 #include "hsddp_hkd.h"
 #include "hsddp_refs.h"
 #include "hsddp_sim.h"
+#include "hsddp_mc.h"
 
 namespace hsddp {
 
@@ -39,7 +40,9 @@ struct SimResult {
     std::vector<hsddp_sim_row_t> rows;      // batch x n_samples
     std::vector<double> x_final;            // batch x n_samples x 36
     std::vector<double> X, U;               // keep_traj: batch x n_samples x (n_steps + 1) x 36, batch x n_samples x n_steps x 12
+    std::vector<hsddp_mc_extra_t> extra;    // batch x n_samples after a disturbed run (include/hsddp_mc.h), else empty
 };
+inline hsddp_mc_dist_t default_disturbance() { return hsddp_mc_dist_t{}; }      // every switch off
 class Simulation {
 public:
     Simulation(hsddp_handle_t* h, int batch, int n_samples, int n_steps, bool keep_traj = false) : batch_(batch), R_(n_samples), n_(n_steps), keep_(keep_traj) {
@@ -50,7 +53,13 @@ public:
     Simulation(const Simulation&) = delete;
     Simulation& operator=(const Simulation&) = delete;
     // x0: batch x n_samples x 36 (host memory, or device memory with src_device = 1)
-    bool run(const double* x0, int src_device = 0) { rc_ = s_ ? hsddp_sim_run(s_, x0, src_device) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    bool run(const double* x0, int src_device = 0) { rc_ = s_ ? hsddp_sim_run(s_, x0, src_device) : HSDDP_EINVAL; if (rc_ == HSDDP_OK) mc_ = false; return rc_ == HSDDP_OK; }
+    // disturbed run: actuator / estimate noise, torque limit, fall height, and a push kick (batch x n_samples x 36, or null) at dist.kick_step
+    bool run(const double* x0, const hsddp_mc_dist_t& dist, const double* kick, int src_device = 0, int kick_device = 0) {
+        rc_ = s_ ? hsddp_mc_run(s_, x0, src_device, &dist, kick, kick_device) : HSDDP_EINVAL;
+        if (rc_ == HSDDP_OK) mc_ = true;
+        return rc_ == HSDDP_OK;
+    }
     SimResult result() {
         SimResult r;
         if (!s_) return r;
@@ -61,13 +70,14 @@ public:
             r.X.resize(cnt * (size_t)(n_ + 1) * 36); r.U.resize(cnt * (size_t)n_ * 12);
             rc_ = hsddp_sim_get_traj(s_, 0, batch_, r.X.data(), r.U.data());
         }
+        if (rc_ == HSDDP_OK && mc_) { r.extra.resize(cnt); rc_ = hsddp_mc_get_extra(s_, 0, batch_, r.extra.data()); }
         return r;
     }
     const double* device_final() { return s_ ? hsddp_sim_device_final(s_) : nullptr; }      // batch x n_samples x 36 on the device
     int last_error() const { return rc_; }
 private:
     hsddp_sim_t* s_ = nullptr;
-    int batch_, R_, n_, rc_ = 0; bool keep_;
+    int batch_, R_, n_, rc_ = 0; bool keep_, mc_ = false;
 };
 
 template <typename T = double>

@@ -7,12 +7,46 @@
     sim = Simulation(solver, n_samples=16, n_steps=50)  # kept across ticks: run() makes no device allocation
     sim.run(x0); rows, x_final = sim.rows()
 
-Nothing here computes anything: the rollout is the k_sim_quad kernel (csrc/wb_sim.hpp)."""
+    d = Disturbance(seed=7, sigma_u=0.2, sigma_q=1e-3, sigma_v=1e-2, u_max=17.0, fall_height=0.16)      # include/hsddp_mc.h
+    res = solver.simulate(x0, n_steps=50, dist=d, kick=kick)      # kick [B, 16, 36] at d.kick_step; res["extra"]["first_fall"], ["n_sat"]
+
+Nothing here computes anything: the rollout is the k_sim_quad / k_sim_quad_mc kernel (csrc/wb_sim.hpp).  mc_normals states the generator of the
+disturbed runs in numpy: the definition the kernel mirrors."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
 from . import _abi
+from .problems import SplitMix64
+
+
+@dataclasses.dataclass
+class Disturbance:
+    """hsddp_mc_dist_t: the switches of a disturbed run.  A sigma of 0, u_max <= 0, fall_height <= 0 switch their term off."""
+    seed: int = 0
+    sigma_u: float = 0.0
+    sigma_q: float = 0.0
+    sigma_v: float = 0.0
+    u_max: float = 0.0
+    fall_height: float = 0.0
+    kick_step: int = 0
+    first_problem: int = 0
+
+    def to_c(self):
+        return _abi.McDist(self.seed & ((1 << 64) - 1), self.sigma_u, self.sigma_q, self.sigma_v, self.u_max, self.fall_height, self.kick_step, self.first_problem)
+
+
+def mc_normals(seed, problem, r, s):
+    """The 48 standard normal numbers of (global problem, sample r, step s) of a disturbed run: coordinate c = 0..11 is added (times sigma_u) to
+    the torque of joint c, c = 12..47 (times sigma_q / sigma_v) to state coordinate c - 12 of the estimate.  Coordinate c is Box-Muller on draws
+    n0 + 1 and n0 + 2 of SplitMix64(seed), n0 = 2 (((problem 65536 + r) 65536 + s) 48 + c): a function of its arguments alone."""
+    if not (problem >= 0 and 0 <= r < 65536 and 0 <= s <= 65536):
+        raise ValueError(f"mc_normals: problem {problem}, sample {r}, step {s}")
+    rng = SplitMix64(seed)
+    rng.skip(2 * 48 * ((problem * 65536 + r) * 65536 + s))
+    u = np.array([rng.next() for _ in range(96)])
+    return np.sqrt(-2.0 * np.log(1.0 - u[0::2])) * np.cos(2.0 * np.pi * u[1::2])      # 1 - u is in (0, 1]
 
 
 class Simulation:
@@ -20,6 +54,7 @@ class Simulation:
 
     def __init__(self, solver, n_samples, n_steps, keep_traj=False):
         self.lib = _abi.bind_sim(solver.lib)      # raises on a library without include/hsddp_sim.h (the CPU checker)
+        self.disturbed = False
         self.solver, self.R, self.n_steps, self.keep_traj = solver, int(n_samples), int(n_steps), bool(keep_traj)
         self.s = C.c_void_p()
         rc = self.lib.hsddp_sim_create(solver.h, self.R, self.n_steps, 1 if keep_traj else 0, C.byref(self.s))
@@ -38,22 +73,46 @@ class Simulation:
         except Exception:
             pass
 
-    def run(self, x0):
-        """x0: [B, R, 36] float64, a numpy array (copied) or a contiguous torch tensor on the handle's device (read in place)."""
+    def _source(self, name, x):
+        """(address, on the device, what keeps it alive) of a [B, R, 36] float64 numpy array or contiguous torch tensor on the handle's device."""
         shape = (self.solver.batch, self.R, 36)
-        if type(x0).__module__.startswith("torch"):
+        if type(x).__module__.startswith("torch"):
             import torch
-            if x0.dtype != torch.float64 or not x0.is_contiguous() or x0.device.type != "cuda" or tuple(x0.shape) != shape:
-                raise ValueError(f"x0: need a contiguous float64 tensor of shape {shape} on the handle's device, got {x0.dtype} {tuple(x0.shape)} on {x0.device}")
-            torch.cuda.current_stream(x0.device).synchronize()      # the kernel runs on the handle's stream
-            rc = self.lib.hsddp_sim_run(self.s, x0.data_ptr(), 1)
-        else:
-            x0 = np.ascontiguousarray(x0, dtype=np.float64)
-            if x0.shape != shape:
-                raise ValueError(f"x0: shape {x0.shape}, need {shape}")
-            rc = self.lib.hsddp_sim_run(self.s, x0.ctypes.data, 0)
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.device.type != "cuda" or tuple(x.shape) != shape:
+                raise ValueError(f"{name}: need a contiguous float64 tensor of shape {shape} on the handle's device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+            torch.cuda.current_stream(x.device).synchronize()      # the kernel runs on the handle's stream
+            return x.data_ptr(), 1, x
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != shape:
+            raise ValueError(f"{name}: shape {x.shape}, need {shape}")
+        return x.ctypes.data, 0, x
+
+    def run(self, x0, dist=None, kick=None):
+        """x0: [B, R, 36] float64, a numpy array (copied) or a contiguous torch tensor on the handle's device (read in place).
+        dist (Disturbance) and / or kick ([B, R, 36], as x0; added to the state at step dist.kick_step): a disturbed run (include/hsddp_mc.h)."""
+        p, dev, keep = self._source("x0", x0)
+        if dist is None and kick is None:
+            rc = self.lib.hsddp_sim_run(self.s, p, dev)
+            if rc != 0:
+                raise RuntimeError(f"hsddp_sim_run failed rc={rc}")
+            self.disturbed = False
+            return
+        _abi.bind_mc(self.lib)
+        d = (dist if dist is not None else Disturbance()).to_c()
+        kp, kdev, kkeep = self._source("kick", kick) if kick is not None else (None, 0, None)
+        rc = self.lib.hsddp_mc_run(self.s, p, dev, C.byref(d), kp, kdev)
         if rc != 0:
-            raise RuntimeError(f"hsddp_sim_run failed rc={rc}")
+            raise RuntimeError(f"hsddp_mc_run failed rc={rc}")
+        self.disturbed = True
+
+    def extra(self, b0=0, nb=None):
+        """Structured array [nb, R] of hsddp_mc_extra_t (first_fall, n_sat) of the last run, which has to be a disturbed one."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        out = np.zeros((max(nb, 0), self.R), dtype=_abi.MC_EXTRA_DTYPE)
+        rc = _abi.bind_mc(self.lib).hsddp_mc_get_extra(self.s, b0, nb, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_mc_get_extra failed rc={rc}")
+        return out
 
     def rows(self, b0=0, nb=None):
         """(rows [nb, R] as a structured array of hsddp_sim_row_t, x_final [nb, R, 36]) of the last run."""
@@ -85,13 +144,16 @@ class Simulation:
         return float(ms.value)
 
 
-def simulate(solver, x0, n_steps, keep_traj=False):
-    """One-off simulation on `solver`: dict with rows, x_final and, with keep_traj, X and U (see Simulation)."""
+def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None):
+    """One-off simulation on `solver`: dict with rows, x_final and, with keep_traj, X and U (see Simulation); a disturbed run (dist / kick given)
+    returns extra too."""
     sim = Simulation(solver, x0.shape[1], n_steps, keep_traj)
     try:
-        sim.run(x0)
+        sim.run(x0, dist=dist, kick=kick)
         rows, xf = sim.rows()
         out = dict(rows=rows, x_final=xf)
+        if sim.disturbed:
+            out["extra"] = sim.extra()
         if keep_traj:
             out["X"], out["U"] = sim.traj()
         return out
