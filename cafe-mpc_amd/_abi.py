@@ -259,6 +259,30 @@ def bind_mc(lib):
     return lib
 
 
+# include/hsddp_grf.h: ground-reaction-force records of a simulation object (libhsddp_hip.so only)
+GRF_EXPORTS = ["hsddp_grf_set", "hsddp_grf_get"]
+
+
+class GrfRow(C.Structure):
+    """hsddp_grf_row_t"""
+    _fields_ = [("min_fz", C.c_double), ("min_cone", C.c_double), ("max_fz", C.c_double), ("first_slip", C.c_int), ("n_slip", C.c_int)]
+
+
+GRF_ROW_DTYPE = np.dtype([("min_fz", "<f8"), ("min_cone", "<f8"), ("max_fz", "<f8"), ("first_slip", "<i4"), ("n_slip", "<i4")])
+
+
+def bind_grf(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_grf.h (and of hsddp_sim.h, which they work on).  Raises if the library lacks any."""
+    missing = [s for s in GRF_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the contact-force record entry points {missing}")
+    bind_sim(lib)
+    H = C.c_void_p
+    lib.hsddp_grf_set.argtypes = [H, C.c_double, C.c_double]
+    lib.hsddp_grf_get.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return lib
+
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -514,14 +538,16 @@ class Solver:
                  "get_references")
         return out
 
-    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None):
+    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None):
         """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)
         over the first n_steps whole-body control knots (include/hsddp_sim.h): dict with rows (structured array [batch, R] of dev_q, dev_v,
         min_height, max_torque, first_bad), x_final [batch, R, 36] and, with keep_traj, X [batch, R, n_steps + 1, 36] and U [batch, R, n_steps, 12].
         sim.Simulation keeps the device object across calls.  dist (sim.Disturbance) / kick [batch, R, 36]: a disturbed run (include/hsddp_mc.h),
-        which also returns extra (structured array [batch, R] of first_fall, n_sat)."""
+        which also returns extra (structured array [batch, R] of first_fall, n_sat).  grf = (mu, fz_min): contact-force records
+        (include/hsddp_grf.h), grf (structured array [batch, R] of min_fz, min_cone, max_fz, first_slip, n_slip) and, with keep_traj, Y
+        [batch, R, n_steps, 12]."""
         from . import sim
-        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick)
+        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf)
 
     def get_history(self, problem=0, cap=4096):
         """MultiPhaseDDP::get_solver_info(cost, dyn_feas, eqn_feas, ineq_feas) (MultiPhaseDDP.h:85): the four float history buffers."""

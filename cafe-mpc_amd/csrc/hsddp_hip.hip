@@ -19,6 +19,7 @@
 #include "hsddp_hkd.h"
 #include "hsddp_refs.h"
 #include "hsddp_sim.h"
+#include "hsddp_grf.h"
 #include "hsddp_mc.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
@@ -1701,12 +1702,15 @@ struct hsddp_sim {
     // disturbed runs (hsddp_mc.h): allocated at the first one.  last_mc: 0 the last run was plain, 1 disturbed, 2 hsddp_mc_run with every switch off
     double *d_extra = nullptr, *d_kick = nullptr; WbsMcArgs* d_mc = nullptr;      // [B R][2] first_fall | n_sat ; staging of a host kick ; the switches
     int last_mc = 0;
+    // contact-force records (hsddp_grf.h): allocated by the first hsddp_grf_set that switches them on.  grf_on: what later runs do; last_grf: what the last run did
+    double *d_grf_rows = nullptr, *d_Y = nullptr; WbsGrfArgs* d_grf = nullptr;      // [B R][SIM_GRF_ROW] ; [B R][n_steps][12] (keep) ; thresholds and destinations
+    bool grf_on = false, last_grf = false;
 };
 static void sim_free(hsddp_sim* s) {
     if (!s) return;
     hipSetDevice(s->h->device);
     if (s->h->stream) hipStreamSynchronize(s->h->stream);
-    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc};
+    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf};
     for (void* q : p) if (q) hipFree(q);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -1750,22 +1754,32 @@ int hsddp_sim_create(hsddp_handle_t* h, int n_samples, int n_steps, int keep_tra
 
 void hsddp_sim_destroy(hsddp_sim_t* s) { sim_free(s); }
 
-// the one launch path of a run: the plain kernel, or (mc) the disturbed one with the switches that are already on the device at s->d_mc
+// the one launch path of a run: the plain kernel, or (mc) the disturbed one with the switches that are already on the device at s->d_mc; with the
+// contact-force records on (hsddp_grf_set), the twin of that kernel that keeps them
 static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, bool noise = false) {
     hsddp_handle* h = s->h;
     const size_t total = (size_t)h->batch * s->R;
     if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
     HIPCK(hipEventRecord(s->ev0, h->stream));
-    if (!mc)
-        hipLaunchKernelGGL(k_sim_quad, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
-                           src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U);
-    else
-        hipLaunchKernelGGL(noise ? k_sim_quad_mc : k_sim_quad_mc0, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
-                           src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, (const WbsMcArgs*)s->d_mc);
+    if (!s->grf_on) {
+        if (!mc)
+            hipLaunchKernelGGL(k_sim_quad, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
+                               src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U);
+        else
+            hipLaunchKernelGGL(noise ? k_sim_quad_mc : k_sim_quad_mc0, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
+                               src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, (const WbsMcArgs*)s->d_mc);
+    } else {
+        if (!mc)
+            hipLaunchKernelGGL(k_sim_quad_grf, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
+                               src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, (const WbsGrfArgs*)s->d_grf);
+        else
+            hipLaunchKernelGGL(noise ? k_sim_quad_mc_grf : k_sim_quad_mc0_grf, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
+                               src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, (const WbsMcArgs*)s->d_mc, (const WbsGrfArgs*)s->d_grf);
+    }
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(s->ev1, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    s->timed = true;
+    s->timed = true; s->last_grf = s->grf_on;
     return HSDDP_OK;
 }
 
@@ -1842,6 +1856,40 @@ int hsddp_sim_get_traj(hsddp_sim_t* s, int b0, int nb, double* X, double* U) {
     const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R, sx = (size_t)(s->n_steps + 1) * 36, su = (size_t)s->n_steps * 12;
     if (X) HIPCK(hipMemcpy(X, s->d_X + off * sx, cnt * sx * 8, hipMemcpyDeviceToHost));
     if (U) HIPCK(hipMemcpy(U, s->d_U + off * su, cnt * su * 8, hipMemcpyDeviceToHost));
+    return HSDDP_OK;
+}
+
+int hsddp_grf_set(hsddp_sim_t* s, double mu, double fz_min) {
+    if (!s || !std::isfinite(mu) || !std::isfinite(fz_min) || mu < 0.0 || fz_min < 0.0) return HSDDP_EINVAL;
+    if (mu == 0.0) { s->grf_on = false; return HSDDP_OK; }      // later runs launch the kernels without records; the buffers are kept
+    hsddp_handle* h = s->h;
+    HIPCK(hipSetDevice(h->device));
+    const size_t total = (size_t)h->batch * s->R;
+    // (as MC_CK of hsddp_mc_run: an allocation that fails returns its code at once; the buffers made before it are kept for the next call and freed
+    // with the object, and the records stay off - "nothing changed" holds for what a run does, not for those allocations)
+#define GRF_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
+    if (!s->d_grf_rows) GRF_CK(hipMalloc((void**)&s->d_grf_rows, total * SIM_GRF_ROW * 8));
+    if (s->keep && !s->d_Y) GRF_CK(hipMalloc((void**)&s->d_Y, total * (size_t)s->n_steps * 12 * 8));
+    if (!s->d_grf) GRF_CK(hipMalloc((void**)&s->d_grf, sizeof(WbsGrfArgs)));
+#undef GRF_CK
+    WbsGrfArgs a;
+    a.mu = mu; a.fz_min = fz_min; a.rows = s->d_grf_rows; a.Y = s->keep ? s->d_Y : nullptr;
+    HIPCK(hipMemcpyAsync(s->d_grf, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));      // (pageable source: staged before the call returns; the runs are on this stream)
+    s->grf_on = true;
+    return HSDDP_OK;
+}
+
+int hsddp_grf_get(hsddp_sim_t* s, int b0, int nb, hsddp_grf_row_t* rows, double* Y) {
+    if (!sim_range_ok(s, b0, nb) || !rows || !s->last_grf || (Y && !s->keep)) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(s->h->device));
+    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R, sy = (size_t)s->n_steps * 12;
+    std::vector<double> r(cnt * SIM_GRF_ROW);
+    HIPCK(hipMemcpy(r.data(), s->d_grf_rows + off * SIM_GRF_ROW, r.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < cnt; i++) {
+        const double* q = &r[i * SIM_GRF_ROW];
+        rows[i].min_fz = q[0]; rows[i].min_cone = q[1]; rows[i].max_fz = q[2]; rows[i].first_slip = (int)q[3]; rows[i].n_slip = (int)q[4];
+    }
+    if (Y) HIPCK(hipMemcpy(Y, s->d_Y + off * sy, cnt * sy * 8, hipMemcpyDeviceToHost));
     return HSDDP_OK;
 }
 

@@ -55,9 +55,14 @@ template <class Q, class S> HD S wbs_qmax(const S& a) { return -Q::vmin(-a); }  
 
 // Contact dynamics of one state on a lane quad.  cmask: bit l = leg l is in the contact set; mode, damping, bg_alpha: see the head of the file
 // (all four wave-uniform).  out_b (6, replicated) / out_l (the lane's leg): mode 0 the accelerations qdd, mode 1 the velocities after the impact.
-template <class Q, class S = typename Q::S>
+// lam_out (optional, one V3<S>*): the contact force of the lane's foot, world axes - the multiplier of the solve; zero for a leg outside the contact
+// set.  It is a parameter PACK so that a call without it instantiates the function it instantiated before the output existed, signature and body:
+// as a defaulted pointer argument it moved the register allocation of every caller (k_sim_quad: 24 -> 0 B of scratch - welcome, but not this
+// change's business, which has to leave the existing kernels what they are).  The store keeps its null test although no caller passes null: with it
+// the three kernels that take the force compile to 0 / 76 / 0 B of scratch per lane, without it to 40 / 148 / 44 (make resources).
+template <class Q, class S = typename Q::S, class... LO>
 HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double damping, double bg_alpha, const S (&qb)[6], const S (&vb)[6], const S (&ql)[3],
-                             const S (&vl_)[3], const S (&ul)[3], S (&out_b)[6], V3<S>& out_l) {
+                             const S (&vl_)[3], const S (&ul)[3], S (&out_b)[6], V3<S>& out_l, LO*... lam_out) {
     const S zero = S(0.0);
     const double m0 = mode == 0 ? 1.0 : 0.0, m1 = 1.0 - m0;      // (1.0 * x is x: mode 0 is the arithmetic of wbq_rollout_knot)
     const S sx = Q::legc(1.0, 1.0, -1.0, -1.0), sy = Q::legc(1.0, -1.0, 1.0, -1.0);
@@ -346,6 +351,7 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         rhs = {pick(lam0.x, lam1.x, lam2.x, lam3.x), pick(lam0.y, lam1.y, lam2.y, lam3.y), pick(lam0.z, lam1.z, lam2.z, lam3.z)};
     }
     const V3<S> lam = scale(cl, rhs);      // contact force of the lane's foot (world axes); zero for a swing leg
+    if constexpr (sizeof...(LO) > 0) { ((lam_out != nullptr ? (void)(*lam_out = lam) : (void)0), ...); }
     // qdd = L^-T (y + X lam): base part replicated, leg part in the lane
     S qddb[6]; V3<S> qddl;
     {
@@ -385,9 +391,22 @@ struct WbsMcArgs {
 // NOISE 0: the walk of a run whose three sigmas are zero, compiled without the generator.  Measured (MI355X, config 3 x 16 samples x 200 steps, plain
 // run 9.88 ms): with the generator compiled in and branched over, a run with only u_max set took 11.74 ms - the register allocation of the whole
 // loop pays for code that does not run; without it 9.83 ms.  So the host picks the instantiation, and every other switch stays a run-time branch.
-struct WbsPlain { static constexpr int MC = 0, NOISE = 0; };
-template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_; const WbsMcArgs* a; };
+struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0; };
+template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0; const WbsMcArgs* a; };
 constexpr int SIM_PARK_MC = SIM_PARK + 2;       // ... and n_sat, first_fall
+// Contact-force records (include/hsddp_grf.h): GRF 1 in the policy.  The walk takes the lane's multiplier of every mode-0 solve, keeps five running
+// values per lane (lane = leg) - smallest / largest stance fz, smallest cone margin, first violating step, violations - and joins them over the
+// quad at the end; every `if constexpr (D::GRF)` below is its code, and the policies above compile to what they compiled to without it.  The
+// thresholds and the destinations live in device memory and are read through a laundered pointer, as the switches of a disturbed run are.
+struct WbsGrfArgs {
+    double mu, fz_min;          // friction coefficient of the pyramid (> 0); smallest admissible normal force
+    double* rows; double* Y;    // [B R][SIM_GRF_ROW]; [B R][n_steps][12] or null
+};
+constexpr int SIM_GRF_ROW = 5;     // min_fz | min_cone | max_fz | first_slip | n_slip
+constexpr int SIM_GRF_PARK = 5;    // the lane's running values, parked behind the others
+constexpr double SIM_GRF_NONE = 1e18;      // first_slip of a lane without a violation while the walk runs: above every step index
+struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1; const WbsGrfArgs* gr; };
+template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; };
 
 // The generator (sim.mc_normals is its definition): draw(n) is output n >= 1 of SplitMix64(seed), whose state is the counter seed + n G; the normal of
 // coordinate c of (global problem, sample, step) is Box-Muller on draws n0 + 1 and n0 + 2, n0 = 2 (((problem 65536 + sample) 65536 + step) 48 + c).
@@ -418,11 +437,13 @@ inline void wbs_mc_normal3(unsigned long long seed, unsigned long long base, con
     for (int l = 0; l < 4; l++) { double t[3]; wbs_mc_normal3_lane(seed, base, (int)c.v[l], t); for (int j = 0; j < 3; j++) z[j].v[l] = t[j]; }
 }
 inline const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { return p; }
+inline const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { return p; }
 #else
 HD void wbs_mc_normal3(unsigned long long seed, unsigned long long base, const double& c, double (&z)[3]) { wbs_mc_normal3_lane(seed, base, (int)c, z); }
 // the switches are read again at every step from a pointer the compiler cannot see through: held in scalar registers across the contact solve
 // they were spilled (as kernel arguments by value: 94 scalar registers in scratch)
 HD const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { asm volatile("" : "+s"(p)); return p; }
+HD const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { asm volatile("" : "+s"(p)); return p; }
 #endif
 
 template <class Q, class D = WbsPlain>
@@ -437,6 +458,8 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
     S alive = one, first_bad = S(-1.0);
     S nsat = zero, ffall = S(-1.0);             // (disturbed walk only) saturated torques of the lane's leg; first step below fall_height
     S dq = zero, dv = zero, umax = zero, hmin = qb[2];      // (per-lane maxima over the base and the lane's leg: joined over the quad at the end)
+    // (records only) of the lane's foot while it is a stance foot: smallest / largest fz, smallest cone margin, first violating step, violations
+    S gfmin = S(HUGE_VAL), gcmin = S(HUGE_VAL), gfmax = S(-HUGE_VAL), gfirst = S(SIM_GRF_NONE), gslip = zero;
     // deviation of the state from row `kx` of a phase's Xbar: base part replicated, the lane's leg
     auto deviation = [&](PhaseC& P, size_t kx, S (&eb)[6], S (&wb)[6], S (&el)[3], S (&wl)[3]) {
         _Pragma("unroll") for (int i = 0; i < 6; i++) { eb[i] = qb[i] - Q::ld(P.Xbar, kx + i, 0); wb[i] = vb[i] - Q::ld(P.Xbar, kx + 18 + i, 0); }
@@ -465,8 +488,14 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         S* const c = stash + threadIdx.x;
         S* v[24] = {&qb[0], &qb[1], &qb[2], &qb[3], &qb[4], &qb[5], &vb[0], &vb[1], &vb[2], &vb[3], &vb[4], &vb[5], &ql[0], &ql[1], &ql[2], &vl[0], &vl[1], &vl[2],
                     &dq, &dv, &umax, &hmin, &alive, &first_bad};
-        if (out) { _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; if constexpr (D::MC) { c[64 * 24] = nsat; c[64 * 25] = ffall; } }
-        else { asm volatile("" ::: "memory"); _Pragma("unroll") for (int i = 0; i < 24; i++) *v[i] = c[64 * i]; if constexpr (D::MC) { nsat = c[64 * 24]; ffall = c[64 * 25]; } }
+        constexpr int G0 = D::MC ? SIM_PARK_MC : SIM_PARK;      // (records) the five running values behind the others
+        if (out) {
+            _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; if constexpr (D::MC) { c[64 * 24] = nsat; c[64 * 25] = ffall; }
+            if constexpr (D::GRF) { c[64 * G0] = gfmin; c[64 * (G0 + 1)] = gcmin; c[64 * (G0 + 2)] = gfmax; c[64 * (G0 + 3)] = gfirst; c[64 * (G0 + 4)] = gslip; }
+        } else {
+            asm volatile("" ::: "memory"); _Pragma("unroll") for (int i = 0; i < 24; i++) *v[i] = c[64 * i]; if constexpr (D::MC) { nsat = c[64 * 24]; ffall = c[64 * 25]; }
+            if constexpr (D::GRF) { gfmin = c[64 * G0]; gcmin = c[64 * (G0 + 1)]; gfmax = c[64 * (G0 + 2)]; gfirst = c[64 * (G0 + 3)]; gslip = c[64 * (G0 + 4)]; }
+        }
     };
 #endif
     // the rows of a knot the feedback reads: Xbar (base q, base v, leg q, leg v), Ubar and the lane's three rows of K
@@ -572,8 +601,28 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         for (int mode = 0; mode <= reset; mode++) {
             S ob[6]; V3<S> ol;
             park(true);
-            wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol);
-            park(false);
+            if constexpr (D::GRF) {
+                V3<S> lam;
+                wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol, &lam);
+                park(false);
+                // ---- records: the force of the step on the lane's foot, counted if the foot is a stance foot of the phase (a select on the
+                // wave-uniform contact mask) and the sample had not diverged before the step (`alive` is still the value the step began with).
+                // The impact takes no record.
+                if (mode == 0) {
+                    const WbsGrfArgs ga = *wbs_grf_fresh(dist.gr);
+                    const S st = Q::legc((cm_dyn & 1) ? 1.0 : 0.0, (cm_dyn & 2) ? 1.0 : 0.0, (cm_dyn & 4) ? 1.0 : 0.0, (cm_dyn & 8) ? 1.0 : 0.0);
+                    const typename Q::B on = Q::gt(alive * st, S(0.5));
+                    const S cone = ga.mu * lam.z - wbs_max<Q, S>(wbs_abs<Q, S>(lam.x), wbs_abs<Q, S>(lam.y));
+                    const S bad = wbs_max<Q, S>(Q::sel(Q::gt(S(ga.fz_min), lam.z), one, zero), Q::sel(Q::gt(zero, cone), one, zero));
+                    const typename Q::B slip = Q::gt(alive * st * bad, S(0.5));
+                    gfmin = Q::sel(on, Q::min(gfmin, lam.z), gfmin); gcmin = Q::sel(on, Q::min(gcmin, cone), gcmin); gfmax = Q::sel(on, wbs_max<Q, S>(gfmax, lam.z), gfmax);
+                    gfirst = Q::sel(slip, Q::min(gfirst, S((double)s)), gfirst); gslip = gslip + Q::sel(slip, one, zero);
+                    if (ga.Y != nullptr) { Q::st(ga.Y, (g * (size_t)n_steps + s) * 12, 3, lam.x); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 1, 3, lam.y); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 2, 3, lam.z); }
+                }
+            } else {
+                wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol);
+                park(false);
+            }
             if (mode == 0) {      // forward Euler (WBM.cpp:25-26), then the divergence test on the new state
                 S xb[6], yb[6], xl[3], yl[3], nsq = zero;
                 _Pragma("unroll") for (int i = 0; i < 6; i++) { xb[i] = qb[i] + vb[i] * dt; yb[i] = vb[i] + ob[i] * dt; nsq = nsq + w0 * (xb[i] * xb[i] + yb[i] * yb[i]); }
@@ -605,6 +654,12 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         const WbsMcArgs mc = *wbs_mc_fresh(dist.a);
         if (mc.fall > 0.0) ffall = Q::sel(Q::gt(alive * Q::sel(Q::gt(zero, ffall), one, zero) * Q::sel(Q::gt(S(mc.fall), qb[2]), one, zero), S(0.5)), S((double)n_steps), ffall);
         Q::st0(mc.extra, g * 2, ffall); Q::st0(mc.extra, g * 2 + 1, Q::sum(nsat));
+    }
+    if constexpr (D::GRF) {      // the quad's record: the four feet joined (first_slip: the earliest; none: -1)
+        const WbsGrfArgs ga = *wbs_grf_fresh(dist.gr);
+        const S first = Q::vmin(gfirst);
+        Q::st0(ga.rows, g * SIM_GRF_ROW, Q::vmin(gfmin)); Q::st0(ga.rows, g * SIM_GRF_ROW + 1, Q::vmin(gcmin)); Q::st0(ga.rows, g * SIM_GRF_ROW + 2, wbs_qmax<Q, S>(gfmax));
+        Q::st0(ga.rows, g * SIM_GRF_ROW + 3, Q::sel(Q::gt(first, S(0.5 * SIM_GRF_NONE)), S(-1.0), first)); Q::st0(ga.rows, g * SIM_GRF_ROW + 4, Q::sum(gslip));
     }
     if (trajX != nullptr) store_state((g * (size_t)(n_steps + 1) + n_steps) * 36);
     _Pragma("unroll") for (int i = 0; i < 6; i++) { Q::st0(xfinal, g * 36 + i, qb[i]); Q::st0(xfinal, g * 36 + 18 + i, vb[i]); }
@@ -639,6 +694,28 @@ k_sim_quad(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_
 WBS_MC_KERNEL(k_sim_quad_mc, 1)
 WBS_MC_KERNEL(k_sim_quad_mc0, 0)
 #undef WBS_MC_KERNEL
+// The walks with contact-force records (hsddp_grf_set): the same three programs with GRF 1 in the policy; gr points at the thresholds and the
+// destinations in device memory.  The host picks one of the six kernels; with the records off it launches the three above.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))
+k_sim_quad_grf(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU,
+               const WbsGrfArgs* gr) {
+    __shared__ double stash[(SIM_PARK + SIM_GRF_PARK) * 64];
+    const int g = blockIdx.x * 16 + (threadIdx.x >> 2);
+    if (g >= total) return;
+    wbs_walk<QS, WbsGrf>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, WbsGrf{gr});
+}
+#define WBS_MC_GRF_KERNEL(NAME, NOISE)                                                                                                                                         \
+    __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))                                                                               \
+    NAME(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU, \
+         const WbsMcArgs* mc, const WbsGrfArgs* gr) {                                                                                                                          \
+        __shared__ double stash[(SIM_PARK_MC + SIM_GRF_PARK) * 64];                                                                                                            \
+        const int g = blockIdx.x * 16 + (threadIdx.x >> 2);                                                                                                                    \
+        if (g >= total) return;                                                                                                                                                \
+        wbs_walk<QS, WbsMcGrf<NOISE>>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, WbsMcGrf<NOISE>{mc, gr});               \
+    }
+WBS_MC_GRF_KERNEL(k_sim_quad_mc_grf, 1)
+WBS_MC_GRF_KERNEL(k_sim_quad_mc0_grf, 0)
+#undef WBS_MC_GRF_KERNEL
 #endif
 
 }  // namespace hs

@@ -20,6 +20,7 @@
 #include "hsddp_refs.h"
 #include "hsddp_sim.h"
 #include "hsddp_mc.h"
+#include "hsddp_grf.h"
 
 namespace hsddp {
 
@@ -41,6 +42,8 @@ struct SimResult {
     std::vector<double> x_final;            // batch x n_samples x 36
     std::vector<double> X, U;               // keep_traj: batch x n_samples x (n_steps + 1) x 36, batch x n_samples x n_steps x 12
     std::vector<hsddp_mc_extra_t> extra;    // batch x n_samples after a disturbed run (include/hsddp_mc.h), else empty
+    std::vector<hsddp_grf_row_t> grf;       // batch x n_samples after a run with the contact-force records on (include/hsddp_grf.h), else empty
+    std::vector<double> Y;                  // ... and with keep_traj the contact forces, batch x n_samples x n_steps x 12
 };
 inline hsddp_mc_dist_t default_disturbance() { return hsddp_mc_dist_t{}; }      // every switch off
 class Simulation {
@@ -53,13 +56,17 @@ public:
     Simulation(const Simulation&) = delete;
     Simulation& operator=(const Simulation&) = delete;
     // x0: batch x n_samples x 36 (host memory, or device memory with src_device = 1)
-    bool run(const double* x0, int src_device = 0) { rc_ = s_ ? hsddp_sim_run(s_, x0, src_device) : HSDDP_EINVAL; if (rc_ == HSDDP_OK) mc_ = false; return rc_ == HSDDP_OK; }
+    bool run(const double* x0, int src_device = 0) { rc_ = s_ ? hsddp_sim_run(s_, x0, src_device) : HSDDP_EINVAL; if (rc_ == HSDDP_OK) { mc_ = false; grf_run_ = grf_; } return rc_ == HSDDP_OK; }
     // disturbed run: actuator / estimate noise, torque limit, fall height, and a push kick (batch x n_samples x 36, or null) at dist.kick_step
     bool run(const double* x0, const hsddp_mc_dist_t& dist, const double* kick, int src_device = 0, int kick_device = 0) {
         rc_ = s_ ? hsddp_mc_run(s_, x0, src_device, &dist, kick, kick_device) : HSDDP_EINVAL;
-        if (rc_ == HSDDP_OK) mc_ = true;
+        if (rc_ == HSDDP_OK) { mc_ = true; grf_run_ = grf_; }
         return rc_ == HSDDP_OK;
     }
+    // contact-force records for every later run: mu > 0 on with these thresholds, mu == 0 off (include/hsddp_grf.h)
+    bool set_grf(double mu, double fz_min = 0.0) { rc_ = s_ ? hsddp_grf_set(s_, mu, fz_min) : HSDDP_EINVAL; if (rc_ == HSDDP_OK) grf_ = mu > 0.0; return rc_ == HSDDP_OK; }
+    // the records of the last run alone (result() holds them too): rows batch x n_samples, Y batch x n_samples x n_steps x 12 or null
+    bool grf(hsddp_grf_row_t* rows, double* Y = nullptr) { rc_ = s_ ? hsddp_grf_get(s_, 0, batch_, rows, Y) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     SimResult result() {
         SimResult r;
         if (!s_) return r;
@@ -71,13 +78,17 @@ public:
             rc_ = hsddp_sim_get_traj(s_, 0, batch_, r.X.data(), r.U.data());
         }
         if (rc_ == HSDDP_OK && mc_) { r.extra.resize(cnt); rc_ = hsddp_mc_get_extra(s_, 0, batch_, r.extra.data()); }
+        if (rc_ == HSDDP_OK && grf_run_) {
+            r.grf.resize(cnt); if (keep_) r.Y.resize(cnt * (size_t)n_ * 12);
+            rc_ = hsddp_grf_get(s_, 0, batch_, r.grf.data(), keep_ ? r.Y.data() : nullptr);
+        }
         return r;
     }
     const double* device_final() { return s_ ? hsddp_sim_device_final(s_) : nullptr; }      // batch x n_samples x 36 on the device
     int last_error() const { return rc_; }
 private:
     hsddp_sim_t* s_ = nullptr;
-    int batch_, R_, n_, rc_ = 0; bool keep_, mc_ = false;
+    int batch_, R_, n_, rc_ = 0; bool keep_, mc_ = false, grf_ = false, grf_run_ = false;      // grf_run_: the last run was made with the records on
 };
 
 template <typename T = double>

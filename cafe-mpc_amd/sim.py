@@ -10,8 +10,10 @@
     d = Disturbance(seed=7, sigma_u=0.2, sigma_q=1e-3, sigma_v=1e-2, u_max=17.0, fall_height=0.16)      # include/hsddp_mc.h
     res = solver.simulate(x0, n_steps=50, dist=d, kick=kick)      # kick [B, 16, 36] at d.kick_step; res["extra"]["first_fall"], ["n_sat"]
 
+    res = solver.simulate(x0, n_steps=50, keep_traj=True, grf=(0.6, 0.0))      # include/hsddp_grf.h: res["grf"]["min_fz"], ["min_cone"], ["n_slip"], res["Y"]
+
 Nothing here computes anything: the rollout is the k_sim_quad / k_sim_quad_mc kernel (csrc/wb_sim.hpp).  mc_normals states the generator of the
-disturbed runs in numpy: the definition the kernel mirrors."""
+disturbed runs in numpy, grf_rows the contact-force records: the definitions the kernel mirrors."""
 import ctypes as C
 import dataclasses
 
@@ -49,12 +51,40 @@ def mc_normals(seed, problem, r, s):
     return np.sqrt(-2.0 * np.log(1.0 - u[0::2])) * np.cos(2.0 * np.pi * u[1::2])      # 1 - u is in (0, 1]
 
 
+def grf_rows(Y, contact, mu, fz_min, first_bad=None):
+    """The contact-force records of include/hsddp_grf.h from the forces themselves.  Y: [..., n, 12] world-frame contact forces per step (foot l at
+    3 l .. 3 l + 2); contact: [n, 4], foot l is a stance foot of step s iff contact[s, l] > 0; first_bad: None, or an int array of Y's leading shape
+    - where it is >= 0 only the steps s <= first_bad count (the sample was alive when they began).  Over the stance (foot, step) pairs that count:
+    cone = mu fz - max(|fx|, |fy|), a pair violates iff fz < fz_min or cone < 0.  Returns a structured array (GRF_ROW_DTYPE) of Y's leading shape:
+    min_fz, min_cone (+inf without a stance pair), max_fz (-inf), first_slip (-1 without a violation), n_slip."""
+    Y = np.asarray(Y, dtype=np.float64)
+    n = Y.shape[-2]
+    lead = Y.shape[:-2]
+    F = Y.reshape(lead + (n, 4, 3))
+    st = np.broadcast_to(np.asarray(contact).reshape(n, 4) > 0, lead + (n, 4))
+    if first_bad is not None:
+        fb = np.asarray(first_bad).reshape(lead + (1, 1))
+        st = st & ((fb < 0) | (np.arange(n).reshape(n, 1) <= fb))
+    fz = F[..., 2]
+    cone = mu * fz - np.maximum(np.abs(F[..., 0]), np.abs(F[..., 1]))
+    viol = st & ((fz < fz_min) | (cone < 0.0))
+    out = np.zeros(lead, dtype=_abi.GRF_ROW_DTYPE)
+    out["min_fz"] = np.where(st, fz, np.inf).min(axis=(-2, -1), initial=np.inf)
+    out["min_cone"] = np.where(st, cone, np.inf).min(axis=(-2, -1), initial=np.inf)
+    out["max_fz"] = np.where(st, fz, -np.inf).max(axis=(-2, -1), initial=-np.inf)
+    step = viol.any(axis=-1)
+    out["first_slip"] = np.where(step.any(axis=-1), step.argmax(axis=-1), -1) if n else -1
+    out["n_slip"] = viol.sum(axis=(-2, -1))
+    return out
+
+
 class Simulation:
     """One hsddp_sim_t on a Solver's handle.  Stale after Solver.reconfigure (run raises; create a new one).  Close it before the solver."""
 
     def __init__(self, solver, n_samples, n_steps, keep_traj=False):
         self.lib = _abi.bind_sim(solver.lib)      # raises on a library without include/hsddp_sim.h (the CPU checker)
         self.disturbed = False
+        self.grf_on = False
         self.solver, self.R, self.n_steps, self.keep_traj = solver, int(n_samples), int(n_steps), bool(keep_traj)
         self.s = C.c_void_p()
         rc = self.lib.hsddp_sim_create(solver.h, self.R, self.n_steps, 1 if keep_traj else 0, C.byref(self.s))
@@ -114,6 +144,24 @@ class Simulation:
             raise RuntimeError(f"hsddp_mc_get_extra failed rc={rc}")
         return out
 
+    def set_grf(self, mu, fz_min=0.0):
+        """Contact-force records (include/hsddp_grf.h) for every later run: mu > 0 switches them on with these thresholds, mu == 0 off."""
+        rc = _abi.bind_grf(self.lib).hsddp_grf_set(self.s, float(mu), float(fz_min))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_grf_set failed rc={rc}")
+        self.grf_on = mu > 0
+
+    def grf(self, b0=0, nb=None):
+        """Structured array [nb, R] of hsddp_grf_row_t of the last run, which has to be one with the records on; with keep_traj the pair
+        (rows, Y [nb, R, n_steps, 12])."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0), self.R), dtype=_abi.GRF_ROW_DTYPE)
+        Y = np.zeros((max(nb, 0), self.R, self.n_steps, 12)) if self.keep_traj else None
+        rc = _abi.bind_grf(self.lib).hsddp_grf_get(self.s, b0, nb, rows.ctypes.data, Y.ctypes.data if Y is not None else None)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_grf_get failed rc={rc}")
+        return (rows, Y) if self.keep_traj else rows
+
     def rows(self, b0=0, nb=None):
         """(rows [nb, R] as a structured array of hsddp_sim_row_t, x_final [nb, R, 36]) of the last run."""
         nb = self.solver.batch - b0 if nb is None else nb
@@ -144,11 +192,13 @@ class Simulation:
         return float(ms.value)
 
 
-def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None):
+def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None):
     """One-off simulation on `solver`: dict with rows, x_final and, with keep_traj, X and U (see Simulation); a disturbed run (dist / kick given)
-    returns extra too."""
+    returns extra too; grf = (mu, fz_min) adds the contact-force records grf and, with keep_traj, Y."""
     sim = Simulation(solver, x0.shape[1], n_steps, keep_traj)
     try:
+        if grf is not None:
+            sim.set_grf(*grf)
         sim.run(x0, dist=dist, kick=kick)
         rows, xf = sim.rows()
         out = dict(rows=rows, x_final=xf)
@@ -156,6 +206,11 @@ def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None):
             out["extra"] = sim.extra()
         if keep_traj:
             out["X"], out["U"] = sim.traj()
+        if sim.grf_on:
+            if keep_traj:
+                out["grf"], out["Y"] = sim.grf()
+            else:
+                out["grf"] = sim.grf()
         return out
     finally:
         sim.close()
