@@ -63,9 +63,11 @@ template <int NT> __device__ __forceinline__ void hs_phase_sync_all() { hs_phase
 #if !defined(HS_HOST_EMU) && defined(__HIP_DEVICE_COMPILE__)
 #define HS_GLOBAL __attribute__((address_space(1)))
 #define HS_CONST __attribute__((address_space(4)))
+#define HS_LDS __attribute__((address_space(3)))      // a pointer into the workgroup's LDS that is handed around (ds_read, not a flat load)
 #else
 #define HS_GLOBAL
 #define HS_CONST
+#define HS_LDS
 #endif
 // generic pointer that the optimiser knows to point into constant memory (address-space inference follows the double cast)
 #define HS_AS_CONST(T, p) ((const T*)(const HS_CONST T*)(p))

@@ -32,6 +32,7 @@
 #include "hkd_pack.hpp"
 #include "refs.hpp"
 #include "wb_sim.hpp"
+#include "rollout_args.hpp"
 
 using namespace hs;
 
@@ -39,7 +40,6 @@ using namespace hs;
 #define SYNC_COUNTERS() do { HIPCK(hipStreamSynchronize(h->stream)); HIPCK(hipGetLastError()); if (h->h_counters[0] < 0 || h->h_counters[1] < 0 || h->h_counters[2] < 0 || h->h_counters[3] < 0) { fprintf(stderr, "[hsddp_hip] counters not delivered (%s:%d)\n", __FILE__, __LINE__); return HSDDP_ENODEV; } } while (0)
 #define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return HSDDP_ENODEV; } } while (0)
 
-struct SlotArrays { double *cost, *dsq, *ming, *maxh; };
 // device allocations made by this library (hsddp_debug_malloc_count: the MPC-tick test watches it); atomic: hsddp_ensemble_solve runs the
 // candidates' solves on one host thread each, and a first solve allocates its history buffers
 static std::atomic<long long> g_dev_allocs{0};
@@ -60,16 +60,6 @@ static std::atomic<long long> g_dev_allocs{0};
 #define LQ_ATTR __attribute__((amdgpu_waves_per_eu(LQ_WPE, LQ_WPE)))
 
 // ------------------------------------------------------------------------------------------------ kernels
-enum { MASK_NONE = 0, MASK_LS = 1, MASK_INNER = 2, MASK_OUTER = 3, MASK_LS_OK = 4, MASK_COMMIT = 5 };
-__device__ inline bool masked_out(const ProbState& s, int mask) {
-    if (mask == MASK_LS) return !s.ls_active;
-    if (mask == MASK_INNER) return !s.inner_active;
-    if (mask == MASK_OUTER) return !s.outer_active;
-    if (mask == MASK_LS_OK) return !s.ls_success;
-    if (mask == MASK_COMMIT) return !s.need_commit;
-    return false;
-}
-
 // Single shooting from phase `first` on, by ONE wave: every knot takes the state its predecessor simulated (SinglePhase.cpp:187,211-220).
 // Used for the young phases the receding-horizon update creates (SS_set empty, MHPCProblem.cpp:340-351; first > 0, stops at the next
 // phase with shooting nodes) and for the whole horizon when option.MS is false (MultiPhaseDDP.cpp:65-68; first = 0, descriptors with
@@ -95,13 +85,8 @@ template <bool WBM, class LDS> __device__ __forceinline__ void rollout_chain(LDS
     }
 }
 
-// Step lengths of one launch.  Ordinary launches carry one (eps[0], or the problem's own ls_eps when from_state is set: the commit of a
-// batched line search); a PROBE launch carries the candidates eps[0..n-1] of MultiPhaseDDP::line_search (MultiPhaseDDP.cpp:95-133) that
-// are still to be tried: grid = candidates x problems x slots, candidate c only leaves the per-slot partials of its merit function in
-// slice c of the slot arrays - except candidate `writer` (the last of the search), which also writes the trajectories like an ordinary trial.
-constexpr int MAXCAND = 12;
-struct EpsList { double e[MAXCAND]; int n, writer, from_state; };
-// Probe launches: grid = candidates x units.  Workgroups go round-robin over the 8 XCDs (one L2 each); the candidates of a unit read the same
+// Probe launches of the ONE-WAVE kernels (k_rollout, k_rollout_hkd; the quad kernel loops over the candidates inside a unit's wave instead):
+// grid = candidates x units.  Workgroups go round-robin over the 8 XCDs (one L2 each); the candidates of a unit read the same
 // trajectories and differ in eps only.  Unit u lives on XCD u % 8 and its candidates occupy consecutive dispatch slots of that XCD, so one of them
 // brings the lines into that L2 and the others find them there (candidate-major order streamed the whole ensemble from HBM once per candidate:
 // probe launch of the quad kernel 11.4 -> 9.8 ms).  QUAD_CAND_MAJOR 1 = the old order.
@@ -183,39 +168,12 @@ __global__ void __launch_bounds__(64) ROLL_ATTR k_rollout(ROLL_ARGS) { __shared_
 #endif
 __global__ void __launch_bounds__(64) ROLL_HKD_ATTR k_rollout_hkd(ROLL_ARGS) { __shared__ RedLds L; rollout_body<false>(L, ROLL_PASS); }
 
-// The whole-body running knots of the phases with shooting nodes on LANE QUADS (wb_quad.hpp): one lane per leg, sixteen problems of the same
-// (candidate, knot) per wave.  grid = candidates x knots of the list x ceil(batch / 16); qslots: the slots this kernel owns.
-#ifndef QUAD_WPE
-#define QUAD_WPE 1      // waves per SIMD the quad kernel is compiled for (1: up to 512 registers, nothing in scratch; 2: 256 registers)
+// The whole-body running knots of the phases with shooting nodes run on lane quads: k_rollout_quad, hsddp_quad.hip.  The Makefile compiles that
+// file as a translation unit of its own (-DHS_QUAD_SEPARATE here) because it wants one more compiler switch than the rest of the library; any
+// other build - one hipcc command over this file - takes it in here and is the same library, the quad kernel with about 90 B of scratch per lane.
+#ifndef HS_QUAD_SEPARATE
+#include "hsddp_quad.hip"
 #endif
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QUAD_WPE, QUAD_WPE)))
-k_rollout_quad(const PhaseDev* ph_, const int* slot_phase, const int* slot_k, const int* qslots, int nq, int nslots, int batch, ModelDev md, EpsList el, OptDev opt, const double* x0,
-               SlotArrays sa, const ProbState* st, int mask, int* fail, unsigned long long* units, const int* plist, int nlist) {
-    PhaseC* ph = (PhaseC*)ph_;
-    // plist / nlist: the problems this launch is for (null: all of the batch, `mask` picks).  A probe launch of a line search or a commit launch only
-    // concerns some problems; packed sixteen to a wave from the list the deciding kernel left behind, its waves are full whatever the share is
-    const int nprob = plist != nullptr ? nlist : batch;
-    const int nbg = (nprob + 15) >> 4;
-    const int per = nq * nbg;
-    int c, r; cand_unit(per, blockIdx.x, c, r);
-    const int qi = r / nbg, bg = r - qi * nbg;
-    const int s = qslots[qi], pi = slot_phase[s], k = slot_k[s];
-    const int ix = bg * 16 + (threadIdx.x >> 2);
-    const int b = ix < nprob ? (plist != nullptr ? plist[ix] : ix) : batch;
-    const bool active = b < batch && !masked_out(st[b < batch ? b : 0], mask);
-    {   // knots this launch rolls out (measurement only): one atomic per wave
-        const unsigned long long m = __ballot(active && (threadIdx.x & 3) == 0);
-        if (threadIdx.x == 0 && m != 0) atomicAdd(units, (unsigned long long)__popcll(m));
-    }
-    if (!active) return;      // (a quad leaves or stays as a whole: the cross-lane steps below need all four lanes)
-    const double eps = el.from_state ? st[b].ls_eps : el.e[c];
-    const QuadOut q = wbq_rollout_knot<QD>(ph[pi], md, b, k, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, c == el.writer);
-    if ((threadIdx.x & 3) == 0) {
-        const size_t slot = ((size_t)c * batch + b) * nslots + s;
-        sa.cost[slot] = q.cost; sa.dsq[slot] = q.dsq; sa.ming[slot] = q.ming; sa.maxh[slot] = 0.0;
-        if (q.bad) fail[(size_t)c * batch + b] = 1;
-    }
-}
 
 // Batched line search, decision step (MultiPhaseDDP::line_search, MultiPhaseDDP.cpp:108-131, for the candidates of one probe launch): per
 // problem the candidates are examined IN ORDER - reduction of the slice's partials, merit, Armijo test - exactly as if they had been
@@ -959,8 +917,8 @@ static void launch_rollout_list(hsddp_handle* h, const EpsList& el, const SlotAr
     hipMemsetAsync(h->d_fail, 0, (size_t)h->batch * el.n * sizeof(int), h->stream);
     if (h->quad && o.MS && h->nq > 0) {      // whole-body running knots on lane quads, the rest (terminal knots, single-rigid-body tail) on the one-wave programs
         const int nbg = ((plist ? nlist : h->batch) + 15) / 16;
-        hipLaunchKernelGGL(k_rollout_quad, dim3((unsigned)((size_t)el.n * h->nq * nbg)), dim3(64), 0, h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
-                           h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist);
+        launch_k_rollout_quad((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
+                              h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist);
         if (h->n_other > 0)
             hipLaunchKernelGGL(k_rollout, dim3((unsigned)((size_t)el.n * h->batch * h->n_other)), dim3(64), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
                                h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots);
@@ -1300,13 +1258,6 @@ int hsddp_get_kernel_times(hsddp_handle_t* h, int max_n, double* ms, long long* 
 int hsddp_debug_lq_prof(unsigned long long* out16, int reset) {
     hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_lq_prof), 16 * sizeof(unsigned long long));
     if (reset) { unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_lq_prof), z, sizeof(z)); }
-    return 0;
-}
-#endif
-#ifdef QUAD_PROF
-int hsddp_debug_quad_prof(unsigned long long* out24, int reset) {
-    hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_quad_prof), 24 * sizeof(unsigned long long));
-    if (reset) { unsigned long long z[24] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_quad_prof), z, sizeof(z)); }
     return 0;
 }
 #endif

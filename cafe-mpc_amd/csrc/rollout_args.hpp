@@ -1,0 +1,28 @@
+// What the rollout kernels of hsddp_hip.hip and the lane-quad rollout kernel share.  The quad kernel is a translation unit of its own
+// (hsddp_quad.hip) because it is compiled with one more switch than the rest of the library (Makefile).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "hs_types.hpp"
+
+struct SlotArrays { double *cost, *dsq, *ming, *maxh; };
+enum { MASK_NONE = 0, MASK_LS = 1, MASK_INNER = 2, MASK_OUTER = 3, MASK_LS_OK = 4, MASK_COMMIT = 5 };
+__device__ inline bool masked_out(const hs::ProbState& s, int mask) {
+    if (mask == MASK_LS) return !s.ls_active;
+    if (mask == MASK_INNER) return !s.inner_active;
+    if (mask == MASK_OUTER) return !s.outer_active;
+    if (mask == MASK_LS_OK) return !s.ls_success;
+    if (mask == MASK_COMMIT) return !s.need_commit;
+    return false;
+}
+
+// Step lengths of one launch.  Ordinary launches carry one (eps[0], or the problem's own ls_eps when from_state is set: the commit of a
+// batched line search); a PROBE launch carries the candidates eps[0..n-1] of MultiPhaseDDP::line_search (MultiPhaseDDP.cpp:95-133) that
+// are still to be tried (one-wave kernels: grid = candidates x problems x slots; quad kernel: a loop in each unit's wave), candidate c only leaves the per-slot partials of its merit function in
+// slice c of the slot arrays - except candidate `writer` (the last of the search), which also writes the trajectories like an ordinary trial.
+constexpr int MAXCAND = 12;
+struct EpsList { double e[MAXCAND]; int n, writer, from_state; };
+
+// k_rollout_quad (hsddp_quad.hip): grid = one workgroup per unit (knot of the quad list x group of sixteen problems)
+void launch_k_rollout_quad(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, const int* slot_phase, const int* slot_k, const int* qslots, int nq, int nslots, int batch,
+                           hs::ModelDev md, EpsList el, hs::OptDev opt, const double* x0, SlotArrays sa, const hs::ProbState* st, int mask, int* fail, unsigned long long* units,
+                           const int* plist, int nlist);

@@ -17,7 +17,8 @@
 //     from one Newton-Euler pass per leg, the foot Jacobians from the geometric (axis x arm) form - no unit-acceleration passes;
 //   * the contact solve is the block form of the one in wb_knot.hpp (M = L L^T legs first, X = L^-1 Jc^T, G = X^T X + 1e-12 I,
 //     lam = G^-1 (-X^T y - gam), qdd = L^-T (y + X lam)): the same factorisation, so the same numbers up to summation order.
-// No LDS, no barrier.  Everything is a template over the scalar S: `double` on the GPU (cross-lane steps = DPP quad_perm), a
+// The knot program itself uses no LDS and no barrier; where its step-independent inputs are read from is the caller's choice (QuadIn below).
+// Everything is a template over the scalar S: `double` on the GPU (cross-lane steps = DPP quad_perm), a
 // four-wide value on the host (tests/_emu: the four lanes of a quad evaluated together), so the kernel logic is checked against the
 // oracle in a container that has no GPU.
 #pragma once
@@ -89,6 +90,19 @@ struct QD {      // GPU: S = one lane's double; the quad's other lanes are reach
     static HD bool any(B m) { return __any(m) != 0; }      // over the WAVE (uniform): only ever used to skip work no lane needs
     static HD B lnot(B m) { return !m; }
     static HD double lane0(S x) { return x; }
+};
+// QD for a wave that evaluates SEVERAL knots in a loop (k_rollout_quad: the candidates of a probe launch).  Everything that depends on the lane
+// alone - the leg selects of legc, the per-leg offsets of ld / st - is invariant in such a loop, and the compiler hoists all of it (some sixty
+// doubles of link constants, masks and offsets) out of the loop and carries it through the knot's register peak: 220 B of scratch per lane.
+// Here the lane's leg comes out of LDS (the kernel fills lane_slot() once): one ds_read per trip that cannot move out of a loop whose trips
+// begin with a memory barrier, so each trip forms its lane constants where it uses them, as the straight-line kernel does.
+struct QDL : QD {
+    static HD HS_LDS int* lane_slot() { __shared__ int leg[64]; return (HS_LDS int*)leg; }
+    static HD int lane() { return lane_slot()[threadIdx.x]; }
+    static HD S legc(double a, double b, double c, double d) { const int l = lane(); return l == 0 ? a : l == 1 ? b : l == 2 ? c : d; }
+    template <class PT> static HD S ld(PT p, size_t off, int stride) { return p[off + (size_t)(lane() * stride)]; }
+    template <class PT> static HD void st(PT p, size_t off, int stride, S x) { p[off + (size_t)(lane() * stride)] = x; }
+    template <class PT> static HD void st0(PT p, size_t off, S x) { if (lane() == 0) p[off] = x; }
 };
 #endif
 
@@ -202,7 +216,7 @@ template <class Q, class S> HD S q_barrier(const S& g, const S& delta) {
 struct QuadOut { double cost, dsq, ming; bool bad; };
 // diagnostic stamps (-DQUAD_PROF, tools/microbench.py): cycles of one wave from the middle of a launch between consecutive marks
 #if defined(QUAD_PROF) && !defined(HS_HOST_EMU)
-__device__ unsigned long long g_quad_prof[24];
+static __device__ unsigned long long g_quad_prof[24];      // (read by hsddp_debug_quad_prof of the translation unit that holds the kernel)
 #define QP0() unsigned long long qp_t_ = 0; const bool qp_on_ = (blockIdx.x == HS_QUAD_PROF_BLOCK && threadIdx.x == 0); if (qp_on_) qp_t_ = clock64();
 #define QP(i) if (qp_on_) { const unsigned long long t_ = clock64(); atomicAdd(&g_quad_prof[i], t_ - qp_t_); qp_t_ = t_; }
 #ifndef HS_QUAD_PROF_BLOCK
@@ -214,12 +228,20 @@ __device__ unsigned long long g_quad_prof[24];
 #endif
 template <int I> struct IC { static constexpr int value = I; };
 
+// The step-independent inputs of a knot - everything the rollout reads that is the same for every step length - as rows indexed from 0:
+//   xbar, dx: the states of knots k and k + 1 (72 values; row h of the phase behind its last running knot);  ubar, du, kdx: 12 values each;
+//   rr: the knot's row of the packed references (80).
+// The eight-argument form of wbq_rollout_knot points them into the phase's arrays (tests/_emu, one evaluation per knot); k_rollout_quad copies
+// the rows of a wave's sixteen problems into LDS once and evaluates every candidate of the launch from there (PT = an LDS pointer).
+template <class PT> struct QuadIn { PT xbar, dx, ubar, du, kdx, rr; };
+
 // One whole-body rollout knot k < h of problem b of a phase WITH shooting nodes, step length eps, evaluated by a lane quad.
 //   wr = false: a probe - only (cost, defect^2, min g, divergence) come back;  wr = true additionally stores everything wb_rollout_knot
 //   stores: X, U, Y, Xsim, Defect, g, lbase, l and the contact-solve cache of the knot in the layout the LQ knot fetches (hs_types.hpp KC_*).
 //   wr must be uniform over the wave.
-template <class Q>
-HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr) {
+//   in: the rows of the knot's step-independent inputs (QuadIn).
+template <class Q, class PT>
+HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr, const QuadIn<PT>& in) {
     using S = typename Q::S;
     const bool WR = wr;
     const int h = P.h;
@@ -227,10 +249,10 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     QP0()
     // ---- state of the knot: the floating base replicated in every lane, the lane's own leg
     S qb[6], vb[6], ql[3], vl_[3], ul[3];
-    _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::ld(P.Xbar, kx + i, 0) + eps * Q::ld(P.dX, kx + i, 0); vb[i] = Q::ld(P.Xbar, kx + 18 + i, 0) + eps * Q::ld(P.dX, kx + 18 + i, 0); }
+    _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::ld(in.xbar, i, 0) + eps * Q::ld(in.dx, i, 0); vb[i] = Q::ld(in.xbar, 18 + i, 0) + eps * Q::ld(in.dx, 18 + i, 0); }
     _Pragma("unroll") for (int j = 0; j < 3; j++) {
-        ql[j] = Q::ld(P.Xbar, kx + 6 + j, 3) + eps * Q::ld(P.dX, kx + 6 + j, 3); vl_[j] = Q::ld(P.Xbar, kx + 24 + j, 3) + eps * Q::ld(P.dX, kx + 24 + j, 3);
-        ul[j] = Q::ld(P.Ubar, ku + j, 3) + eps * (Q::ld(P.dU, ku + j, 3) + Q::ld(P.KdX, ku + j, 3));      // u = ubar + eps (dU + K dX), wb_knot.hpp / DESIGN section 4
+        ql[j] = Q::ld(in.xbar, 6 + j, 3) + eps * Q::ld(in.dx, 6 + j, 3); vl_[j] = Q::ld(in.xbar, 24 + j, 3) + eps * Q::ld(in.dx, 24 + j, 3);
+        ul[j] = Q::ld(in.ubar, j, 3) + eps * (Q::ld(in.du, j, 3) + Q::ld(in.kdx, j, 3));      // u = ubar + eps (dU + K dX), wb_knot.hpp / DESIGN section 4
     }
     if (WR) {
         _Pragma("unroll") for (int j = 0; j < 3; j++) {
@@ -242,7 +264,7 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     // references and barrier parameters fetched with the state (one exposed round trip for all of them) and dead before the contact solve's
     // register peak; what needs the dynamics (defect, foot costs, friction pyramid) reads later, ahead of the contact solve (see below).
     const double dt = P.dt;
-    const HS_GLOBAL double* rr = P.rref + ref_row(P, b, k) * 80;
+    const PT rr = in.rr;
     const size_t gk = kk * P.ng;
     const S zero = S(0.0);
     const S w0 = Q::legc(1.0, 0.0, 0.0, 0.0);      // the replicated base entries are counted once
@@ -482,8 +504,8 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     // are issued HERE: their round trip runs under the contact solve instead of being exposed at the end
     S xnb[6], vnb[6], xnl[3], vnl[3];
     auto read_next = [&]() {
-        _Pragma("unroll") for (int i = 0; i < 6; i++) { xnb[i] = Q::ld(P.Xbar, kx + 36 + i, 0) + eps * Q::ld(P.dX, kx + 36 + i, 0); vnb[i] = Q::ld(P.Xbar, kx + 54 + i, 0) + eps * Q::ld(P.dX, kx + 54 + i, 0); }
-        _Pragma("unroll") for (int j = 0; j < 3; j++) { xnl[j] = Q::ld(P.Xbar, kx + 42 + j, 3) + eps * Q::ld(P.dX, kx + 42 + j, 3); vnl[j] = Q::ld(P.Xbar, kx + 60 + j, 3) + eps * Q::ld(P.dX, kx + 60 + j, 3); }
+        _Pragma("unroll") for (int i = 0; i < 6; i++) { xnb[i] = Q::ld(in.xbar, 36 + i, 0) + eps * Q::ld(in.dx, 36 + i, 0); vnb[i] = Q::ld(in.xbar, 54 + i, 0) + eps * Q::ld(in.dx, 54 + i, 0); }
+        _Pragma("unroll") for (int j = 0; j < 3; j++) { xnl[j] = Q::ld(in.xbar, 42 + j, 3) + eps * Q::ld(in.dx, 42 + j, 3); vnl[j] = Q::ld(in.xbar, 60 + j, 3) + eps * Q::ld(in.dx, 60 + j, 3); }
     };
 #ifdef QUAD_NEXT_EARLY      // (measured: the 18 values held through the factorisation cost 24 spilled registers)
     read_next();
@@ -757,6 +779,12 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     const double ns = Q::lane0(nsq);
     o.bad = (ns > 1e12) || !(ns == ns);      // ||Xsim|| > 1e6 (SinglePhase.cpp:205)
     return o;
+}
+template <class Q>
+HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr) {
+    const size_t kx = ((size_t)b * (P.h + 1) + k) * 36, ku = ((size_t)b * P.h + k) * 12;
+    const QuadIn<const HS_GLOBAL double*> in = {P.Xbar + kx, P.dX + kx, P.Ubar + ku, P.dU + ku, P.KdX + ku, P.rref + ref_row(P, b, k) * 80};
+    return wbq_rollout_knot<Q>(P, md, b, k, eps, reb_active, x0, wr, in);
 }
 
 }  // namespace hs
