@@ -17,6 +17,8 @@ from .ensemble import ScheduleEnsemble, select_rows  # noqa: F401
 from . import hkd_command  # noqa: F401
 from . import sim  # noqa: F401
 from .sim import Simulation  # noqa: F401
+from . import episode  # noqa: F401
+from .episode import Episode  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
 HIP_LIB_PATH = _os.path.join(_HERE, "libhsddp_hip.so")

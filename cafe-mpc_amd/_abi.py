@@ -283,6 +283,43 @@ def bind_grf(lib):
     return lib
 
 
+# include/hsddp_episode.h: batched closed-loop MPC episodes (libhsddp_hip.so only)
+EPISODE_EXPORTS = ["hsddp_episode_create", "hsddp_episode_destroy", "hsddp_episode_reset", "hsddp_episode_advance", "hsddp_episode_get_rows",
+                   "hsddp_episode_get_log", "hsddp_episode_device_state", "hsddp_episode_sim", "hsddp_episode_status"]
+
+
+class EpisodeRow(C.Structure):
+    """hsddp_episode_row_t"""
+    _fields_ = [(n, C.c_double) for n in ("dev_q", "dev_v", "min_height", "max_torque", "min_fz", "min_cone", "max_fz", "track_cost")] + \
+               [(n, C.c_int) for n in ("n_sat", "n_slip", "first_slip", "steps", "bad_solves", "end_reason", "end_step", "pad")]
+
+
+EPISODE_ROW_DTYPE = np.dtype([(n, "<f8" if t is C.c_double else "<i4") for n, t in EpisodeRow._fields_])
+
+
+def bind_episode(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_episode.h (and of the simulation headers it builds on).  Raises if the library
+    lacks any."""
+    missing = [s for s in EPISODE_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the episode entry points {missing}")
+    bind_mc(lib); bind_grf(lib)
+    H = C.c_void_p
+    lib.hsddp_episode_create.argtypes = [H, C.c_int, C.c_int, C.c_int, C.POINTER(H)]
+    lib.hsddp_episode_destroy.argtypes = [H]
+    lib.hsddp_episode_destroy.restype = None
+    lib.hsddp_episode_reset.argtypes = [H, C.c_void_p, C.c_int]
+    lib.hsddp_episode_advance.argtypes = [H, C.POINTER(McDist), C.c_void_p, C.c_int]
+    lib.hsddp_episode_get_rows.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.hsddp_episode_get_log.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hsddp_episode_device_state.argtypes = [H]
+    lib.hsddp_episode_device_state.restype = C.c_void_p
+    lib.hsddp_episode_sim.argtypes = [H]
+    lib.hsddp_episode_sim.restype = C.c_void_p
+    lib.hsddp_episode_status.argtypes = [H, IP, IP, IP]
+    return lib
+
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -548,6 +585,12 @@ class Solver:
         [batch, R, n_steps, 12]."""
         from . import sim
         return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf)
+
+    def episode(self, n_exec, max_ticks, keep_log=False):
+        """An episode.Episode on this solver (include/hsddp_episode.h): batched closed-loop MPC ticks with the simulated state handed to the next
+        solve on the device.  Close it before the solver."""
+        from . import episode
+        return episode.Episode(self, n_exec, max_ticks, keep_log)
 
     def get_history(self, problem=0, cap=4096):
         """MultiPhaseDDP::get_solver_info(cost, dyn_feas, eqn_feas, ineq_feas) (MultiPhaseDDP.h:85): the four float history buffers."""

@@ -21,6 +21,7 @@
 #include "hsddp_sim.h"
 #include "hsddp_grf.h"
 #include "hsddp_mc.h"
+#include "hsddp_episode.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -32,6 +33,7 @@
 #include "hkd_pack.hpp"
 #include "refs.hpp"
 #include "wb_sim.hpp"
+#include "episode.hpp"
 #include "rollout_args.hpp"
 
 using namespace hs;
@@ -1668,23 +1670,37 @@ static void sim_free(hsddp_sim* s) {
     delete s;
 }
 static bool sim_range_ok(const hsddp_sim* s, int b0, int nb) { return s && nb > 0 && b0 >= 0 && b0 <= s->h->batch - nb; }
+// step -> (phase, knot) over the leading whole-body control knots of the handle's CURRENT window, as hsddp_export_mpc_command walks them; the reset
+// map of a phase is applied behind its last knot when the window goes on.  map: 3 n_steps ints.  False if the window holds fewer such knots.
+// pending (optional): the phase whose reset map lies behind the LAST step - the one no run applies (hsddp_episode.h) - or -1.
+static bool sim_step_map(const hsddp_handle* h, int n_steps, int* map, int* pending = nullptr) {
+    int n = 0, pend = -1;
+    for (int i = 0; i < h->nph && n < n_steps; i++) {
+        if (h->ph[i].model != HSDDP_MODEL_WB) break;
+        for (int k = 0; k < h->ph[i].h && n < n_steps; k++, n++) {
+            map[n] = i; map[n_steps + n] = k;
+            const bool td = k == h->ph[i].h - 1 && h->ph[i].has_impact;
+            map[2 * (size_t)n_steps + n] = (td && n + 1 < n_steps) ? 1 : 0;
+            if (td && n + 1 == n_steps) pend = i;
+        }
+    }
+    if (pending) *pending = pend;
+    return n == n_steps;
+}
+// the switches hsddp_mc_run accepts on object s
+static bool mc_dist_ok(const hsddp_sim* s, const hsddp_mc_dist_t* d, const double* kick) {
+    auto sigma_ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    if (!sigma_ok(d->sigma_u) || !sigma_ok(d->sigma_q) || !sigma_ok(d->sigma_v) || !std::isfinite(d->u_max) || !std::isfinite(d->fall_height) || d->first_problem < 0) return false;
+    if (kick && (d->kick_step < 0 || d->kick_step >= s->n_steps)) return false;
+    return s->n_steps <= 65536 && s->R <= 65536;      // the generator numbers samples and steps in 16 bits each
+}
 
 extern "C" {
 
 int hsddp_sim_create(hsddp_handle_t* h, int n_samples, int n_steps, int keep_traj, hsddp_sim_t** out) {
     if (!h || !out || n_samples <= 0 || n_steps <= 0) return HSDDP_EINVAL;
-    // step -> (phase, knot) over the leading whole-body control knots, as hsddp_export_mpc_command walks them; the reset map of a phase is applied
-    // behind its last knot when the window goes on
     std::vector<int> map(3 * (size_t)n_steps, 0);
-    int n = 0;
-    for (int i = 0; i < h->nph && n < n_steps; i++) {
-        if (h->ph[i].model != HSDDP_MODEL_WB) break;
-        for (int k = 0; k < h->ph[i].h && n < n_steps; k++, n++) {
-            map[n] = i; map[n_steps + n] = k;
-            map[2 * (size_t)n_steps + n] = (k == h->ph[i].h - 1 && n + 1 < n_steps && h->ph[i].has_impact) ? 1 : 0;
-        }
-    }
-    if (n < n_steps) return HSDDP_EINVAL;
+    if (!sim_step_map(h, n_steps, map.data())) return HSDDP_EINVAL;
     const size_t total = (size_t)h->batch * n_samples;
     if (total >= ((size_t)1 << 31)) return HSDDP_ENOTSUP;      // quads are indexed in 32 bits
     HIPCK(hipSetDevice(h->device));
@@ -1748,10 +1764,7 @@ int hsddp_mc_run(hsddp_sim_t* s, const double* x0, int x0_device, const hsddp_mc
     if (!s || !x0 || !d) return HSDDP_EINVAL;
     hsddp_handle* h = s->h;
     if (s->gen != h->window_gen) return HSDDP_EINVAL;
-    auto sigma_ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
-    if (!sigma_ok(d->sigma_u) || !sigma_ok(d->sigma_q) || !sigma_ok(d->sigma_v) || !std::isfinite(d->u_max) || !std::isfinite(d->fall_height) || d->first_problem < 0) return HSDDP_EINVAL;
-    if (kick && (d->kick_step < 0 || d->kick_step >= s->n_steps)) return HSDDP_EINVAL;
-    if (s->n_steps > 65536 || s->R > 65536) return HSDDP_EINVAL;      // the generator numbers samples and steps in 16 bits each
+    if (!mc_dist_ok(s, d, kick)) return HSDDP_EINVAL;
     HIPCK(hipSetDevice(h->device));
     if (!kick && d->sigma_u == 0.0 && d->sigma_q == 0.0 && d->sigma_v == 0.0 && d->u_max <= 0.0 && d->fall_height <= 0.0) {      // nothing switched on: the plain kernel
         const int rc = sim_launch(s, x0, x0_device, false);
@@ -1850,6 +1863,165 @@ int hsddp_sim_get_kernel_time_ms(hsddp_sim_t* s, float* ms) {
     if (!s || !ms || !s->timed) return HSDDP_EINVAL;
     HIPCK(hipSetDevice(s->h->device));
     HIPCK(hipEventElapsedTime(ms, s->ev0, s->ev1));
+    return HSDDP_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ MPC episodes (hsddp_episode.h)
+}  // extern "C"
+static_assert(sizeof(hsddp_episode_row_t) == sizeof(EpiRow), "the device row is hsddp_episode_row_t");
+struct hsddp_episode {
+    hsddp_handle* h = nullptr;
+    hsddp_sim* sim = nullptr;                               // one sample per problem, n_exec steps, trajectories kept
+    int n_exec = 0, max_ticks = 0, keep = 0, tick = 0, n_impacts = 0;
+    bool started = false;                                   // hsddp_episode_reset has given the states
+    int pending = -1;                                       // phase of the bound window whose reset map lies behind the tick's last step, else -1
+    std::vector<int> map, map_new;                          // host copies of the step map: the bound one (source of the upload) / scratch of a rebind
+    std::vector<EpiRow> row0;                               // [B] rows of a reset (source of the upload)
+    double* d_state = nullptr; EpiRow* d_rows = nullptr;    // [B][36] ; [B]
+    double *d_X = nullptr, *d_U = nullptr, *d_Y = nullptr;  // the log (keep): [B][max_ticks n_exec + 1][36], [B][max_ticks n_exec][12] twice
+};
+static void episode_free(hsddp_episode* e) {
+    if (!e) return;
+    hipSetDevice(e->h->device);
+    if (e->h->stream) hipStreamSynchronize(e->h->stream);
+    if (e->sim) sim_free(e->sim);
+    void* p[] = {e->d_state, e->d_rows, e->d_X, e->d_U, e->d_Y};
+    for (void* q : p) if (q) hipFree(q);
+    delete e;
+}
+static bool episode_range_ok(const hsddp_episode* e, int b0, int nb) { return e && nb > 0 && b0 >= 0 && b0 <= e->h->batch - nb; }
+// seed of tick t (hsddp_episode.h): the seed itself, then the raw outputs of SplitMix64(seed)
+static unsigned long long episode_tick_seed(unsigned long long seed, int t) {
+    if (t == 0) return seed;
+    unsigned long long z = seed + (unsigned long long)t * WBS_MC_G;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+extern "C" {
+
+int hsddp_episode_create(hsddp_handle_t* h, int n_exec, int max_ticks, int keep_log, hsddp_episode_t** out) {
+    if (!h || !out || n_exec <= 0 || max_ticks <= 0 || h->f32) return HSDDP_EINVAL;
+    const size_t B = h->batch, steps = (size_t)max_ticks * n_exec;
+    if (steps >= ((size_t)1 << 31)) return HSDDP_ENOTSUP;      // global step indices are ints
+    hsddp_sim* s = nullptr;
+    int rc = hsddp_sim_create(h, 1, n_exec, 1, &s);
+    if (rc != HSDDP_OK) return rc;
+    hsddp_episode* e = new hsddp_episode();
+    e->h = h; e->sim = s; e->n_exec = n_exec; e->max_ticks = max_ticks; e->keep = keep_log ? 1 : 0;
+    e->map.assign(3 * (size_t)n_exec, 0); e->map_new.assign(3 * (size_t)n_exec, 0);
+    sim_step_map(h, n_exec, e->map.data(), &e->pending);
+    EpiRow r0{};
+    r0.min_height = HUGE_VAL; r0.min_fz = HUGE_VAL; r0.min_cone = HUGE_VAL; r0.max_fz = -HUGE_VAL; r0.first_slip = -1; r0.end_step = -1;
+    e->row0.assign(B, r0);
+#define EPI_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); episode_free(e); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
+    EPI_CK(hipMalloc((void**)&e->d_state, B * 36 * 8));
+    EPI_CK(hipMalloc((void**)&e->d_rows, B * sizeof(EpiRow)));
+    if (e->keep) {
+        EPI_CK(hipMalloc((void**)&e->d_X, B * (steps + 1) * 36 * 8)); EPI_CK(hipMalloc((void**)&e->d_U, B * steps * 12 * 8)); EPI_CK(hipMalloc((void**)&e->d_Y, B * steps * 12 * 8));
+        EPI_CK(hipMemset(e->d_X, 0, B * (steps + 1) * 36 * 8)); EPI_CK(hipMemset(e->d_U, 0, B * steps * 12 * 8)); EPI_CK(hipMemset(e->d_Y, 0, B * steps * 12 * 8));
+    }
+    EPI_CK(hipMemset(e->d_state, 0, B * 36 * 8));
+    EPI_CK(hipMemcpy(e->d_rows, e->row0.data(), B * sizeof(EpiRow), hipMemcpyHostToDevice));
+#undef EPI_CK
+    *out = e; return HSDDP_OK;
+}
+
+void hsddp_episode_destroy(hsddp_episode_t* e) { episode_free(e); }
+
+int hsddp_episode_reset(hsddp_episode_t* e, const double* x0, int src_device) {
+    if (!e || !x0) return HSDDP_EINVAL;
+    hsddp_handle* h = e->h;
+    const size_t B = h->batch, steps = (size_t)e->max_ticks * e->n_exec;
+    HIPCK(hipSetDevice(h->device));
+    HIPCK(hipMemcpyAsync(e->d_state, x0, B * 36 * 8, src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipMemcpyAsync(h->d_x0, e->d_state, B * 36 * 8, hipMemcpyDeviceToDevice, h->stream));      // what hsddp_set_initial_condition leaves
+    HIPCK(hipMemcpyAsync(e->d_rows, e->row0.data(), B * sizeof(EpiRow), hipMemcpyHostToDevice, h->stream));
+    if (e->keep) {
+        HIPCK(hipMemsetAsync(e->d_X, 0, B * (steps + 1) * 36 * 8, h->stream)); HIPCK(hipMemsetAsync(e->d_U, 0, B * steps * 12 * 8, h->stream));
+        HIPCK(hipMemsetAsync(e->d_Y, 0, B * steps * 12 * 8, h->stream));
+    }
+    HIPCK(hipStreamSynchronize(h->stream));
+    e->tick = 0; e->n_impacts = 0; e->started = true;
+    return HSDDP_OK;
+}
+
+int hsddp_episode_advance(hsddp_episode_t* e, const hsddp_mc_dist_t* dist, const double* kick, int kick_device) {
+    if (!e || !e->started || e->tick >= e->max_ticks) return HSDDP_EINVAL;
+    hsddp_handle* h = e->h; hsddp_sim* s = e->sim;
+    if (kick && !dist) return HSDDP_EINVAL;                       // (the step of the push is the disturbance's)
+    if (dist && !mc_dist_ok(s, dist, kick)) return HSDDP_EINVAL;
+    const bool moved = s->gen != h->window_gen;
+    int pend = e->pending;
+    if (moved && !sim_step_map(h, e->n_exec, e->map_new.data(), &pend)) return HSDDP_EINVAL;      // the window no longer leads with n_exec whole-body knots
+    HIPCK(hipSetDevice(h->device));
+    // rebind: the step map of the new window into the simulation object's buffer (the walk below synchronises the stream).  It stays in place if the
+    // walk then fails with a device error - the map is that of the handle's current window either way; "nothing changed" is promised for HSDDP_EINVAL
+    if (moved) {
+        e->map.swap(e->map_new); e->pending = pend;
+        HIPCK(hipMemcpyAsync(s->d_map, e->map.data(), e->map.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        s->gen = h->window_gen;
+    }
+    int rc;
+    if (!dist) rc = hsddp_sim_run(s, e->d_state, 1);
+    else {
+        hsddp_mc_dist_t d = *dist; d.seed = episode_tick_seed(dist->seed, e->tick);
+        rc = hsddp_mc_run(s, e->d_state, 1, &d, kick, kick_device);
+    }
+    if (rc != HSDDP_OK) return rc;
+    EpiCommitArgs a;
+    a.n_exec = e->n_exec; a.tick = e->tick; a.max_ticks = e->max_ticks; a.handoff = e->pending < 0 ? 1 : 0;
+    a.map = s->d_map; a.simX = s->d_X; a.simU = s->d_U; a.simY = s->last_grf ? s->d_Y : nullptr;
+    a.fin = s->d_final; a.sim_rows = s->d_rows; a.extra = s->last_mc == 1 ? s->d_extra : nullptr; a.grf_rows = s->last_grf ? s->d_grf_rows : nullptr;
+    a.st = h->d_st; a.rows = e->d_rows; a.state = e->d_state; a.x0 = h->d_x0;
+    a.logX = e->d_X; a.logU = e->d_U; a.logY = e->d_Y;
+    // (both kernels are timed into the handle's kernel table, hsddp_get_kernel_times, like the solver's; the walk's time is the simulation object's)
+    { Timed t(h, "k_episode_commit"); hipLaunchKernelGGL(k_episode_commit, dim3((unsigned)h->batch), dim3(64), 0, h->stream, h->d_ph, a); }
+    if (e->pending >= 0) {      // the tick ended on a touchdown: the reset map the moved window no longer holds
+        Timed t(h, "k_episode_impact");
+        hipLaunchKernelGGL(k_episode_impact, dim3((unsigned)((h->batch + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, e->pending, h->batch, (const EpiRow*)e->d_rows, e->d_state, h->d_x0);
+        e->n_impacts++;
+    }
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(h->stream));
+    drain_events(h);
+    e->tick++;
+    return HSDDP_OK;
+}
+
+int hsddp_episode_get_rows(hsddp_episode_t* e, int b0, int nb, hsddp_episode_row_t* rows, double* x_now) {
+    if (!episode_range_ok(e, b0, nb) || !rows) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(e->h->device));
+    HIPCK(hipMemcpy(rows, e->d_rows + b0, (size_t)nb * sizeof(EpiRow), hipMemcpyDeviceToHost));
+    if (x_now) HIPCK(hipMemcpy(x_now, e->d_state + (size_t)b0 * 36, (size_t)nb * 36 * 8, hipMemcpyDeviceToHost));
+    return HSDDP_OK;
+}
+
+int hsddp_episode_get_log(hsddp_episode_t* e, int b0, int nb, double* X, double* U, double* Y) {
+    if (!episode_range_ok(e, b0, nb) || !e->keep) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(e->h->device));
+    const size_t steps = (size_t)e->max_ticks * e->n_exec, sx = (steps + 1) * 36, su = steps * 12;
+    if (X) HIPCK(hipMemcpy(X, e->d_X + (size_t)b0 * sx, (size_t)nb * sx * 8, hipMemcpyDeviceToHost));
+    if (U) HIPCK(hipMemcpy(U, e->d_U + (size_t)b0 * su, (size_t)nb * su * 8, hipMemcpyDeviceToHost));
+    if (Y) HIPCK(hipMemcpy(Y, e->d_Y + (size_t)b0 * su, (size_t)nb * su * 8, hipMemcpyDeviceToHost));
+    return HSDDP_OK;
+}
+
+const double* hsddp_episode_device_state(hsddp_episode_t* e) { return e ? e->d_state : nullptr; }
+hsddp_sim_t* hsddp_episode_sim(hsddp_episode_t* e) { return e ? e->sim : nullptr; }
+
+int hsddp_episode_status(hsddp_episode_t* e, int* tick, int* n_alive, int* n_impacts) {
+    if (!e) return HSDDP_EINVAL;
+    if (n_alive) {
+        HIPCK(hipSetDevice(e->h->device));
+        std::vector<EpiRow> r((size_t)e->h->batch);
+        HIPCK(hipMemcpy(r.data(), e->d_rows, r.size() * sizeof(EpiRow), hipMemcpyDeviceToHost));
+        int n = 0; for (const EpiRow& q : r) n += q.end_reason == 0 ? 1 : 0;
+        *n_alive = n;
+    }
+    if (tick) *tick = e->tick;
+    if (n_impacts) *n_impacts = e->n_impacts;
     return HSDDP_OK;
 }
 

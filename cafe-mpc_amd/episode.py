@@ -1,0 +1,216 @@
+"""Batched closed-loop MPC episodes (include/hsddp_episode.h; libhsddp_hip.so only): B robots, each running its own MPC against the simulated
+whole-body dynamics, with the simulated state handed to the next solve on the device.
+
+    ep = solver.episode(n_exec=2, max_ticks=50, keep_log=True)      # or Episode(solver, 2, 50, True)
+    ep.set_grf(0.6)                                                 # optional: contact-force records (include/hsddp_grf.h)
+    ep.reset(x0)                                                    # [B, 36]; also the solver's initial condition
+    solver.solve(opt)
+    out = run_mhpc(solver, pd, phases, opt_rt, 50, dist=Disturbance(seed=7, sigma_u=0.2, fall_height=0.12), episode=ep)
+    rows, x_now = ep.rows(); X, U, Y = ep.log(); tick, n_alive, n_impacts = ep.status()
+
+Nothing here computes anything on the product path: the walk is the kernel of sim.Simulation, the commit and the pending reset map are
+k_episode_commit / k_episode_impact (csrc/episode.hpp).  tick_seed and fold_rows state the seed schedule and the commit in numpy: the
+definitions the library mirrors."""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+
+from . import _abi
+from .sim import Disturbance
+
+_M64 = (1 << 64) - 1
+
+
+def tick_seed(seed, t):
+    """Seed of the noise of tick t: the seed itself for t = 0, else the t-th raw 64-bit output of SplitMix64(seed) (problems.SplitMix64: the state
+    after t steps, mixed, before the shift that makes a double of it)."""
+    seed &= _M64
+    if t == 0:
+        return seed
+    z = (seed + t * 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def empty_rows(n):
+    """The rows a reset leaves: nothing seen yet."""
+    r = np.zeros(n, dtype=_abi.EPISODE_ROW_DTYPE)
+    r["min_height"] = np.inf; r["min_fz"] = np.inf; r["min_cone"] = np.inf; r["max_fz"] = -np.inf; r["first_slip"] = -1; r["end_step"] = -1
+    return r
+
+
+def fold_rows(rows, tick, sim_rows, X, U, q, r, xr, ur, extra=None, grf=None, status=None):
+    """The commit of one tick into the episode rows (k_episode_commit), for the problems alive at the start of the tick (end_reason == 0); the
+    others are returned unchanged.  rows: [B] EPISODE_ROW_DTYPE before the tick; sim_rows: [B] SIM_ROW_DTYPE of the tick's walk; X [B, n + 1, 36],
+    U [B, n, 12]: the tick's trajectory; q [n, 36], r [n, 12]: the weights of the phase each step maps to; xr [B or 1, n, 36], ur [B or 1, n, 12]: the
+    reference rows of the steps' knots; extra: [B] MC_EXTRA_DTYPE of a disturbed walk or None; grf: [B] GRF_ROW_DTYPE with the force records on or
+    None; status: [B] status of the handle's last solve or None.  Returns the rows after the tick."""
+    out = rows.copy()
+    n = U.shape[1]
+    base = tick * n
+    live = rows["end_reason"] == 0
+    for f in ("dev_q", "dev_v", "max_torque"):
+        out[f] = np.where(live, np.fmax(rows[f], sim_rows[f]), rows[f])
+    out["min_height"] = np.where(live, np.fmin(rows["min_height"], sim_rows["min_height"]), rows["min_height"])
+    if extra is not None:
+        out["n_sat"] = np.where(live, rows["n_sat"] + extra["n_sat"], rows["n_sat"])
+    if grf is not None:
+        out["min_fz"] = np.where(live, np.fmin(rows["min_fz"], grf["min_fz"]), rows["min_fz"])
+        out["min_cone"] = np.where(live, np.fmin(rows["min_cone"], grf["min_cone"]), rows["min_cone"])
+        out["max_fz"] = np.where(live, np.fmax(rows["max_fz"], grf["max_fz"]), rows["max_fz"])
+        out["first_slip"] = np.where(live & (rows["first_slip"] < 0) & (grf["first_slip"] >= 0), base + grf["first_slip"], rows["first_slip"])
+        out["n_slip"] = np.where(live, rows["n_slip"] + grf["n_slip"], rows["n_slip"])
+    out["steps"] = np.where(live, rows["steps"] + n, rows["steps"])
+    if status is not None:
+        out["bad_solves"] = np.where(live & (np.asarray(status) == 1), rows["bad_solves"] + 1, rows["bad_solves"])
+    dx = X[:, :n] - xr; du = U - ur
+    cost = 0.5 * (q[None] * dx * dx).sum(axis=(1, 2)) + 0.5 * (r[None] * du * du).sum(axis=(1, 2))
+    out["track_cost"] = np.where(live, rows["track_cost"] + cost, rows["track_cost"])
+    fb = sim_rows["first_bad"]
+    ff = extra["first_fall"] if extra is not None else np.full(len(rows), -1)
+    fell = (ff >= 0) & ((fb < 0) | (ff <= fb))
+    reason = np.where(fell, 2, np.where(fb >= 0, 1, 0))
+    step = np.where(fell, ff, fb)
+    out["end_reason"] = np.where(live, reason, rows["end_reason"])
+    out["end_step"] = np.where(live & (reason != 0), base + step, rows["end_step"])
+    return out
+
+
+def step_weights(phases, smap):
+    """q [n, 36], r [n, 12] of the phases the steps of a step map (3 x n: phase, knot, reset) belong to."""
+    q = np.array([[phases[p]["desc"].q[i] for i in range(36)] for p in smap[0]])
+    r = np.array([[phases[p]["desc"].r[j] for j in range(12)] for p in smap[0]])
+    return q, r
+
+
+def step_refs(solver, smap):
+    """xr [B, n, 36], ur [B, n, 12]: the reference rows every problem tracks at the knots of a step map (hsddp_get_references)."""
+    refs = {p: solver.get_references(int(p)) for p in set(int(p) for p in smap[0])}
+    xr = np.stack([refs[int(p)]["xr"][:, k] for p, k in zip(smap[0], smap[1])], axis=1)
+    ur = np.stack([refs[int(p)]["ur"][:, k] for p, k in zip(smap[0], smap[1])], axis=1)
+    return xr, ur
+
+
+class Episode:
+    """One hsddp_episode_t on a Solver's handle.  Survives Solver.reconfigure (advance rebinds its step map).  Close it before the solver."""
+
+    def __init__(self, solver, n_exec, max_ticks, keep_log=False):
+        self.lib = _abi.bind_episode(solver.lib)      # raises on a library without include/hsddp_episode.h (the CPU checker)
+        self.solver, self.n_exec, self.max_ticks, self.keep_log = solver, int(n_exec), int(max_ticks), bool(keep_log)
+        self.e = C.c_void_p()
+        rc = self.lib.hsddp_episode_create(solver.h, self.n_exec, self.max_ticks, 1 if keep_log else 0, C.byref(self.e))
+        if rc != 0:
+            self.e = C.c_void_p()
+            raise RuntimeError(f"hsddp_episode_create failed rc={rc}")
+
+    def close(self):
+        if self.e:
+            self.lib.hsddp_episode_destroy(self.e)
+            self.e = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _source(self, name, x):
+        """(address, on the device, what keeps it alive) of a [B, 36] float64 numpy array or contiguous torch tensor on the handle's device."""
+        shape = (self.solver.batch, 36)
+        if type(x).__module__.startswith("torch"):
+            import torch
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.device.type != "cuda" or tuple(x.shape) != shape:
+                raise ValueError(f"{name}: need a contiguous float64 tensor of shape {shape} on the handle's device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+            torch.cuda.current_stream(x.device).synchronize()      # the copy runs on the handle's stream
+            return x.data_ptr(), 1, x
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != shape:
+            raise ValueError(f"{name}: shape {x.shape}, need {shape}")
+        return x.ctypes.data, 0, x
+
+    def reset(self, x0):
+        """x0 [B, 36]: the states of tick 0 and the solver's initial condition; rows and log emptied, tick = 0."""
+        p, dev, keep = self._source("x0", x0)
+        rc = self.lib.hsddp_episode_reset(self.e, p, dev)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_episode_reset failed rc={rc}")
+
+    def set_grf(self, mu, fz_min=0.0):
+        """Contact-force records (include/hsddp_grf.h) for every later tick: mu > 0 on with these thresholds, mu == 0 off."""
+        rc = self.lib.hsddp_grf_set(self.lib.hsddp_episode_sim(self.e), float(mu), float(fz_min))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_grf_set failed rc={rc}")
+
+    def advance(self, dist=None, kick=None):
+        """One tick: n_exec steps of the solver's current policy from the episode's states, committed and handed to the solver.  dist
+        (sim.Disturbance; its seed is the episode's, the tick's is tick_seed) and / or kick ([B, 36] at step dist.kick_step of the tick)."""
+        if dist is None and kick is not None:
+            dist = Disturbance()
+        d = dist.to_c() if dist is not None else None
+        kp, kdev, keep = self._source("kick", kick) if kick is not None else (None, 0, None)
+        rc = self.lib.hsddp_episode_advance(self.e, C.byref(d) if d is not None else None, kp, kdev)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_episode_advance failed rc={rc}")
+
+    def rows(self, b0=0, nb=None):
+        """(rows [nb] as a structured array of hsddp_episode_row_t, the current states [nb, 36])."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros(max(nb, 0), dtype=_abi.EPISODE_ROW_DTYPE); x = np.zeros((max(nb, 0), 36))
+        rc = self.lib.hsddp_episode_get_rows(self.e, b0, nb, rows.ctypes.data, x.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_episode_get_rows failed rc={rc}")
+        return rows, x
+
+    def log(self, b0=0, nb=None):
+        """(X [nb, max_ticks n_exec + 1, 36], U, Y [nb, max_ticks n_exec, 12]); needs keep_log.  Entries behind the ticks made so far are zero."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        n = self.max_ticks * self.n_exec
+        X = np.zeros((max(nb, 0), n + 1, 36)); U = np.zeros((max(nb, 0), n, 12)); Y = np.zeros((max(nb, 0), n, 12))
+        rc = self.lib.hsddp_episode_get_log(self.e, b0, nb, X.ctypes.data, U.ctypes.data, Y.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_episode_get_log failed rc={rc}")
+        return X, U, Y
+
+    def state(self):
+        """Device address of the current states [B, 36] (valid while the object lives)."""
+        return int(self.lib.hsddp_episode_device_state(self.e) or 0)
+
+    def status(self):
+        """(ticks advanced since the last reset, problems still alive, reset maps applied by advance)."""
+        t, a, i = C.c_int(), C.c_int(), C.c_int()
+        rc = self.lib.hsddp_episode_status(self.e, C.byref(t), C.byref(a), C.byref(i))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_episode_status failed rc={rc}")
+        return t.value, a.value, i.value
+
+
+def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False):
+    """The receding-horizon loop of MHPCLocomotion::update with the SIMULATED state fed back, for the whole batch.  solver: solved for the window
+    `phases` of pd (builder.MHPCProblemData).  Per tick: episode.advance, pd.update(), builder.shift_solver_in_place, hook(tick, phases) - the
+    place for solver.set_references - and solver.solve(opt_rt).  kicks: {tick: (kick_step, [B, 36])}.  episode: an Episode already reset; None
+    creates one (n_exec = dt_mpc / dt_wb, max_ticks = n_ticks) and resets it to the solver's Xbar[0].  Returns a dict: episode, phases (the last
+    window), n_iters / n_ls_iters / n_reg_iters / cost [n_ticks, B], alive [n_ticks]."""
+    from . import builder
+    if episode is None:
+        episode = Episode(solver, int(round(float(pd.cfg["dt_mpc"]) / pd.dt_wb)), n_ticks, keep_log)
+        episode.reset(np.ascontiguousarray(solver.field(0, "XBAR")[:, 0]))
+    out = dict(n_iters=[], n_ls_iters=[], n_reg_iters=[], cost=[], alive=[])
+    for t in range(n_ticks):
+        d, k = dist, None
+        if kicks is not None and t in kicks:
+            step, k = kicks[t]
+            d = dataclasses.replace(dist if dist is not None else Disturbance(), kick_step=int(step))
+        episode.advance(d, k)
+        m = pd.update()
+        phases, _ = builder.shift_solver_in_place(solver, phases, pd, m, ubar_mode="zero")
+        if hook is not None:
+            hook(t, phases)
+        solver.solve(opt_rt)
+        ia = solver.info_arrays()
+        out["n_iters"].append(ia["n_iters"]); out["n_ls_iters"].append(ia["n_ls_iters"]); out["n_reg_iters"].append(ia["n_reg_iters"]); out["cost"].append(ia["actual_cost"])
+        out["alive"].append(episode.status()[1])
+    res = {k: np.array(v) for k, v in out.items()}
+    res["episode"] = episode; res["phases"] = phases
+    return res

@@ -21,6 +21,7 @@
 #include "hsddp_sim.h"
 #include "hsddp_mc.h"
 #include "hsddp_grf.h"
+#include "hsddp_episode.h"
 
 namespace hsddp {
 
@@ -89,6 +90,49 @@ public:
 private:
     hsddp_sim_t* s_ = nullptr;
     int batch_, R_, n_, rc_ = 0; bool keep_, mc_ = false, grf_ = false, grf_run_ = false;      // grf_run_: the last run was made with the records on
+};
+
+// Batched closed-loop MPC episodes (include/hsddp_episode.h): one device object on a solver's handle that executes the first n_exec knots of the
+// current policy from its own states, commits the tick and hands the states to the next solve on the device.  Survives
+// MultiPhaseDDP::reconfigure (advance() rebinds the step map); destroy it before the solver.
+struct EpisodeLog { std::vector<double> X, U, Y; };      // batch x (max_ticks n_exec + 1) x 36, batch x max_ticks n_exec x 12 twice
+class Episode {
+public:
+    Episode(hsddp_handle_t* h, int batch, int n_exec, int max_ticks, bool keep_log = false) : batch_(batch), n_(n_exec), ticks_(max_ticks), keep_(keep_log) {
+        rc_ = hsddp_episode_create(h, n_exec, max_ticks, keep_log ? 1 : 0, &e_);
+        if (rc_ != HSDDP_OK) e_ = nullptr;
+    }
+    ~Episode() { if (e_) hsddp_episode_destroy(e_); }
+    Episode(const Episode&) = delete;
+    Episode& operator=(const Episode&) = delete;
+    // x0: batch x 36 (host memory, or device memory with src_device = 1): the states of tick 0 and the solver's initial condition
+    bool reset(const double* x0, int src_device = 0) { rc_ = e_ ? hsddp_episode_reset(e_, x0, src_device) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // one tick; dist null: the plain walk.  kick: batch x 36 or null, added at step dist->kick_step of the tick
+    bool advance(const hsddp_mc_dist_t* dist = nullptr, const double* kick = nullptr, int kick_device = 0) {
+        rc_ = e_ ? hsddp_episode_advance(e_, dist, kick, kick_device) : HSDDP_EINVAL; return rc_ == HSDDP_OK;
+    }
+    // contact-force records for every later tick (include/hsddp_grf.h)
+    bool set_grf(double mu, double fz_min = 0.0) { rc_ = e_ ? hsddp_grf_set(hsddp_episode_sim(e_), mu, fz_min) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    std::vector<hsddp_episode_row_t> rows(std::vector<double>* x_now = nullptr) {
+        std::vector<hsddp_episode_row_t> r((size_t)batch_);
+        if (x_now) x_now->resize((size_t)batch_ * 36);
+        rc_ = e_ ? hsddp_episode_get_rows(e_, 0, batch_, r.data(), x_now ? x_now->data() : nullptr) : HSDDP_EINVAL;
+        return r;
+    }
+    EpisodeLog log() {
+        EpisodeLog l;
+        if (!e_ || !keep_) { rc_ = HSDDP_EINVAL; return l; }
+        const size_t n = (size_t)ticks_ * n_;
+        l.X.resize((size_t)batch_ * (n + 1) * 36); l.U.resize((size_t)batch_ * n * 12); l.Y.resize((size_t)batch_ * n * 12);
+        rc_ = hsddp_episode_get_log(e_, 0, batch_, l.X.data(), l.U.data(), l.Y.data());
+        return l;
+    }
+    const double* state() { return e_ ? hsddp_episode_device_state(e_) : nullptr; }      // batch x 36 on the device
+    bool status(int* tick, int* n_alive, int* n_impacts) { rc_ = e_ ? hsddp_episode_status(e_, tick, n_alive, n_impacts) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    int last_error() const { return rc_; }
+private:
+    hsddp_episode_t* e_ = nullptr;
+    int batch_, n_, ticks_, rc_ = 0; bool keep_;
 };
 
 template <typename T = double>
