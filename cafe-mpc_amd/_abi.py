@@ -283,6 +283,24 @@ def bind_grf(lib):
     return lib
 
 
+# include/hsddp_substep.h: sub-stepped integration of a simulation object (libhsddp_hip.so only).  A list and a binder of their own: the lists
+# and binders above are those of their headers and stay as they are.
+SUBSTEP_EXPORTS = ["hsddp_substep_set", "hsddp_substep_get"]
+SUBSTEP_MAX = 64          # HSDDP_SUBSTEP_MAX
+
+
+def bind_substep(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_substep.h (and of hsddp_sim.h, which they work on).  Raises if the library lacks any."""
+    missing = [s for s in SUBSTEP_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the substep entry points {missing}")
+    bind_sim(lib)
+    H = C.c_void_p
+    lib.hsddp_substep_set.argtypes = [H, C.c_int]
+    lib.hsddp_substep_get.argtypes = [H, IP]
+    return lib
+
+
 # include/hsddp_episode.h: batched closed-loop MPC episodes (libhsddp_hip.so only)
 EPISODE_EXPORTS = ["hsddp_episode_create", "hsddp_episode_destroy", "hsddp_episode_reset", "hsddp_episode_advance", "hsddp_episode_get_rows",
                    "hsddp_episode_get_log", "hsddp_episode_device_state", "hsddp_episode_sim", "hsddp_episode_status"]
@@ -575,16 +593,17 @@ class Solver:
                  "get_references")
         return out
 
-    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None):
+    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1):
         """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)
         over the first n_steps whole-body control knots (include/hsddp_sim.h): dict with rows (structured array [batch, R] of dev_q, dev_v,
         min_height, max_torque, first_bad), x_final [batch, R, 36] and, with keep_traj, X [batch, R, n_steps + 1, 36] and U [batch, R, n_steps, 12].
         sim.Simulation keeps the device object across calls.  dist (sim.Disturbance) / kick [batch, R, 36]: a disturbed run (include/hsddp_mc.h),
         which also returns extra (structured array [batch, R] of first_fall, n_sat).  grf = (mu, fz_min): contact-force records
         (include/hsddp_grf.h), grf (structured array [batch, R] of min_fz, min_cone, max_fz, first_slip, n_slip) and, with keep_traj, Y
-        [batch, R, n_steps, 12]."""
+        [batch, R, n_steps, 12].  substeps = S > 1: every control knot is S forward-Euler steps of dt / S under the knot's torque
+        (include/hsddp_substep.h); shapes and meanings stay, n_slip counts (foot, substep) pairs."""
         from . import sim
-        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf)
+        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps)
 
     def episode(self, n_exec, max_ticks, keep_log=False):
         """An episode.Episode on this solver (include/hsddp_episode.h): batched closed-loop MPC ticks with the simulated state handed to the next

@@ -20,6 +20,7 @@
 #include "hsddp_refs.h"
 #include "hsddp_sim.h"
 #include "hsddp_grf.h"
+#include "hsddp_substep.h"
 #include "hsddp_mc.h"
 #include "hsddp_episode.h"
 #include "hs_types.hpp"
@@ -1646,6 +1647,16 @@ int hsddp_get_references(hsddp_handle_t* h, int phase, int b0, int nb, double* x
 
 // ------------------------------------------------------------------------------------------------ closed-loop policy simulation (hsddp_sim.h)
 }  // extern "C"
+// The sub-stepped kernels and their launcher (hsddp_substep.h): hsddp_sub.hip, which the Makefile compiles as a translation unit of its own
+// (-DHS_SUB_SEPARATE here) so that this file's code object stays what it was; any other build takes it in here.
+#ifdef HS_SUB_SEPARATE
+namespace hs {
+void wbs_sub_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
+                    double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb);
+}
+#else
+#include "hsddp_sub.hip"
+#endif
 struct hsddp_sim {
     hsddp_handle* h = nullptr;
     int R = 0, n_steps = 0, keep = 0, gen = 0;
@@ -1658,12 +1669,14 @@ struct hsddp_sim {
     // contact-force records (hsddp_grf.h): allocated by the first hsddp_grf_set that switches them on.  grf_on: what later runs do; last_grf: what the last run did
     double *d_grf_rows = nullptr, *d_Y = nullptr; WbsGrfArgs* d_grf = nullptr;      // [B R][SIM_GRF_ROW] ; [B R][n_steps][12] (keep) ; thresholds and destinations
     bool grf_on = false, last_grf = false;
+    // sub-stepped integration (hsddp_substep.h): what later runs use; the trip count on the device, allocated by the first hsddp_substep_set above 1
+    int substeps = 1; WbsSubArgs* d_sub = nullptr;
 };
 static void sim_free(hsddp_sim* s) {
     if (!s) return;
     hipSetDevice(s->h->device);
     if (s->h->stream) hipStreamSynchronize(s->h->stream);
-    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf};
+    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf, s->d_sub};
     for (void* q : p) if (q) hipFree(q);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -1722,13 +1735,18 @@ int hsddp_sim_create(hsddp_handle_t* h, int n_samples, int n_steps, int keep_tra
 void hsddp_sim_destroy(hsddp_sim_t* s) { sim_free(s); }
 
 // the one launch path of a run: the plain kernel, or (mc) the disturbed one with the switches that are already on the device at s->d_mc; with the
-// contact-force records on (hsddp_grf_set), the twin of that kernel that keeps them
+// contact-force records on (hsddp_grf_set), the twin of that kernel that keeps them; with more than one substep (hsddp_substep_set), the sub-stepped
+// twin of whichever of the six that is
 static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, bool noise = false) {
     hsddp_handle* h = s->h;
     const size_t total = (size_t)h->batch * s->R;
     if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
     HIPCK(hipEventRecord(s->ev0, h->stream));
-    if (!s->grf_on) {
+    if (s->substeps > 1) {
+        // (the launcher leaves the runtime's error state alone: a failed launch is caught by the hipGetLastError below, as for the other kernels)
+        wbs_sub_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
+                       s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : nullptr, s->d_sub);
+    } else if (!s->grf_on) {
         if (!mc)
             hipLaunchKernelGGL(k_sim_quad, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
                                src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U);
@@ -1854,6 +1872,29 @@ int hsddp_grf_get(hsddp_sim_t* s, int b0, int nb, hsddp_grf_row_t* rows, double*
         rows[i].min_fz = q[0]; rows[i].min_cone = q[1]; rows[i].max_fz = q[2]; rows[i].first_slip = (int)q[3]; rows[i].n_slip = (int)q[4];
     }
     if (Y) HIPCK(hipMemcpy(Y, s->d_Y + off * sy, cnt * sy * 8, hipMemcpyDeviceToHost));
+    return HSDDP_OK;
+}
+
+int hsddp_substep_set(hsddp_sim_t* s, int substeps) {
+    if (!s || substeps < 1 || substeps > HSDDP_SUBSTEP_MAX) return HSDDP_EINVAL;
+    hsddp_handle* h = s->h;
+    if (substeps > 1 || s->d_sub) {      // (an object that never asks for more than one holds what it held before)
+        HIPCK(hipSetDevice(h->device));
+        if (!s->d_sub) {
+            hipError_t e_ = hipMalloc((void**)&s->d_sub, sizeof(WbsSubArgs));
+            if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] hipMalloc of the substep block failed: %s\n", hipGetErrorString(e_)); s->d_sub = nullptr; return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; }
+        }
+        WbsSubArgs a;
+        a.substeps = substeps; a.pad = 0;
+        HIPCK(hipMemcpyAsync(s->d_sub, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));      // (pageable source: staged before the call returns; the runs are on this stream)
+    }
+    s->substeps = substeps;
+    return HSDDP_OK;
+}
+
+int hsddp_substep_get(hsddp_sim_t* s, int* substeps) {
+    if (!s || !substeps) return HSDDP_EINVAL;
+    *substeps = s->substeps;
     return HSDDP_OK;
 }
 

@@ -391,8 +391,8 @@ struct WbsMcArgs {
 // NOISE 0: the walk of a run whose three sigmas are zero, compiled without the generator.  Measured (MI355X, config 3 x 16 samples x 200 steps, plain
 // run 9.88 ms): with the generator compiled in and branched over, a run with only u_max set took 11.74 ms - the register allocation of the whole
 // loop pays for code that does not run; without it 9.83 ms.  So the host picks the instantiation, and every other switch stays a run-time branch.
-struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0; };
-template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0; const WbsMcArgs* a; };
+struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0; };
+template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0; const WbsMcArgs* a; };
 constexpr int SIM_PARK_MC = SIM_PARK + 2;       // ... and n_sat, first_fall
 // Contact-force records (include/hsddp_grf.h): GRF 1 in the policy.  The walk takes the lane's multiplier of every mode-0 solve, keeps five running
 // values per lane (lane = leg) - smallest / largest stance fz, smallest cone margin, first violating step, violations - and joins them over the
@@ -405,8 +405,19 @@ struct WbsGrfArgs {
 constexpr int SIM_GRF_ROW = 5;     // min_fz | min_cone | max_fz | first_slip | n_slip
 constexpr int SIM_GRF_PARK = 5;    // the lane's running values, parked behind the others
 constexpr double SIM_GRF_NONE = 1e18;      // first_slip of a lane without a violation while the walk runs: above every step index
-struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1; const WbsGrfArgs* gr; };
-template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; };
+struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0; const WbsGrfArgs* gr; };
+template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
+// Sub-stepped integration (include/hsddp_substep.h): SUB 1 in the policy.  A control knot is S forward-Euler steps of dt / S under the knot's torque
+// (zero-order hold): the feedback, the noise and every record of the state stay once per control step, the contact solve, the divergence test and
+// the force records run once per substep.  S is a run-time trip count read from device memory through a laundered pointer, as the other switches
+// are.  The lane's three torques now live across contact solves and join the parked column (SIM_SUB_PARK, behind everything else); every `if
+// constexpr (D::SUB)` below is this code, and the six policies above compile to what they compiled to without it.
+struct WbsSubArgs { int substeps, pad; };      // 2 .. 64 (the host launches the kernels above for 1)
+constexpr int SIM_SUB_PARK = 3;
+struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1; const WbsMcArgs* a; const WbsSubArgs* sb; };
+struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
 
 // The generator (sim.mc_normals is its definition): draw(n) is output n >= 1 of SplitMix64(seed), whose state is the counter seed + n G; the normal of
 // coordinate c of (global problem, sample, step) is Box-Muller on draws n0 + 1 and n0 + 2, n0 = 2 (((problem 65536 + sample) 65536 + step) 48 + c).
@@ -438,12 +449,14 @@ inline void wbs_mc_normal3(unsigned long long seed, unsigned long long base, con
 }
 inline const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { return p; }
 inline const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { return p; }
+inline const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { return p; }
 #else
 HD void wbs_mc_normal3(unsigned long long seed, unsigned long long base, const double& c, double (&z)[3]) { wbs_mc_normal3_lane(seed, base, (int)c, z); }
 // the switches are read again at every step from a pointer the compiler cannot see through: held in scalar registers across the contact solve
 // they were spilled (as kernel arguments by value: 94 scalar registers in scratch)
 HD const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { asm volatile("" : "+s"(p)); return p; }
+HD const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { asm volatile("" : "+s"(p)); return p; }
 #endif
 
 template <class Q, class D = WbsPlain>
@@ -482,19 +495,22 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
     // them in a column of LDS of its own around the call instead (24 x 64 doubles = 12 KB per wave; lane-private, so no barrier): 304 -> 52 B of
     // scratch per lane, 13.6 -> 11.0 ms at config 3 x 16 samples x 200 steps.  The empty asm keeps the compiler from forwarding the registers.
 #ifdef HS_HOST_EMU
-    auto park = [](bool) {};
+    auto park = [](bool, S*) {};
 #else
-    auto park = [&](bool out) {
+    auto park = [&](bool out, S* u3) {      // u3: the lane's torques, parked by the sub-stepped walk alone
         S* const c = stash + threadIdx.x;
         S* v[24] = {&qb[0], &qb[1], &qb[2], &qb[3], &qb[4], &qb[5], &vb[0], &vb[1], &vb[2], &vb[3], &vb[4], &vb[5], &ql[0], &ql[1], &ql[2], &vl[0], &vl[1], &vl[2],
                     &dq, &dv, &umax, &hmin, &alive, &first_bad};
         constexpr int G0 = D::MC ? SIM_PARK_MC : SIM_PARK;      // (records) the five running values behind the others
+        constexpr int U0 = G0 + (D::GRF ? SIM_GRF_PARK : 0);    // (substeps) the torques behind those
         if (out) {
             _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; if constexpr (D::MC) { c[64 * 24] = nsat; c[64 * 25] = ffall; }
             if constexpr (D::GRF) { c[64 * G0] = gfmin; c[64 * (G0 + 1)] = gcmin; c[64 * (G0 + 2)] = gfmax; c[64 * (G0 + 3)] = gfirst; c[64 * (G0 + 4)] = gslip; }
+            if constexpr (D::SUB) { c[64 * U0] = u3[0]; c[64 * (U0 + 1)] = u3[1]; c[64 * (U0 + 2)] = u3[2]; }
         } else {
             asm volatile("" ::: "memory"); _Pragma("unroll") for (int i = 0; i < 24; i++) *v[i] = c[64 * i]; if constexpr (D::MC) { nsat = c[64 * 24]; ffall = c[64 * 25]; }
             if constexpr (D::GRF) { gfmin = c[64 * G0]; gcmin = c[64 * (G0 + 1)]; gfmax = c[64 * (G0 + 2)]; gfirst = c[64 * (G0 + 3)]; gslip = c[64 * (G0 + 4)]; }
+            if constexpr (D::SUB) { u3[0] = c[64 * U0]; u3[1] = c[64 * (U0 + 1)]; u3[2] = c[64 * (U0 + 2)]; }
         }
     };
 #endif
@@ -593,18 +609,23 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         if (trajX != nullptr) store_state((g * (size_t)(n_steps + 1) + s) * 36);
         if (trajU != nullptr) { _Pragma("unroll") for (int j = 0; j < 3; j++) Q::st(trajU, (g * (size_t)n_steps + s) * 12 + j, 3, ul[j]); }
         // ---- the step, and behind the last knot of a phase with a touchdown the impact: ONE call site of the dynamics, the phase boundary is a
-        // uniform branch of the loop
+        // uniform branch of the loop.  Sub-stepped walk: S trips of the step with the same torques, then the impact - S + reset trips, the last one
+        // in mode 1 when reset is set.  A quad that diverged in an earlier trip rides along through the rest (the selects below keep its state).
         const int cm_dyn = (P.contact[0] > 0 ? 1 : 0) | (P.contact[1] > 0 ? 2 : 0) | (P.contact[2] > 0 ? 4 : 0) | (P.contact[3] > 0 ? 8 : 0);
         const int cm_td = (P.td[0] ? 1 : 0) | (P.td[1] ? 2 : 0) | (P.td[2] ? 4 : 0) | (P.td[3] ? 8 : 0);
         const double dt = P.dt, alpha = P.bg_alpha;
+        int last = reset;
+        if constexpr (D::SUB) last = reset + wbs_uniform(wbs_sub_fresh(dist.sb)->substeps) - 1;
         _Pragma("nounroll")
-        for (int mode = 0; mode <= reset; mode++) {
+        for (int trip = 0; trip <= last; trip++) {
+            int mode = trip;
+            if constexpr (D::SUB) mode = (reset != 0 && trip == last) ? 1 : 0;
             S ob[6]; V3<S> ol;
-            park(true);
+            park(true, ul);
             if constexpr (D::GRF) {
                 V3<S> lam;
                 wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol, &lam);
-                park(false);
+                park(false, ul);
                 // ---- records: the force of the step on the lane's foot, counted if the foot is a stance foot of the phase (a select on the
                 // wave-uniform contact mask) and the sample had not diverged before the step (`alive` is still the value the step began with).
                 // The impact takes no record.
@@ -617,17 +638,19 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                     const typename Q::B slip = Q::gt(alive * st * bad, S(0.5));
                     gfmin = Q::sel(on, Q::min(gfmin, lam.z), gfmin); gcmin = Q::sel(on, Q::min(gcmin, cone), gcmin); gfmax = Q::sel(on, wbs_max<Q, S>(gfmax, lam.z), gfmax);
                     gfirst = Q::sel(slip, Q::min(gfirst, S((double)s)), gfirst); gslip = gslip + Q::sel(slip, one, zero);
-                    if (ga.Y != nullptr) { Q::st(ga.Y, (g * (size_t)n_steps + s) * 12, 3, lam.x); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 1, 3, lam.y); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 2, 3, lam.z); }
+                    if (ga.Y != nullptr && (D::SUB == 0 || trip == 0)) { Q::st(ga.Y, (g * (size_t)n_steps + s) * 12, 3, lam.x); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 1, 3, lam.y); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 2, 3, lam.z); }
                 }
             } else {
                 wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol);
-                park(false);
+                park(false, ul);
             }
             if (mode == 0) {      // forward Euler (WBM.cpp:25-26), then the divergence test on the new state
+                double hs = dt;       // (substeps) the step of a trip, dt / S: one division, formed where it is used
+                if constexpr (D::SUB) hs = dt / (double)wbs_uniform(wbs_sub_fresh(dist.sb)->substeps);
                 S xb[6], yb[6], xl[3], yl[3], nsq = zero;
-                _Pragma("unroll") for (int i = 0; i < 6; i++) { xb[i] = qb[i] + vb[i] * dt; yb[i] = vb[i] + ob[i] * dt; nsq = nsq + w0 * (xb[i] * xb[i] + yb[i] * yb[i]); }
+                _Pragma("unroll") for (int i = 0; i < 6; i++) { xb[i] = qb[i] + vb[i] * hs; yb[i] = vb[i] + ob[i] * hs; nsq = nsq + w0 * (xb[i] * xb[i] + yb[i] * yb[i]); }
                 const S o3[3] = {ol.x, ol.y, ol.z};
-                _Pragma("unroll") for (int j = 0; j < 3; j++) { xl[j] = ql[j] + vl[j] * dt; yl[j] = vl[j] + o3[j] * dt; nsq = nsq + (xl[j] * xl[j] + yl[j] * yl[j]); }
+                _Pragma("unroll") for (int j = 0; j < 3; j++) { xl[j] = ql[j] + vl[j] * hs; yl[j] = vl[j] + o3[j] * hs; nsq = nsq + (xl[j] * xl[j] + yl[j] * yl[j]); }
                 nsq = Q::sum(nsq);
                 // good <=> !(nsq > 1e12) && nsq == nsq   (below 1e12 adding one always gives a larger number; a NaN compares false)
                 const S good = Q::sel(Q::gt(nsq, S(1e12)), zero, one) * Q::sel(Q::gt(nsq + 1.0, nsq), one, zero);
@@ -668,7 +691,7 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
     Q::st0(rows, g * SIM_ROW + 3, wbs_qmax<Q, S>(umax)); Q::st0(rows, g * SIM_ROW + 4, first_bad);
 }
 
-#ifndef HS_HOST_EMU
+#if !defined(HS_HOST_EMU) && !defined(HS_SIM_WALK_ONLY)      // (HS_SIM_WALK_ONLY: hsddp_sub.hip takes the walk and defines kernels of its own)
 // grid = ceil(B R / 16) waves of sixteen quads.  The loop is sequential in the knots, so a launch has B R / 16 waves whatever the window length.
 #ifndef SIM_WPE
 #define SIM_WPE 1      // waves per SIMD the kernel is compiled for (as k_rollout_quad: up to 512 registers)
@@ -716,6 +739,7 @@ k_sim_quad_grf(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, in
 WBS_MC_GRF_KERNEL(k_sim_quad_mc_grf, 1)
 WBS_MC_GRF_KERNEL(k_sim_quad_mc0_grf, 0)
 #undef WBS_MC_GRF_KERNEL
+// The sub-stepped walks (hsddp_substep_set with S > 1) are six more instantiations with SUB 1 in the policy: hsddp_sub.hip, a translation unit of its own.
 #endif
 
 }  // namespace hs

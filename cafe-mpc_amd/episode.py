@@ -3,6 +3,7 @@ whole-body dynamics, with the simulated state handed to the next solve on the de
 
     ep = solver.episode(n_exec=2, max_ticks=50, keep_log=True)      # or Episode(solver, 2, 50, True)
     ep.set_grf(0.6)                                                 # optional: contact-force records (include/hsddp_grf.h)
+    ep.set_substeps(4)                                              # optional: sub-stepped integration (include/hsddp_substep.h)
     ep.reset(x0)                                                    # [B, 36]; also the solver's initial condition
     solver.solve(opt)
     out = run_mhpc(solver, pd, phases, opt_rt, 50, dist=Disturbance(seed=7, sigma_u=0.2, fall_height=0.12), episode=ep)
@@ -142,6 +143,20 @@ class Episode:
         rc = self.lib.hsddp_grf_set(self.lib.hsddp_episode_sim(self.e), float(mu), float(fz_min))
         if rc != 0:
             raise RuntimeError(f"hsddp_grf_set failed rc={rc}")
+
+    def set_substeps(self, substeps):
+        """Sub-stepped integration (include/hsddp_substep.h) for every later tick: S Euler steps of dt / S per control knot, torque held."""
+        rc = _abi.bind_substep(self.lib).hsddp_substep_set(self.lib.hsddp_episode_sim(self.e), int(substeps))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_substep_set failed rc={rc}")
+
+    @property
+    def substeps(self):
+        v = C.c_int()
+        rc = _abi.bind_substep(self.lib).hsddp_substep_get(self.lib.hsddp_episode_sim(self.e), C.byref(v))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_substep_get failed rc={rc}")
+        return v.value
 
     def advance(self, dist=None, kick=None):
         """One tick: n_exec steps of the solver's current policy from the episode's states, committed and handed to the solver.  dist

@@ -21,6 +21,7 @@
 #include "hsddp_sim.h"
 #include "hsddp_mc.h"
 #include "hsddp_grf.h"
+#include "hsddp_substep.h"
 #include "hsddp_episode.h"
 
 namespace hsddp {
@@ -66,6 +67,9 @@ public:
     }
     // contact-force records for every later run: mu > 0 on with these thresholds, mu == 0 off (include/hsddp_grf.h)
     bool set_grf(double mu, double fz_min = 0.0) { rc_ = s_ ? hsddp_grf_set(s_, mu, fz_min) : HSDDP_EINVAL; if (rc_ == HSDDP_OK) grf_ = mu > 0.0; return rc_ == HSDDP_OK; }
+    // sub-stepped integration for every later run: S Euler steps of dt / S per control knot under the knot's torque, 1 <= S <= 64 (include/hsddp_substep.h)
+    bool set_substeps(int substeps) { rc_ = s_ ? hsddp_substep_set(s_, substeps) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    int substeps() { int v = 1; rc_ = s_ ? hsddp_substep_get(s_, &v) : HSDDP_EINVAL; return v; }
     // the records of the last run alone (result() holds them too): rows batch x n_samples, Y batch x n_samples x n_steps x 12 or null
     bool grf(hsddp_grf_row_t* rows, double* Y = nullptr) { rc_ = s_ ? hsddp_grf_get(s_, 0, batch_, rows, Y) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     SimResult result() {
@@ -113,6 +117,8 @@ public:
     }
     // contact-force records for every later tick (include/hsddp_grf.h)
     bool set_grf(double mu, double fz_min = 0.0) { rc_ = e_ ? hsddp_grf_set(hsddp_episode_sim(e_), mu, fz_min) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // sub-stepped integration for every later tick (include/hsddp_substep.h)
+    bool set_substeps(int substeps) { rc_ = e_ ? hsddp_substep_set(hsddp_episode_sim(e_), substeps) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     std::vector<hsddp_episode_row_t> rows(std::vector<double>* x_now = nullptr) {
         std::vector<hsddp_episode_row_t> r((size_t)batch_);
         if (x_now) x_now->resize((size_t)batch_ * 36);

@@ -12,8 +12,10 @@
 
     res = solver.simulate(x0, n_steps=50, keep_traj=True, grf=(0.6, 0.0))      # include/hsddp_grf.h: res["grf"]["min_fz"], ["min_cone"], ["n_slip"], res["Y"]
 
+    res = solver.simulate(x0, n_steps=50, substeps=4)      # include/hsddp_substep.h: four Euler steps of dt / 4 per control knot, torque held
+
 Nothing here computes anything: the rollout is the k_sim_quad / k_sim_quad_mc kernel (csrc/wb_sim.hpp).  mc_normals states the generator of the
-disturbed runs in numpy, grf_rows the contact-force records: the definitions the kernel mirrors."""
+disturbed runs in numpy, grf_rows the contact-force records and grf_rows_sub those of a sub-stepped run: the definitions the kernel mirrors."""
 import ctypes as C
 import dataclasses
 
@@ -75,6 +77,32 @@ def grf_rows(Y, contact, mu, fz_min, first_bad=None):
     step = viol.any(axis=-1)
     out["first_slip"] = np.where(step.any(axis=-1), step.argmax(axis=-1), -1) if n else -1
     out["n_slip"] = viol.sum(axis=(-2, -1))
+    return out
+
+
+def grf_rows_sub(Y, contact, mu, fz_min, counted=None):
+    """The contact-force records of a sub-stepped run (include/hsddp_substep.h) from the forces of every substep.  Y: [..., n, S, 12], the force of
+    substep j of control step s; contact: [n, 4] as for grf_rows (a foot stands through all substeps of a step); counted: None, or a boolean array
+    [..., n, S] - substep (s, j) counts iff the sample was alive when it began.  min_fz, min_cone and max_fz run over the stance (foot, substep)
+    pairs that count; first_slip is the CONTROL step of the first violating substep; n_slip counts violating (foot, substep) pairs.  This is
+    grf_rows on the n S flattened substeps with the contact rows repeated and first_slip // S."""
+    Y = np.asarray(Y, dtype=np.float64)
+    n, S = Y.shape[-3], Y.shape[-2]
+    lead = Y.shape[:-3]
+    F = Y.reshape(lead + (n, S, 4, 3))
+    st = np.broadcast_to((np.asarray(contact).reshape(n, 1, 4) > 0), lead + (n, S, 4))
+    if counted is not None:
+        st = st & np.asarray(counted, dtype=bool).reshape(lead + (n, S, 1))
+    fz = F[..., 2]
+    cone = mu * fz - np.maximum(np.abs(F[..., 0]), np.abs(F[..., 1]))
+    viol = st & ((fz < fz_min) | (cone < 0.0))
+    out = np.zeros(lead, dtype=_abi.GRF_ROW_DTYPE)
+    out["min_fz"] = np.where(st, fz, np.inf).min(axis=(-3, -2, -1), initial=np.inf)
+    out["min_cone"] = np.where(st, cone, np.inf).min(axis=(-3, -2, -1), initial=np.inf)
+    out["max_fz"] = np.where(st, fz, -np.inf).max(axis=(-3, -2, -1), initial=-np.inf)
+    step = viol.any(axis=(-2, -1))
+    out["first_slip"] = np.where(step.any(axis=-1), step.argmax(axis=-1), -1) if n else -1
+    out["n_slip"] = viol.sum(axis=(-3, -2, -1))
     return out
 
 
@@ -151,6 +179,22 @@ class Simulation:
             raise RuntimeError(f"hsddp_grf_set failed rc={rc}")
         self.grf_on = mu > 0
 
+    def set_substeps(self, substeps):
+        """Sub-stepped integration (include/hsddp_substep.h) for every later run: S forward-Euler steps of dt / S per control knot under the
+        knot's torque, 1 <= S <= 64; 1 is the plain walk."""
+        rc = _abi.bind_substep(self.lib).hsddp_substep_set(self.s, int(substeps))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_substep_set failed rc={rc}")
+
+    @property
+    def substeps(self):
+        """What later runs use, as the library reports it (hsddp_substep_get)."""
+        v = C.c_int()
+        rc = _abi.bind_substep(self.lib).hsddp_substep_get(self.s, C.byref(v))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_substep_get failed rc={rc}")
+        return v.value
+
     def grf(self, b0=0, nb=None):
         """Structured array [nb, R] of hsddp_grf_row_t of the last run, which has to be one with the records on; with keep_traj the pair
         (rows, Y [nb, R, n_steps, 12])."""
@@ -192,11 +236,14 @@ class Simulation:
         return float(ms.value)
 
 
-def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None):
+def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1):
     """One-off simulation on `solver`: dict with rows, x_final and, with keep_traj, X and U (see Simulation); a disturbed run (dist / kick given)
-    returns extra too; grf = (mu, fz_min) adds the contact-force records grf and, with keep_traj, Y."""
+    returns extra too; grf = (mu, fz_min) adds the contact-force records grf and, with keep_traj, Y; substeps = S > 1 integrates every control
+    knot in S steps (include/hsddp_substep.h)."""
     sim = Simulation(solver, x0.shape[1], n_steps, keep_traj)
     try:
+        if substeps != 1:
+            sim.set_substeps(substeps)
         if grf is not None:
             sim.set_grf(*grf)
         sim.run(x0, dist=dist, kick=kick)
