@@ -111,14 +111,16 @@ __device__ __forceinline__ void cand_unit(int per, int g, int& c, int& r) {
 // their small knots are not held to the whole-body kernels' two waves per SIMD
 union RedLds { HkdLds h; SrbLds s; };
 // slot_list / nlist: the slots this launch covers (null: all nslots) - when the lane-quad kernel takes the whole-body running knots of a launch,
-// the one-wave programs only see the rest (terminal knots with their reset maps, single-rigid-body knots); unit_knots: running knots among them
+// the one-wave programs only see the rest (the terminal knots it leaves with their reset maps, single-rigid-body knots); unit_knots: running knots
+// among them; plist / nprob: the problems this launch is for (null: all nprob = batch of them, `mask` picks)
 #define ROLL_ARGS const PhaseDev* ph_, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, ModelDev md, EpsList el, OptDev opt, const double* x0, SlotArrays sa, \
-                  const ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist, int unit_knots
+                  const ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist, int unit_knots, const int* plist, int nprob
 template <bool WBM, class LDS> __device__ __forceinline__ void rollout_body(LDS& L, ROLL_ARGS) {
     PhaseC* ph = (PhaseC*)ph_;   // descriptors: constant memory, scalar loads
-    const int per = batch * nlist;
+    const int per = nprob * nlist;
     int c, r; cand_unit(per, blockIdx.x, c, r);
-    const int b = r / nlist, si = r - b * nlist;
+    const int ip = r / nlist, si = r - ip * nlist;
+    const int b = plist != nullptr ? plist[ip] : ip;
     if (masked_out(st[b], mask)) return;
     if (si == 0 && threadIdx.x == 0) atomicAdd(units, (unsigned long long)unit_knots);     // knots this launch rolls out (measurement only)
     const int s = slot_list != nullptr ? slot_list[si] : si;
@@ -157,7 +159,7 @@ template <bool WBM, class LDS> __device__ __forceinline__ void rollout_body(LDS&
     // single-shooting phases from here on (young phases behind a terminal knot, or the whole horizon): ONE call site, one copy of the code
     if (chain_first >= 0 && chain_first < nph && !ph[chain_first].shooting) rollout_chain<WBM>(L, ph, nph, chain_first, md, b, nslots, eps, opt, so, slot_base, fail, wr);
 }
-#define ROLL_PASS ph_, nph, slot_phase, slot_k, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, slot_list, nlist, unit_knots
+#define ROLL_PASS ph_, nph, slot_phase, slot_k, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, slot_list, nlist, unit_knots, plist, nprob
 __global__ void __launch_bounds__(64) ROLL_ATTR k_rollout(ROLL_ARGS) { __shared__ WbCore L; rollout_body<true>(L, ROLL_PASS); }
 // handles without whole-body phases (has_hkd): no whole-body code, 8 KB of LDS, no register cap
 // (measured on config 5, waves per SIMD rollout / LQ: none/none 111.6 k it/s, 3/- 117.7 k, 4/- 121.9 k, 4/5 122.1 k, 5/5 122.5 k; 8 KB of LDS allow five)
@@ -581,10 +583,12 @@ struct hsddp_handle {
     int *d_slot_phase = nullptr, *d_slot_k = nullptr, *d_fail = nullptr, *d_do_update = nullptr, *d_counters = nullptr, *d_success = nullptr;
     int *d_ls_list = nullptr, *d_commit_list = nullptr;      // problems still searching / needing a commit rollout, in the order the deciding kernel met them (compact grids for the quad kernel)
     int *d_qslots = nullptr, *d_oslots = nullptr; int nq = 0, n_other = 0, other_knots = 0;      // slots of the lane-quad kernel (whole-body running knots of phases with shooting nodes) / the rest
+    int* d_tslots = nullptr; int n_term = 0;      // terminal slots of the lane-quad path (k_rollout_quad_term; split_slots)
     bool ls_speculate = true;         // HSDDP_LS_SPECULATE=0: the full step of every line search is rolled out on its own (see hsddp_solve)
     int ls_chunk = MAXCAND;           // candidates per probe launch (HSDDP_LS_CHUNK): problems that accept inside a chunk skip the later chunks, at one more launch + decision step per chunk
     bool ls_probe_first = false;      // what the previous search of this handle suggests for the next one
     bool quad = true;                 // the lane-quad kernel takes its slots of every multiple-shooting rollout launch (HSDDP_QUAD=0: the one-wave programs everywhere)
+    bool quad_terminal = true;        // ... and the terminal knots split_slots gives it (HSDDP_QUAD_TERMINAL=0: every terminal knot on the one-wave program)
     int* h_counters = nullptr;        // pinned
     SlotArrays sp{}; int sp_cands = 0;       // slot partials of the candidates of a batched line-search launch: [sp_cands][batch][nslots] (allocated on first use)
     bool probe_ok = true;                    // every phase without shooting nodes is a whole-body phase (their chain keeps its state in LDS: probes need no trajectory store)
@@ -658,13 +662,19 @@ static hipError_t dev_replicate(void* base, size_t one, size_t count) {
     return hipSuccess;
 }
 
-// slots of a window by rollout program: the lane-quad kernel owns the running knots of whole-body phases with shooting nodes, the one-wave
-// programs everything else (terminal knots and their reset maps, single-rigid-body / kinodynamic knots, phases without shooting nodes)
-static void split_slots(const std::vector<PhaseDev>& ph, const std::vector<int>& sp, const std::vector<int>& sk, std::vector<int>& qs, std::vector<int>& os, int& other_knots) {
-    qs.clear(); os.clear(); other_knots = 0;
+// slots of a window by rollout program: the lane-quad path owns the running knots of whole-body phases with shooting nodes (qs, k_rollout_quad) and,
+// with quad_terminal, their terminal knots (ts, k_rollout_quad_term) when the reset map stays inside that family: no successor, or a whole-body
+// successor with a shooting node at knot 0.  The one-wave programs keep everything else (os): a terminal knot in front of a WB -> SRB projection or
+// of a phase without shooting nodes (whose chain the terminal wave walks), single-rigid-body / kinodynamic knots, phases without shooting nodes.
+static void split_slots(const std::vector<PhaseDev>& ph, const std::vector<int>& sp, const std::vector<int>& sk, bool quad_terminal, std::vector<int>& qs, std::vector<int>& ts,
+                        std::vector<int>& os, int& other_knots) {
+    qs.clear(); ts.clear(); os.clear(); other_knots = 0;
     for (size_t s = 0; s < sp.size(); s++) {
         const PhaseDev& P = ph[sp[s]];
-        if (P.model == HSDDP_MODEL_WB && P.shooting && sk[s] < P.h) qs.push_back((int)s);
+        const PhaseDev* N = (size_t)sp[s] + 1 < ph.size() ? &ph[sp[s] + 1] : nullptr;
+        const bool wbms = P.model == HSDDP_MODEL_WB && P.shooting;
+        if (wbms && sk[s] < P.h) qs.push_back((int)s);
+        else if (wbms && quad_terminal && (N == nullptr || (N->model == HSDDP_MODEL_WB && N->shooting))) ts.push_back((int)s);
         else { os.push_back((int)s); if (sk[s] < P.h) other_knots++; }
     }
 }
@@ -747,7 +757,7 @@ int hsddp_create_ex(hsddp_handle_t** out, int n_phases, const hsddp_phase_desc_t
     h->slots_cap = h->nslots + 16; h->nph_cap = n_phases + 8;      // slack: a receding-horizon update adds or drops a phase (one slot) now and then
     if (!rc) rc |= dalloc(h, &h->d_ph, h->nph_cap); if (!rc) rc |= dalloc(h, &h->d_ph_ss, h->nph_cap);
     if (!rc) rc |= dalloc(h, &h->d_slot_phase, h->slots_cap); if (!rc) rc |= dalloc(h, &h->d_slot_k, h->slots_cap);
-    if (!rc) rc |= dalloc(h, &h->d_qslots, h->slots_cap); if (!rc) rc |= dalloc(h, &h->d_oslots, h->slots_cap);
+    if (!rc) rc |= dalloc(h, &h->d_qslots, h->slots_cap); if (!rc) rc |= dalloc(h, &h->d_oslots, h->slots_cap); if (!rc) rc |= dalloc(h, &h->d_tslots, h->slots_cap);
     if (!rc) rc |= dalloc(h, &h->d_fail, B * MAXCAND); if (!rc) rc |= dalloc(h, &h->d_do_update, B); if (!rc) rc |= dalloc(h, &h->d_counters, 4); if (!rc) rc |= dalloc(h, &h->d_ls_list, B); if (!rc) rc |= dalloc(h, &h->d_commit_list, B); if (!rc) rc |= dalloc(h, &h->d_success, B);
     if (!rc) rc |= dalloc(h, &h->d_st, B); if (!rc) rc |= dalloc(h, &h->d_x0, B * h->ph[0].n); if (!rc) rc |= dalloc(h, &h->d_units, 8);
     if (!rc) rc |= dalloc(h, &h->sa.cost, B * h->slots_cap); if (!rc) rc |= dalloc(h, &h->sa.dsq, B * h->slots_cap);
@@ -761,11 +771,13 @@ int hsddp_create_ex(hsddp_handle_t** out, int n_phases, const hsddp_phase_desc_t
     CREATE_CK(hipMemcpy(h->d_slot_phase, sp.data(), sp.size() * 4, hipMemcpyHostToDevice));
     CREATE_CK(hipMemcpy(h->d_slot_k, sk.data(), sk.size() * 4, hipMemcpyHostToDevice));
     {
-        std::vector<int> qs, os; split_slots(h->ph, sp, sk, qs, os, h->other_knots);
-        h->nq = (int)qs.size(); h->n_other = (int)os.size();
-        if (h->nq) CREATE_CK(hipMemcpy(h->d_qslots, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
-        if (h->n_other) CREATE_CK(hipMemcpy(h->d_oslots, os.data(), os.size() * 4, hipMemcpyHostToDevice));
         const char* e = getenv("HSDDP_QUAD"); h->quad = !(e && e[0] == '0');
+        const char* e1 = getenv("HSDDP_QUAD_TERMINAL"); h->quad_terminal = !(e1 && e1[0] == '0');
+        std::vector<int> qs, ts, os; split_slots(h->ph, sp, sk, h->quad_terminal, qs, ts, os, h->other_knots);
+        h->nq = (int)qs.size(); h->n_term = (int)ts.size(); h->n_other = (int)os.size();
+        if (h->nq) CREATE_CK(hipMemcpy(h->d_qslots, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
+        if (h->n_term) CREATE_CK(hipMemcpy(h->d_tslots, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
+        if (h->n_other) CREATE_CK(hipMemcpy(h->d_oslots, os.data(), os.size() * 4, hipMemcpyHostToDevice));
         const char* e2 = getenv("HSDDP_LS_SPECULATE"); h->ls_speculate = !(e2 && e2[0] == '0');
         const char* e3 = getenv("HSDDP_LS_CHUNK"); if (e3 && atoi(e3) >= 1) h->ls_chunk = std::min(atoi(e3), MAXCAND);
     }
@@ -854,10 +866,11 @@ int hsddp_reconfigure(hsddp_handle_t* h, int n_phases, const hsddp_phase_desc_t*
         HIPCK(hipMemcpyAsync(h->d_ph_ss, ss.data(), sizeof(PhaseDev) * n_phases, hipMemcpyHostToDevice, h->stream));
         HIPCK(hipMemcpyAsync(h->d_slot_phase, sp.data(), sp.size() * 4, hipMemcpyHostToDevice, h->stream));
         HIPCK(hipMemcpyAsync(h->d_slot_k, sk.data(), sk.size() * 4, hipMemcpyHostToDevice, h->stream));
-        std::vector<int> qs, os; int other_knots = 0; split_slots(np, sp, sk, qs, os, other_knots);
+        std::vector<int> qs, ts, os; int other_knots = 0; split_slots(np, sp, sk, h->quad_terminal, qs, ts, os, other_knots);
         if (!qs.empty()) HIPCK(hipMemcpyAsync(h->d_qslots, qs.data(), qs.size() * 4, hipMemcpyHostToDevice, h->stream));
+        if (!ts.empty()) HIPCK(hipMemcpyAsync(h->d_tslots, ts.data(), ts.size() * 4, hipMemcpyHostToDevice, h->stream));
         if (!os.empty()) HIPCK(hipMemcpyAsync(h->d_oslots, os.data(), os.size() * 4, hipMemcpyHostToDevice, h->stream));
-        h->nq = (int)qs.size(); h->n_other = (int)os.size(); h->other_knots = other_knots;
+        h->nq = (int)qs.size(); h->n_term = (int)ts.size(); h->n_other = (int)os.size(); h->other_knots = other_knots;
         HIPCK(hipStreamSynchronize(h->stream));      // (the host vectors above are the copy sources; the old window is no longer read after this point)
         // 4. the new window becomes the handle's
         if (!h->gen_allocs.empty()) { for (void* p : h->gen_allocs) hipFree(p); h->gen_allocs.clear(); }      // storage of hsddp_create: first tick only
@@ -918,17 +931,20 @@ static HistDev hist_of(hsddp_handle* h) { return HistDev{h->d_hist, h->hist_cap}
 static void launch_rollout_list(hsddp_handle* h, const EpsList& el, const SlotArrays& sa, const OptDev& o, int mask, const char* name, int unit = UNIT_ROLLOUT, const int* plist = nullptr, int nlist = 0) {
     Timed t(h, name);
     hipMemsetAsync(h->d_fail, 0, (size_t)h->batch * el.n * sizeof(int), h->stream);
-    if (h->quad && o.MS && h->nq > 0) {      // whole-body running knots on lane quads, the rest (terminal knots, single-rigid-body tail) on the one-wave programs
-        const int nbg = ((plist ? nlist : h->batch) + 15) / 16;
+    if (h->quad && o.MS && h->nq > 0) {      // whole-body running knots and the terminal knots behind them on lane quads, the rest on the one-wave programs
+        const int nprob = plist ? nlist : h->batch, nbg = (nprob + 15) / 16;
         launch_k_rollout_quad((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
                               h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist);
-        if (h->n_other > 0)
-            hipLaunchKernelGGL(k_rollout, dim3((unsigned)((size_t)el.n * h->batch * h->n_other)), dim3(64), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
-                               h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots);
+        if (h->n_term > 0)
+            launch_k_rollout_quad_term((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
+                                       plist, nlist);
+        if (h->n_other > 0 && nprob > 0)      // (a window whose every slot is on lane quads launches no one-wave kernel at all)
+            hipLaunchKernelGGL(k_rollout, dim3((unsigned)((size_t)el.n * nprob * h->n_other)), dim3(64), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
+                               h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob);
         return;
     }
     hipLaunchKernelGGL(h->has_hkd ? k_rollout_hkd : k_rollout, dim3((unsigned)((size_t)el.n * h->batch * h->nslots)), dim3(64), 0, h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
-                       h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph);
+                       h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph, (const int*)nullptr, h->batch);
 }
 static void launch_rollout(hsddp_handle* h, double eps, const OptDev& o, int mask, bool eps_from_state = false, const int* plist = nullptr, int nlist = 0) {
     EpsList el{}; el.e[0] = eps; el.n = 1; el.writer = 0; el.from_state = eps_from_state ? 1 : 0;

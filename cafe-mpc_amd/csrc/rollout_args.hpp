@@ -26,3 +26,6 @@ struct EpsList { double e[MAXCAND]; int n, writer, from_state; };
 void launch_k_rollout_quad(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, const int* slot_phase, const int* slot_k, const int* qslots, int nq, int nslots, int batch,
                            hs::ModelDev md, EpsList el, hs::OptDev opt, const double* x0, SlotArrays sa, const hs::ProbState* st, int mask, int* fail, unsigned long long* units,
                            const int* plist, int nlist);
+// k_rollout_quad_term (hsddp_quad.hip): the terminal knots the quad path owns, one workgroup per unit (terminal slot of the list x group of sixteen problems)
+void launch_k_rollout_quad_term(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* tslots, int nslots, int batch,
+                                hs::ModelDev md, EpsList el, hs::OptDev opt, SlotArrays sa, const hs::ProbState* st, int mask, const int* plist, int nlist);

@@ -59,12 +59,15 @@ fetch, nf = counter_by_kernel(pre + "pmc_fetch", "FETCH_SIZE")
 write, nw = counter_by_kernel(pre + "pmc_write", "WRITE_SIZE")
 bl = last_json_line(f"{out}/{pre}pmc_fetch_bench.json") or {}
 units = (bl.get("roofline") or {}).get("kernel_units_knots", {})
-# The rollout family = k_rollout_quad (whole-body running knots on lane quads) + k_rollout (terminal knots, single-rigid-body tail), ordinary
-# rollouts and the probe launches of the batched line search alike: bytes of both kernels over the knots (x candidates) both families processed
+# The rollout family = k_rollout_quad (whole-body running knots on lane quads) + k_rollout_quad_term (their terminal knots) + k_rollout (the
+# one-wave programs: single-rigid-body tail, terminal knots in front of it), ordinary rollouts and the probe launches of the batched line search
+# alike: bytes of the three kernels over the knots (x candidates) the family processed; launches = those of k_rollout_quad
 for acc in (fetch, write):
-    if "k_rollout_quad" in acc:
-        acc["k_rollout"] = acc.get("k_rollout", 0.0) + acc.pop("k_rollout_quad")
+    for q in ("k_rollout_quad", "k_rollout_quad_term"):
+        if q in acc:
+            acc["k_rollout"] = acc.get("k_rollout", 0.0) + acc.pop(q)
 for cnt in (nf, nw):
+    cnt.pop("k_rollout_quad_term", None)
     if "k_rollout_quad" in cnt:
         cnt["k_rollout"] = cnt.get("k_rollout", 0) + cnt.pop("k_rollout_quad")
 units_by_kernel = {"k_rollout": units.get("k_rollout", 0) + units.get("k_ls_probe", 0), "k_lq": units.get("k_lq", 0), "k_sweep": units.get("k_sweep", 0), "k_sweep32": units.get("k_sweep", 0),
