@@ -301,6 +301,26 @@ def bind_substep(lib):
     return lib
 
 
+# include/hsddp_contact.h: unilateral ground contact in a simulation object (libhsddp_hip.so only).  A list and a binder of their own, as above.
+CONTACT_EXPORTS = ["hsddp_contact_set", "hsddp_contact_get_params", "hsddp_contact_get"]
+# hsddp_contact_row_t
+CONTACT_ROW_DTYPE = np.dtype([("first_release", "<i4"), ("n_release", "<i4"), ("n_land", "<i4"), ("n_free", "<i4"), ("free_final", "<i4"), ("pad", "<i4"),
+                              ("max_lift", "<f8")])
+
+
+def bind_contact(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_contact.h (and of hsddp_sim.h, which they work on).  Raises if the library lacks any."""
+    missing = [s for s in CONTACT_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the contact entry points {missing}")
+    bind_sim(lib)
+    H = C.c_void_p
+    lib.hsddp_contact_set.argtypes = [H, C.c_int, C.c_double, C.c_double]
+    lib.hsddp_contact_get_params.argtypes = [H, IP, DP, DP]
+    lib.hsddp_contact_get.argtypes = [H, C.c_int, C.c_int, C.c_void_p]
+    return lib
+
+
 # include/hsddp_episode.h: batched closed-loop MPC episodes (libhsddp_hip.so only)
 EPISODE_EXPORTS = ["hsddp_episode_create", "hsddp_episode_destroy", "hsddp_episode_reset", "hsddp_episode_advance", "hsddp_episode_get_rows",
                    "hsddp_episode_get_log", "hsddp_episode_device_state", "hsddp_episode_sim", "hsddp_episode_status"]
@@ -593,7 +613,7 @@ class Solver:
                  "get_references")
         return out
 
-    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1):
+    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None):
         """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)
         over the first n_steps whole-body control knots (include/hsddp_sim.h): dict with rows (structured array [batch, R] of dev_q, dev_v,
         min_height, max_torque, first_bad), x_final [batch, R, 36] and, with keep_traj, X [batch, R, n_steps + 1, 36] and U [batch, R, n_steps, 12].
@@ -601,9 +621,11 @@ class Solver:
         which also returns extra (structured array [batch, R] of first_fall, n_sat).  grf = (mu, fz_min): contact-force records
         (include/hsddp_grf.h), grf (structured array [batch, R] of min_fz, min_cone, max_fz, first_slip, n_slip) and, with keep_traj, Y
         [batch, R, n_steps, 12].  substeps = S > 1: every control knot is S forward-Euler steps of dt / S under the knot's torque
-        (include/hsddp_substep.h); shapes and meanings stay, n_slip counts (foot, substep) pairs."""
+        (include/hsddp_substep.h); shapes and meanings stay, n_slip counts (foot, substep) pairs.  contact = (fz_rel, z_ground):
+        unilateral ground contact (include/hsddp_contact.h), which also returns contact (structured array [batch, R] of first_release, n_release,
+        n_land, n_free, free_final, max_lift)."""
         from . import sim
-        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps)
+        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps, contact=contact)
 
     def episode(self, n_exec, max_ticks, keep_log=False):
         """An episode.Episode on this solver (include/hsddp_episode.h): batched closed-loop MPC ticks with the simulated state handed to the next

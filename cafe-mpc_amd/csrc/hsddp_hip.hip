@@ -21,6 +21,7 @@
 #include "hsddp_sim.h"
 #include "hsddp_grf.h"
 #include "hsddp_substep.h"
+#include "hsddp_contact.h"
 #include "hsddp_mc.h"
 #include "hsddp_episode.h"
 #include "hs_types.hpp"
@@ -1673,6 +1674,16 @@ void wbs_sub_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const
 #else
 #include "hsddp_sub.hip"
 #endif
+// The kernels with unilateral ground contact and their launcher (hsddp_contact.h): hsddp_uni.hip, a translation unit of its own for the same reason
+// (-DHS_UNI_SEPARATE here).
+#ifdef HS_UNI_SEPARATE
+namespace hs {
+void wbs_uni_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
+                    double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un);
+}
+#else
+#include "hsddp_uni.hip"
+#endif
 struct hsddp_sim {
     hsddp_handle* h = nullptr;
     int R = 0, n_steps = 0, keep = 0, gen = 0;
@@ -1687,12 +1698,20 @@ struct hsddp_sim {
     bool grf_on = false, last_grf = false;
     // sub-stepped integration (hsddp_substep.h): what later runs use; the trip count on the device, allocated by the first hsddp_substep_set above 1
     int substeps = 1; WbsSubArgs* d_sub = nullptr;
+    // unilateral ground contact (hsddp_contact.h): everything below is allocated by the first hsddp_contact_set that switches the rule on.
+    // uni_on: what later runs do; last_uni: what the last run did.  d_uni_grf / d_uni_grows: thresholds and rows of the records the walk always keeps,
+    // used while hsddp_grf_set has them off.  d_uni_F: the free flags an episode carries from tick to tick (uni_keep, set by hsddp_episode_create;
+    // uni_hold: the end_reason of the episode's rows, stride in ints)
+    bool uni_on = false, last_uni = false, uni_keep = false;
+    double uni_fz_rel = 0.0, uni_z_ground = 0.0;
+    WbsUniArgs* d_uni = nullptr; double *d_uni_rows = nullptr, *d_uni_F = nullptr, *d_uni_grows = nullptr; WbsGrfArgs* d_uni_grf = nullptr;
+    const int* uni_hold = nullptr; int uni_hold_stride = 0;
 };
 static void sim_free(hsddp_sim* s) {
     if (!s) return;
     hipSetDevice(s->h->device);
     if (s->h->stream) hipStreamSynchronize(s->h->stream);
-    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf, s->d_sub};
+    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf, s->d_sub, s->d_uni, s->d_uni_rows, s->d_uni_F, s->d_uni_grows, s->d_uni_grf};
     for (void* q : p) if (q) hipFree(q);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -1758,7 +1777,11 @@ static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, b
     const size_t total = (size_t)h->batch * s->R;
     if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
     HIPCK(hipEventRecord(s->ev0, h->stream));
-    if (s->substeps > 1) {
+    if (s->uni_on) {      // (for every S: the walk with the rule carries the sub-step loop and the records)
+        wbs_uni_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
+                       s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : (const WbsGrfArgs*)s->d_uni_grf,
+                       s->d_sub, s->d_uni);
+    } else if (s->substeps > 1) {
         // (the launcher leaves the runtime's error state alone: a failed launch is caught by the hipGetLastError below, as for the other kernels)
         wbs_sub_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
                        s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : nullptr, s->d_sub);
@@ -1780,7 +1803,7 @@ static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, b
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(s->ev1, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    s->timed = true; s->last_grf = s->grf_on;
+    s->timed = true; s->last_grf = s->grf_on; s->last_uni = s->uni_on;
     return HSDDP_OK;
 }
 
@@ -1914,6 +1937,59 @@ int hsddp_substep_get(hsddp_sim_t* s, int* substeps) {
     return HSDDP_OK;
 }
 
+int hsddp_contact_set(hsddp_sim_t* s, int on, double fz_rel, double z_ground) {
+    if (!s || !std::isfinite(fz_rel) || !std::isfinite(z_ground)) return HSDDP_EINVAL;
+    if (!on) { s->uni_on = false; return HSDDP_OK; }      // later runs launch the kernels without the rule; the buffers and the thresholds are kept
+    hsddp_handle* h = s->h;
+    if (h->f32) return HSDDP_ENOTSUP;
+    HIPCK(hipSetDevice(h->device));
+    const size_t total = (size_t)h->batch * s->R;
+    // (as GRF_CK of hsddp_grf_set: an allocation that fails returns its code at once, what was made before it is kept, and the rule stays off)
+#define UNI_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
+    if (!s->d_uni) UNI_CK(hipMalloc((void**)&s->d_uni, sizeof(WbsUniArgs)));
+    if (!s->d_uni_rows) UNI_CK(hipMalloc((void**)&s->d_uni_rows, total * SIM_UNI_ROW * 8));
+    if (!s->d_uni_grows) UNI_CK(hipMalloc((void**)&s->d_uni_grows, total * SIM_GRF_ROW * 8));
+    if (!s->d_uni_grf) {
+        UNI_CK(hipMalloc((void**)&s->d_uni_grf, sizeof(WbsGrfArgs)));
+        WbsGrfArgs g;
+        g.mu = 1.0; g.fz_min = 0.0; g.rows = s->d_uni_grows; g.Y = nullptr;      // (nobody reads these records: hsddp_grf_get refuses while the records are off)
+        HIPCK(hipMemcpyAsync(s->d_uni_grf, &g, sizeof(g), hipMemcpyHostToDevice, h->stream));
+    }
+    if (s->uni_keep && !s->d_uni_F) { UNI_CK(hipMalloc((void**)&s->d_uni_F, total * 4 * 8)); HIPCK(hipMemsetAsync(s->d_uni_F, 0, total * 4 * 8, h->stream)); }
+    if (!s->d_sub) {      // the walk reads its trip count from here for S = 1 too; from now on hsddp_substep_set keeps it current
+        UNI_CK(hipMalloc((void**)&s->d_sub, sizeof(WbsSubArgs)));
+        WbsSubArgs b;
+        b.substeps = s->substeps; b.pad = 0;
+        HIPCK(hipMemcpyAsync(s->d_sub, &b, sizeof(b), hipMemcpyHostToDevice, h->stream));
+    }
+#undef UNI_CK
+    WbsUniArgs a;
+    a.fz_rel = fz_rel; a.z_ground = z_ground; a.rows = s->d_uni_rows; a.F = s->d_uni_F; a.hold = s->uni_hold; a.hold_stride = s->uni_hold_stride; a.pad = 0;
+    HIPCK(hipMemcpyAsync(s->d_uni, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));      // (pageable sources: staged before the calls return; the runs are on this stream)
+    s->uni_on = true; s->uni_fz_rel = fz_rel; s->uni_z_ground = z_ground;
+    return HSDDP_OK;
+}
+
+int hsddp_contact_get_params(hsddp_sim_t* s, int* on, double* fz_rel, double* z_ground) {
+    if (!s || !on || !fz_rel || !z_ground) return HSDDP_EINVAL;
+    *on = s->uni_on ? 1 : 0; *fz_rel = s->uni_fz_rel; *z_ground = s->uni_z_ground;
+    return HSDDP_OK;
+}
+
+int hsddp_contact_get(hsddp_sim_t* s, int b0, int nb, hsddp_contact_row_t* rows) {
+    if (!sim_range_ok(s, b0, nb) || !rows || !s->last_uni) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(s->h->device));
+    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R;
+    std::vector<double> r(cnt * SIM_UNI_ROW);
+    HIPCK(hipMemcpy(r.data(), s->d_uni_rows + off * SIM_UNI_ROW, r.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < cnt; i++) {
+        const double* q = &r[i * SIM_UNI_ROW];
+        rows[i].first_release = (int)q[0]; rows[i].n_release = (int)q[1]; rows[i].n_land = (int)q[2]; rows[i].n_free = (int)q[3]; rows[i].free_final = (int)q[4]; rows[i].pad = 0;
+        rows[i].max_lift = q[5];
+    }
+    return HSDDP_OK;
+}
+
 const double* hsddp_sim_device_final(hsddp_sim_t* s) { return s ? s->d_final : nullptr; }
 
 int hsddp_sim_get_kernel_time_ms(hsddp_sim_t* s, float* ms) {
@@ -1980,6 +2056,7 @@ int hsddp_episode_create(hsddp_handle_t* h, int n_exec, int max_ticks, int keep_
         EPI_CK(hipMemset(e->d_X, 0, B * (steps + 1) * 36 * 8)); EPI_CK(hipMemset(e->d_U, 0, B * steps * 12 * 8)); EPI_CK(hipMemset(e->d_Y, 0, B * steps * 12 * 8));
     }
     EPI_CK(hipMemset(e->d_state, 0, B * 36 * 8));
+    s->uni_keep = true; s->uni_hold = &e->d_rows[0].end_reason; s->uni_hold_stride = (int)(sizeof(EpiRow) / sizeof(int));      // (hsddp_contact.h: F lives across ticks, a frozen robot keeps its own)
     EPI_CK(hipMemcpy(e->d_rows, e->row0.data(), B * sizeof(EpiRow), hipMemcpyHostToDevice));
 #undef EPI_CK
     *out = e; return HSDDP_OK;
@@ -1999,6 +2076,7 @@ int hsddp_episode_reset(hsddp_episode_t* e, const double* x0, int src_device) {
         HIPCK(hipMemsetAsync(e->d_X, 0, B * (steps + 1) * 36 * 8, h->stream)); HIPCK(hipMemsetAsync(e->d_U, 0, B * steps * 12 * 8, h->stream));
         HIPCK(hipMemsetAsync(e->d_Y, 0, B * steps * 12 * 8, h->stream));
     }
+    if (e->sim->d_uni_F) HIPCK(hipMemsetAsync(e->sim->d_uni_F, 0, B * 4 * 8, h->stream));      // (hsddp_contact.h) every foot attached again
     HIPCK(hipStreamSynchronize(h->stream));
     e->tick = 0; e->n_impacts = 0; e->started = true;
     return HSDDP_OK;

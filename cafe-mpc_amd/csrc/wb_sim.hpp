@@ -60,6 +60,14 @@ template <class Q, class S> HD S wbs_qmax(const S& a) { return -Q::vmin(-a); }  
 // as a defaulted pointer argument it moved the register allocation of every caller (k_sim_quad: 24 -> 0 B of scratch - welcome, but not this
 // change's business, which has to leave the existing kernels what they are).  The store keeps its null test although no caller passes null: with it
 // the three kernels that take the force compile to 0 / 76 / 0 B of scratch per lane, without it to 40 / 148 / 44 (make resources).
+// Unilateral contact (include/hsddp_contact.h): the one pack element of a solve whose contact flag is the LANE's own.  cl: 1 if the lane's foot is in
+// the contact set (cmask is not read); the solve hands back the force as above, and the height and vertical velocity of the lane's foot point at the
+// state it was given (qb[2] + rW.z, fvel.z - computed for the bias pass anyway).  The calls without it instantiate what they instantiated before.
+template <class S> struct WbsUniIO { S cl, pz, wz; V3<S> lam; };
+template <class T> struct wbs_is_uni_io { static constexpr bool value = false; };
+template <class S> struct wbs_is_uni_io<WbsUniIO<S>> { static constexpr bool value = true; };
+template <class Q, class S, class... LO> HD S wbs_lane_flag(int cmask, LO*...) { return Q::legc((cmask & 1) ? 1.0 : 0.0, (cmask & 2) ? 1.0 : 0.0, (cmask & 4) ? 1.0 : 0.0, (cmask & 8) ? 1.0 : 0.0); }
+template <class Q, class S> HD S wbs_lane_flag(int, WbsUniIO<S>* io) { return io->cl; }
 template <class Q, class S = typename Q::S, class... LO>
 HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double damping, double bg_alpha, const S (&qb)[6], const S (&vb)[6], const S (&ql)[3],
                              const S (&vl_)[3], const S (&ul)[3], S (&out_b)[6], V3<S>& out_l, LO*... lam_out) {
@@ -207,7 +215,7 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         base_walk(T, fb, nb, hb);
     }
     // ---- foot Jacobian of the leg, world axes: Ja (3 x 3 over abad, hip, knee), Jb (3 x 6 over the base joints) - geometric form axis x arm
-    const S cl = Q::legc((cmask & 1) ? 1.0 : 0.0, (cmask & 2) ? 1.0 : 0.0, (cmask & 4) ? 1.0 : 0.0, (cmask & 8) ? 1.0 : 0.0);      // contact flag of the lane's leg
+    const S cl = wbs_lane_flag<Q, S>(cmask, lam_out...);      // contact flag of the lane's leg
     M33<S> Ja; S Jb[3][6];
     {
         auto b2w = [&](const V3<S>& w) { return rot<2>(T.c3, T.s3, rot<1>(T.c4, T.s4, rot<0>(T.c5, T.s5, w))); };
@@ -351,7 +359,8 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         rhs = {pick(lam0.x, lam1.x, lam2.x, lam3.x), pick(lam0.y, lam1.y, lam2.y, lam3.y), pick(lam0.z, lam1.z, lam2.z, lam3.z)};
     }
     const V3<S> lam = scale(cl, rhs);      // contact force of the lane's foot (world axes); zero for a swing leg
-    if constexpr (sizeof...(LO) > 0) { ((lam_out != nullptr ? (void)(*lam_out = lam) : (void)0), ...); }
+    if constexpr ((wbs_is_uni_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z), ...); }
+    else if constexpr (sizeof...(LO) > 0) { ((lam_out != nullptr ? (void)(*lam_out = lam) : (void)0), ...); }
     // qdd = L^-T (y + X lam): base part replicated, leg part in the lane
     S qddb[6]; V3<S> qddl;
     {
@@ -391,8 +400,8 @@ struct WbsMcArgs {
 // NOISE 0: the walk of a run whose three sigmas are zero, compiled without the generator.  Measured (MI355X, config 3 x 16 samples x 200 steps, plain
 // run 9.88 ms): with the generator compiled in and branched over, a run with only u_max set took 11.74 ms - the register allocation of the whole
 // loop pays for code that does not run; without it 9.83 ms.  So the host picks the instantiation, and every other switch stays a run-time branch.
-struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0; };
-template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0; const WbsMcArgs* a; };
+struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0, UNI = 0; };
+template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0, UNI = 0; const WbsMcArgs* a; };
 constexpr int SIM_PARK_MC = SIM_PARK + 2;       // ... and n_sat, first_fall
 // Contact-force records (include/hsddp_grf.h): GRF 1 in the policy.  The walk takes the lane's multiplier of every mode-0 solve, keeps five running
 // values per lane (lane = leg) - smallest / largest stance fz, smallest cone margin, first violating step, violations - and joins them over the
@@ -405,8 +414,8 @@ struct WbsGrfArgs {
 constexpr int SIM_GRF_ROW = 5;     // min_fz | min_cone | max_fz | first_slip | n_slip
 constexpr int SIM_GRF_PARK = 5;    // the lane's running values, parked behind the others
 constexpr double SIM_GRF_NONE = 1e18;      // first_slip of a lane without a violation while the walk runs: above every step index
-struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0; const WbsGrfArgs* gr; };
-template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
+struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0, UNI = 0; const WbsGrfArgs* gr; };
+template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0, UNI = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
 // Sub-stepped integration (include/hsddp_substep.h): SUB 1 in the policy.  A control knot is S forward-Euler steps of dt / S under the knot's torque
 // (zero-order hold): the feedback, the noise and every record of the state stay once per control step, the contact solve, the divergence test and
 // the force records run once per substep.  S is a run-time trip count read from device memory through a laundered pointer, as the other switches
@@ -414,10 +423,28 @@ template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOI
 // constexpr (D::SUB)` below is this code, and the six policies above compile to what they compiled to without it.
 struct WbsSubArgs { int substeps, pad; };      // 2 .. 64 (the host launches the kernels above for 1)
 constexpr int SIM_SUB_PARK = 3;
-struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1; const WbsSubArgs* sb; };
-template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1; const WbsMcArgs* a; const WbsSubArgs* sb; };
-struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
-template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1, UNI = 0; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1, UNI = 0; const WbsMcArgs* a; const WbsSubArgs* sb; };
+struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+// Unilateral ground contact (include/hsddp_contact.h): UNI 1 in the policy, always with the records and the sub-step loop (GRF 1, SUB 1; S = 1 too).
+// The lane (= leg) carries F, 1 if its foot is a scheduled stance foot that is FREE, and the contact flag of every solve is the lane's own: attached =
+// scheduled and not free.  The trip loop of a control step becomes a small state machine around the ONE call site of the solve -
+//     substep:  solve -> [landing impact on T, solve] -> [release the foot that pulls hardest, solve]* -> records, Euler step
+// - that advances on wave-uniform decisions (a ballot over the wave): a trip is repeated if ANY quad of the wave needs it, and a quad that does not
+// repeats the solve with its own unchanged set and state, which gives it the same numbers (the impact trip is not applied to it: a select).  F, the
+// landing set T, the four counters and max_lift are parked with the rest.  Every `if constexpr (D::UNI)` below is this code, and the twelve policies
+// above compile to what they compiled to without it.
+struct WbsUniArgs {
+    double fz_rel, z_ground;      // a foot whose normal force falls below fz_rel is released; height of the flat ground, world z
+    double* rows;                 // [B R][SIM_UNI_ROW]
+    double* F;                    // [B R][4] the free flags carried from run to run (episodes), loaded at the head and stored at the end; null: F starts empty
+    const int* hold; int hold_stride, pad;      // (episodes) hold[g hold_stride] != 0: sample g is frozen and keeps the F it had; null: every sample stores
+};
+constexpr int SIM_UNI_ROW = 6;      // first_release | n_release | n_land | n_free | free_final | max_lift
+constexpr int SIM_UNI_PARK = 7;     // F, T, first_release, n_release, n_land, n_free, max_lift of the lane, parked behind everything else
+struct WbsUni { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
+template <int NOISE_> struct WbsMcUni { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
 
 // The generator (sim.mc_normals is its definition): draw(n) is output n >= 1 of SplitMix64(seed), whose state is the counter seed + n G; the normal of
 // coordinate c of (global problem, sample, step) is Box-Muller on draws n0 + 1 and n0 + 2, n0 = 2 (((problem 65536 + sample) 65536 + step) 48 + c).
@@ -450,6 +477,8 @@ inline void wbs_mc_normal3(unsigned long long seed, unsigned long long base, con
 inline const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { return p; }
 inline const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { return p; }
 inline const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { return p; }
+inline const WbsUniArgs* wbs_uni_fresh(const WbsUniArgs* p) { return p; }
+inline bool wbs_any(const Q4& f) { return f.v[0] > 0.5 || f.v[1] > 0.5 || f.v[2] > 0.5 || f.v[3] > 0.5; }      // (host: the quad is the whole wave)
 #else
 HD void wbs_mc_normal3(unsigned long long seed, unsigned long long base, const double& c, double (&z)[3]) { wbs_mc_normal3_lane(seed, base, (int)c, z); }
 // the switches are read again at every step from a pointer the compiler cannot see through: held in scalar registers across the contact solve
@@ -457,6 +486,9 @@ HD void wbs_mc_normal3(unsigned long long seed, unsigned long long base, const d
 HD const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { asm volatile("" : "+s"(p)); return p; }
+HD const WbsUniArgs* wbs_uni_fresh(const WbsUniArgs* p) { asm volatile("" : "+s"(p)); return p; }
+// true if the 0 / 1 flag is set in ANY active lane of the wave: a ballot, so the answer is wave-uniform and the branch on it a scalar one
+HD bool wbs_any(double f) { return __builtin_amdgcn_ballot_w64(f > 0.5) != 0ull; }
 #endif
 
 template <class Q, class D = WbsPlain>
@@ -473,6 +505,10 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
     S dq = zero, dv = zero, umax = zero, hmin = qb[2];      // (per-lane maxima over the base and the lane's leg: joined over the quad at the end)
     // (records only) of the lane's foot while it is a stance foot: smallest / largest fz, smallest cone margin, first violating step, violations
     S gfmin = S(HUGE_VAL), gcmin = S(HUGE_VAL), gfmax = S(-HUGE_VAL), gfirst = S(SIM_GRF_NONE), gslip = zero;
+    // (unilateral contact only) F and the landing set T of the lane's foot, 0 / 1; first control step with a release; releases, landings and free
+    // (foot, substep) pairs of the lane's foot; largest height of the foot above the ground at a landing test
+    S fr = zero, tl = zero, ufirst = S(-1.0), nrel = zero, nland = zero, nfree = zero, mlift = S(-HUGE_VAL);
+    if constexpr (D::UNI) { const WbsUniArgs ua = *wbs_uni_fresh(dist.un); if (ua.F != nullptr) fr = Q::ld(ua.F, g * 4, 1); }
     // deviation of the state from row `kx` of a phase's Xbar: base part replicated, the lane's leg
     auto deviation = [&](PhaseC& P, size_t kx, S (&eb)[6], S (&wb)[6], S (&el)[3], S (&wl)[3]) {
         _Pragma("unroll") for (int i = 0; i < 6; i++) { eb[i] = qb[i] - Q::ld(P.Xbar, kx + i, 0); wb[i] = vb[i] - Q::ld(P.Xbar, kx + 18 + i, 0); }
@@ -503,14 +539,17 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                     &dq, &dv, &umax, &hmin, &alive, &first_bad};
         constexpr int G0 = D::MC ? SIM_PARK_MC : SIM_PARK;      // (records) the five running values behind the others
         constexpr int U0 = G0 + (D::GRF ? SIM_GRF_PARK : 0);    // (substeps) the torques behind those
+        constexpr int N0 = U0 + (D::SUB ? SIM_SUB_PARK : 0);    // (unilateral contact) F, T, the counters and max_lift behind those
         if (out) {
             _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; if constexpr (D::MC) { c[64 * 24] = nsat; c[64 * 25] = ffall; }
             if constexpr (D::GRF) { c[64 * G0] = gfmin; c[64 * (G0 + 1)] = gcmin; c[64 * (G0 + 2)] = gfmax; c[64 * (G0 + 3)] = gfirst; c[64 * (G0 + 4)] = gslip; }
             if constexpr (D::SUB) { c[64 * U0] = u3[0]; c[64 * (U0 + 1)] = u3[1]; c[64 * (U0 + 2)] = u3[2]; }
+            if constexpr (D::UNI) { c[64 * N0] = fr; c[64 * (N0 + 1)] = tl; c[64 * (N0 + 2)] = ufirst; c[64 * (N0 + 3)] = nrel; c[64 * (N0 + 4)] = nland; c[64 * (N0 + 5)] = nfree; c[64 * (N0 + 6)] = mlift; }
         } else {
             asm volatile("" ::: "memory"); _Pragma("unroll") for (int i = 0; i < 24; i++) *v[i] = c[64 * i]; if constexpr (D::MC) { nsat = c[64 * 24]; ffall = c[64 * 25]; }
             if constexpr (D::GRF) { gfmin = c[64 * G0]; gcmin = c[64 * (G0 + 1)]; gfmax = c[64 * (G0 + 2)]; gfirst = c[64 * (G0 + 3)]; gslip = c[64 * (G0 + 4)]; }
             if constexpr (D::SUB) { u3[0] = c[64 * U0]; u3[1] = c[64 * (U0 + 1)]; u3[2] = c[64 * (U0 + 2)]; }
+            if constexpr (D::UNI) { fr = c[64 * N0]; tl = c[64 * (N0 + 1)]; ufirst = c[64 * (N0 + 2)]; nrel = c[64 * (N0 + 3)]; nland = c[64 * (N0 + 4)]; nfree = c[64 * (N0 + 5)]; mlift = c[64 * (N0 + 6)]; }
         }
     };
 #endif
@@ -614,56 +653,136 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         const int cm_dyn = (P.contact[0] > 0 ? 1 : 0) | (P.contact[1] > 0 ? 2 : 0) | (P.contact[2] > 0 ? 4 : 0) | (P.contact[3] > 0 ? 8 : 0);
         const int cm_td = (P.td[0] ? 1 : 0) | (P.td[1] ? 2 : 0) | (P.td[2] ? 4 : 0) | (P.td[3] ? 8 : 0);
         const double dt = P.dt, alpha = P.bg_alpha;
-        int last = reset;
-        if constexpr (D::SUB) last = reset + wbs_uniform(wbs_sub_fresh(dist.sb)->substeps) - 1;
-        _Pragma("nounroll")
-        for (int trip = 0; trip <= last; trip++) {
-            int mode = trip;
-            if constexpr (D::SUB) mode = (reset != 0 && trip == last) ? 1 : 0;
-            S ob[6]; V3<S> ol;
-            park(true, ul);
-            if constexpr (D::GRF) {
-                V3<S> lam;
-                wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol, &lam);
+        if constexpr (D::UNI) {
+            // ---- unilateral contact: the state machine of the head of the file.  stg: 0 the first solve of a substep (the landing test follows it), 1 the
+            // landing impact, 2 a solve again, 3 the scheduled reset map.  stg and sub are wave-uniform: they change on ballots only.
+            auto flag = [](int m) { return Q::legc((m & 1) ? 1.0 : 0.0, (m & 2) ? 1.0 : 0.0, (m & 4) ? 1.0 : 0.0, (m & 8) ? 1.0 : 0.0); };      // the lane's bit of a wave-uniform mask, formed at every use
+            fr = Q::sel(Q::gt(alive, S(0.5)), fr * flag(cm_dyn), fr);      // F <- F n C: does something at a phase change only
+            int sub = 0, stg = 0;
+            _Pragma("nounroll")
+            for (;;) {
+                const int mode = (stg == 1 || stg == 3) ? 1 : 0;
+                WbsUniIO<S> io;
+                io.cl = stg == 1 ? tl : stg == 3 ? flag(cm_td) : flag(cm_dyn) * (one - fr);
+                S ob[6]; V3<S> ol;
+                park(true, ul);
+                wbs_contact_dynamics<Q>(md, 0, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol, &io);
                 park(false, ul);
-                // ---- records: the force of the step on the lane's foot, counted if the foot is a stance foot of the phase (a select on the
-                // wave-uniform contact mask) and the sample had not diverged before the step (`alive` is still the value the step began with).
-                // The impact takes no record.
-                if (mode == 0) {
+                if (mode != 0) {      // positions stay, velocities jump: the scheduled reset map for every live sample, a landing for the quads that have one
+                    const typename Q::B on = Q::gt(alive * (stg == 3 ? one : Q::sum(tl)), S(0.5));
+                    const S o3[3] = {ol.x, ol.y, ol.z};
+                    _Pragma("unroll") for (int i = 0; i < 6; i++) vb[i] = Q::sel(on, ob[i], vb[i]);
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) vl[j] = Q::sel(on, o3[j], vl[j]);
+                    if (stg == 3) break;
+                    fr = fr - tl; nland = nland + tl;      // (T holds feet of live samples only)
+                    stg = 2;
+                    continue;
+                }
+                const WbsUniArgs ua = *wbs_uni_fresh(dist.un);
+                const S att = flag(cm_dyn) * (one - fr);      // the set this solve ran on
+                if (stg == 0) {      // landing test at the substep's start state, over the free scheduled stance feet of a live sample
+                    const S fc = alive * fr;
+                    const typename Q::B isf = Q::gt(fc, S(0.5));
+                    mlift = Q::sel(isf, wbs_max<Q, S>(mlift, io.pz - ua.z_ground), mlift);
+                    tl = fc * Q::sel(Q::gt(io.pz, S(ua.z_ground)), zero, one) * Q::sel(Q::gt(zero, io.wz), one, zero);
+                    if (wbs_any(Q::sum(tl))) { stg = 1; continue; }
+                }
+                {   // lift-off test: the attached foot with the smallest normal force, lowest leg on a tie, if that force is below fz_rel
+                    const S lz = Q::sel(Q::gt(att, S(0.5)), io.lam.z, S(HUGE_VAL)), mz = Q::vmin(lz);
+                    const S need = alive * Q::sel(Q::gt(S(ua.fz_rel), mz), one, zero);
+                    if (wbs_any(need)) {
+                        const S lane = Q::legc(0.0, 1.0, 2.0, 3.0);
+                        const S pick = Q::vmin(Q::sel(Q::gt(lz, mz), S(4.0), lane));
+                        const S rel = need * Q::sel(Q::gt(wbs_abs<Q, S>(lane - pick), S(0.5)), zero, one);
+                        fr = fr + rel; nrel = nrel + rel;
+                        ufirst = Q::sel(Q::gt(need * Q::sel(Q::gt(zero, ufirst), one, zero), S(0.5)), S((double)s), ufirst);
+                        stg = 2;
+                        continue;
+                    }
+                }
+                {   // ---- the last solve of the substep.  Records as below, over the ATTACHED feet; a free foot's force is exactly zero
                     const WbsGrfArgs ga = *wbs_grf_fresh(dist.gr);
-                    const S st = Q::legc((cm_dyn & 1) ? 1.0 : 0.0, (cm_dyn & 2) ? 1.0 : 0.0, (cm_dyn & 4) ? 1.0 : 0.0, (cm_dyn & 8) ? 1.0 : 0.0);
-                    const typename Q::B on = Q::gt(alive * st, S(0.5));
+                    const typename Q::B isa = Q::gt(att, S(0.5));
+                    const V3<S> lam = {Q::sel(isa, io.lam.x, zero), Q::sel(isa, io.lam.y, zero), Q::sel(isa, io.lam.z, zero)};
+                    const typename Q::B on = Q::gt(alive * att, S(0.5));
                     const S cone = ga.mu * lam.z - wbs_max<Q, S>(wbs_abs<Q, S>(lam.x), wbs_abs<Q, S>(lam.y));
                     const S bad = wbs_max<Q, S>(Q::sel(Q::gt(S(ga.fz_min), lam.z), one, zero), Q::sel(Q::gt(zero, cone), one, zero));
-                    const typename Q::B slip = Q::gt(alive * st * bad, S(0.5));
+                    const typename Q::B slip = Q::gt(alive * att * bad, S(0.5));
                     gfmin = Q::sel(on, Q::min(gfmin, lam.z), gfmin); gcmin = Q::sel(on, Q::min(gcmin, cone), gcmin); gfmax = Q::sel(on, wbs_max<Q, S>(gfmax, lam.z), gfmax);
                     gfirst = Q::sel(slip, Q::min(gfirst, S((double)s)), gfirst); gslip = gslip + Q::sel(slip, one, zero);
-                    if (ga.Y != nullptr && (D::SUB == 0 || trip == 0)) { Q::st(ga.Y, (g * (size_t)n_steps + s) * 12, 3, lam.x); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 1, 3, lam.y); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 2, 3, lam.z); }
+                    nfree = nfree + alive * fr;
+                    if (ga.Y != nullptr && sub == 0) { Q::st(ga.Y, (g * (size_t)n_steps + s) * 12, 3, lam.x); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 1, 3, lam.y); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 2, 3, lam.z); }
                 }
-            } else {
-                wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol);
-                park(false, ul);
+                const int nsub = wbs_uniform(wbs_sub_fresh(dist.sb)->substeps);
+                {   // forward Euler with dt / S, then the divergence test on the new state (as below)
+                    const double hs = dt / (double)nsub;
+                    S xb[6], yb[6], xl[3], yl[3], nsq = zero;
+                    _Pragma("unroll") for (int i = 0; i < 6; i++) { xb[i] = qb[i] + vb[i] * hs; yb[i] = vb[i] + ob[i] * hs; nsq = nsq + w0 * (xb[i] * xb[i] + yb[i] * yb[i]); }
+                    const S o3[3] = {ol.x, ol.y, ol.z};
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) { xl[j] = ql[j] + vl[j] * hs; yl[j] = vl[j] + o3[j] * hs; nsq = nsq + (xl[j] * xl[j] + yl[j] * yl[j]); }
+                    nsq = Q::sum(nsq);
+                    const S good = Q::sel(Q::gt(nsq, S(1e12)), zero, one) * Q::sel(Q::gt(nsq + 1.0, nsq), one, zero);
+                    first_bad = Q::sel(Q::gt(alive * (one - good), S(0.5)), S((double)s), first_bad);
+                    alive = alive * good;
+                    const typename Q::B on = Q::gt(alive, S(0.5));
+                    _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::sel(on, xb[i], qb[i]); vb[i] = Q::sel(on, yb[i], vb[i]); }
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) { ql[j] = Q::sel(on, xl[j], ql[j]); vl[j] = Q::sel(on, yl[j], vl[j]); }
+                }
+                sub++; stg = 0;
+                if (sub >= nsub) { if (reset != 0) stg = 3; else break; }
             }
-            if (mode == 0) {      // forward Euler (WBM.cpp:25-26), then the divergence test on the new state
-                double hs = dt;       // (substeps) the step of a trip, dt / S: one division, formed where it is used
-                if constexpr (D::SUB) hs = dt / (double)wbs_uniform(wbs_sub_fresh(dist.sb)->substeps);
-                S xb[6], yb[6], xl[3], yl[3], nsq = zero;
-                _Pragma("unroll") for (int i = 0; i < 6; i++) { xb[i] = qb[i] + vb[i] * hs; yb[i] = vb[i] + ob[i] * hs; nsq = nsq + w0 * (xb[i] * xb[i] + yb[i] * yb[i]); }
-                const S o3[3] = {ol.x, ol.y, ol.z};
-                _Pragma("unroll") for (int j = 0; j < 3; j++) { xl[j] = ql[j] + vl[j] * hs; yl[j] = vl[j] + o3[j] * hs; nsq = nsq + (xl[j] * xl[j] + yl[j] * yl[j]); }
-                nsq = Q::sum(nsq);
-                // good <=> !(nsq > 1e12) && nsq == nsq   (below 1e12 adding one always gives a larger number; a NaN compares false)
-                const S good = Q::sel(Q::gt(nsq, S(1e12)), zero, one) * Q::sel(Q::gt(nsq + 1.0, nsq), one, zero);
-                first_bad = Q::sel(Q::gt(alive * (one - good), S(0.5)), S((double)s), first_bad);
-                alive = alive * good;
-                const typename Q::B on = Q::gt(alive, S(0.5));
-                _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::sel(on, xb[i], qb[i]); vb[i] = Q::sel(on, yb[i], vb[i]); }
-                _Pragma("unroll") for (int j = 0; j < 3; j++) { ql[j] = Q::sel(on, xl[j], ql[j]); vl[j] = Q::sel(on, yl[j], vl[j]); }
-            } else {              // reset map: positions stay, velocities jump
-                const typename Q::B on = Q::gt(alive, S(0.5));
-                const S o3[3] = {ol.x, ol.y, ol.z};
-                _Pragma("unroll") for (int i = 0; i < 6; i++) vb[i] = Q::sel(on, ob[i], vb[i]);
-                _Pragma("unroll") for (int j = 0; j < 3; j++) vl[j] = Q::sel(on, o3[j], vl[j]);
+        } else {
+            int last = reset;
+            if constexpr (D::SUB) last = reset + wbs_uniform(wbs_sub_fresh(dist.sb)->substeps) - 1;
+            _Pragma("nounroll")
+            for (int trip = 0; trip <= last; trip++) {
+                int mode = trip;
+                if constexpr (D::SUB) mode = (reset != 0 && trip == last) ? 1 : 0;
+                S ob[6]; V3<S> ol;
+                park(true, ul);
+                if constexpr (D::GRF) {
+                    V3<S> lam;
+                    wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol, &lam);
+                    park(false, ul);
+                    // ---- records: the force of the step on the lane's foot, counted if the foot is a stance foot of the phase (a select on the
+                    // wave-uniform contact mask) and the sample had not diverged before the step (`alive` is still the value the step began with).
+                    // The impact takes no record.
+                    if (mode == 0) {
+                        const WbsGrfArgs ga = *wbs_grf_fresh(dist.gr);
+                        const S st = Q::legc((cm_dyn & 1) ? 1.0 : 0.0, (cm_dyn & 2) ? 1.0 : 0.0, (cm_dyn & 4) ? 1.0 : 0.0, (cm_dyn & 8) ? 1.0 : 0.0);
+                        const typename Q::B on = Q::gt(alive * st, S(0.5));
+                        const S cone = ga.mu * lam.z - wbs_max<Q, S>(wbs_abs<Q, S>(lam.x), wbs_abs<Q, S>(lam.y));
+                        const S bad = wbs_max<Q, S>(Q::sel(Q::gt(S(ga.fz_min), lam.z), one, zero), Q::sel(Q::gt(zero, cone), one, zero));
+                        const typename Q::B slip = Q::gt(alive * st * bad, S(0.5));
+                        gfmin = Q::sel(on, Q::min(gfmin, lam.z), gfmin); gcmin = Q::sel(on, Q::min(gcmin, cone), gcmin); gfmax = Q::sel(on, wbs_max<Q, S>(gfmax, lam.z), gfmax);
+                        gfirst = Q::sel(slip, Q::min(gfirst, S((double)s)), gfirst); gslip = gslip + Q::sel(slip, one, zero);
+                        if (ga.Y != nullptr && (D::SUB == 0 || trip == 0)) { Q::st(ga.Y, (g * (size_t)n_steps + s) * 12, 3, lam.x); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 1, 3, lam.y); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 2, 3, lam.z); }
+                    }
+                } else {
+                    wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol);
+                    park(false, ul);
+                }
+                if (mode == 0) {      // forward Euler (WBM.cpp:25-26), then the divergence test on the new state
+                    double hs = dt;       // (substeps) the step of a trip, dt / S: one division, formed where it is used
+                    if constexpr (D::SUB) hs = dt / (double)wbs_uniform(wbs_sub_fresh(dist.sb)->substeps);
+                    S xb[6], yb[6], xl[3], yl[3], nsq = zero;
+                    _Pragma("unroll") for (int i = 0; i < 6; i++) { xb[i] = qb[i] + vb[i] * hs; yb[i] = vb[i] + ob[i] * hs; nsq = nsq + w0 * (xb[i] * xb[i] + yb[i] * yb[i]); }
+                    const S o3[3] = {ol.x, ol.y, ol.z};
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) { xl[j] = ql[j] + vl[j] * hs; yl[j] = vl[j] + o3[j] * hs; nsq = nsq + (xl[j] * xl[j] + yl[j] * yl[j]); }
+                    nsq = Q::sum(nsq);
+                    // good <=> !(nsq > 1e12) && nsq == nsq   (below 1e12 adding one always gives a larger number; a NaN compares false)
+                    const S good = Q::sel(Q::gt(nsq, S(1e12)), zero, one) * Q::sel(Q::gt(nsq + 1.0, nsq), one, zero);
+                    first_bad = Q::sel(Q::gt(alive * (one - good), S(0.5)), S((double)s), first_bad);
+                    alive = alive * good;
+                    const typename Q::B on = Q::gt(alive, S(0.5));
+                    _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::sel(on, xb[i], qb[i]); vb[i] = Q::sel(on, yb[i], vb[i]); }
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) { ql[j] = Q::sel(on, xl[j], ql[j]); vl[j] = Q::sel(on, yl[j], vl[j]); }
+                } else {              // reset map: positions stay, velocities jump
+                    const typename Q::B on = Q::gt(alive, S(0.5));
+                    const S o3[3] = {ol.x, ol.y, ol.z};
+                    _Pragma("unroll") for (int i = 0; i < 6; i++) vb[i] = Q::sel(on, ob[i], vb[i]);
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) vl[j] = Q::sel(on, o3[j], vl[j]);
+                }
             }
         }
     }
@@ -683,6 +802,14 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         const S first = Q::vmin(gfirst);
         Q::st0(ga.rows, g * SIM_GRF_ROW, Q::vmin(gfmin)); Q::st0(ga.rows, g * SIM_GRF_ROW + 1, Q::vmin(gcmin)); Q::st0(ga.rows, g * SIM_GRF_ROW + 2, wbs_qmax<Q, S>(gfmax));
         Q::st0(ga.rows, g * SIM_GRF_ROW + 3, Q::sel(Q::gt(first, S(0.5 * SIM_GRF_NONE)), S(-1.0), first)); Q::st0(ga.rows, g * SIM_GRF_ROW + 4, Q::sum(gslip));
+    }
+    if constexpr (D::UNI) {      // the quad's contact row: the four feet joined; free_final: bit l = leg l is free; then F back to where it came from
+        const WbsUniArgs ua = *wbs_uni_fresh(dist.un);
+        const S top = wbs_qmax<Q, S>(mlift);
+        Q::st0(ua.rows, g * SIM_UNI_ROW, ufirst); Q::st0(ua.rows, g * SIM_UNI_ROW + 1, Q::sum(nrel)); Q::st0(ua.rows, g * SIM_UNI_ROW + 2, Q::sum(nland));
+        Q::st0(ua.rows, g * SIM_UNI_ROW + 3, Q::sum(nfree)); Q::st0(ua.rows, g * SIM_UNI_ROW + 4, Q::sum(fr * Q::legc(1.0, 2.0, 4.0, 8.0)));
+        Q::st0(ua.rows, g * SIM_UNI_ROW + 5, Q::sel(Q::gt(S(-1e300), top), zero, top));
+        if (ua.F != nullptr && (ua.hold == nullptr || ua.hold[g * (size_t)ua.hold_stride] == 0)) Q::st(ua.F, g * 4, 1, fr);
     }
     if (trajX != nullptr) store_state((g * (size_t)(n_steps + 1) + n_steps) * 36);
     _Pragma("unroll") for (int i = 0; i < 6; i++) { Q::st0(xfinal, g * 36 + i, qb[i]); Q::st0(xfinal, g * 36 + 18 + i, vb[i]); }
@@ -740,6 +867,7 @@ WBS_MC_GRF_KERNEL(k_sim_quad_mc_grf, 1)
 WBS_MC_GRF_KERNEL(k_sim_quad_mc0_grf, 0)
 #undef WBS_MC_GRF_KERNEL
 // The sub-stepped walks (hsddp_substep_set with S > 1) are six more instantiations with SUB 1 in the policy: hsddp_sub.hip, a translation unit of its own.
+// The walks with unilateral ground contact (hsddp_contact_set) are three more with UNI 1: hsddp_uni.hip, likewise.
 #endif
 
 }  // namespace hs

@@ -4,6 +4,7 @@ whole-body dynamics, with the simulated state handed to the next solve on the de
     ep = solver.episode(n_exec=2, max_ticks=50, keep_log=True)      # or Episode(solver, 2, 50, True)
     ep.set_grf(0.6)                                                 # optional: contact-force records (include/hsddp_grf.h)
     ep.set_substeps(4)                                              # optional: sub-stepped integration (include/hsddp_substep.h)
+    ep.set_contact(0.0, 0.0)                                        # optional: unilateral ground contact (include/hsddp_contact.h)
     ep.reset(x0)                                                    # [B, 36]; also the solver's initial condition
     solver.solve(opt)
     out = run_mhpc(solver, pd, phases, opt_rt, 50, dist=Disturbance(seed=7, sigma_u=0.2, fall_height=0.12), episode=ep)
@@ -149,6 +150,22 @@ class Episode:
         rc = _abi.bind_substep(self.lib).hsddp_substep_set(self.lib.hsddp_episode_sim(self.e), int(substeps))
         if rc != 0:
             raise RuntimeError(f"hsddp_substep_set failed rc={rc}")
+
+    def set_contact(self, fz_rel=0.0, z_ground=0.0, on=True):
+        """Unilateral ground contact (include/hsddp_contact.h) for every later tick; the free feet of a robot are carried from tick to tick and
+        cleared by reset.  on = False: the scheduled stance feet are glued to the ground again."""
+        rc = _abi.bind_contact(self.lib).hsddp_contact_set(self.lib.hsddp_episode_sim(self.e), 1 if on else 0, float(fz_rel), float(z_ground))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_contact_set failed rc={rc}")
+
+    def contact_rows(self, b0=0, nb=None):
+        """Structured array [nb] of hsddp_contact_row_t of the last tick, which has to be one with the rule on."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0),), dtype=_abi.CONTACT_ROW_DTYPE)
+        rc = _abi.bind_contact(self.lib).hsddp_contact_get(self.lib.hsddp_episode_sim(self.e), b0, nb, rows.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_contact_get failed rc={rc}")
+        return rows
 
     @property
     def substeps(self):

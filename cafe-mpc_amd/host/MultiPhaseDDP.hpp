@@ -22,6 +22,7 @@
 #include "hsddp_mc.h"
 #include "hsddp_grf.h"
 #include "hsddp_substep.h"
+#include "hsddp_contact.h"
 #include "hsddp_episode.h"
 
 namespace hsddp {
@@ -70,6 +71,10 @@ public:
     // sub-stepped integration for every later run: S Euler steps of dt / S per control knot under the knot's torque, 1 <= S <= 64 (include/hsddp_substep.h)
     bool set_substeps(int substeps) { rc_ = s_ ? hsddp_substep_set(s_, substeps) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     int substeps() { int v = 1; rc_ = s_ ? hsddp_substep_get(s_, &v) : HSDDP_EINVAL; return v; }
+    // unilateral ground contact for every later run (include/hsddp_contact.h): on, the release threshold of the normal force, the height of the ground
+    bool set_contact(bool on, double fz_rel = 0.0, double z_ground = 0.0) { rc_ = s_ ? hsddp_contact_set(s_, on ? 1 : 0, fz_rel, z_ground) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // rows of the last run, which has to be one with the rule on: batch x n_samples
+    bool contact(hsddp_contact_row_t* rows) { rc_ = s_ ? hsddp_contact_get(s_, 0, batch_, rows) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // the records of the last run alone (result() holds them too): rows batch x n_samples, Y batch x n_samples x n_steps x 12 or null
     bool grf(hsddp_grf_row_t* rows, double* Y = nullptr) { rc_ = s_ ? hsddp_grf_get(s_, 0, batch_, rows, Y) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     SimResult result() {
@@ -119,6 +124,8 @@ public:
     bool set_grf(double mu, double fz_min = 0.0) { rc_ = e_ ? hsddp_grf_set(hsddp_episode_sim(e_), mu, fz_min) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // sub-stepped integration for every later tick (include/hsddp_substep.h)
     bool set_substeps(int substeps) { rc_ = e_ ? hsddp_substep_set(hsddp_episode_sim(e_), substeps) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // unilateral ground contact for every later tick; the free feet are carried from tick to tick (include/hsddp_contact.h)
+    bool set_contact(bool on, double fz_rel = 0.0, double z_ground = 0.0) { rc_ = e_ ? hsddp_contact_set(hsddp_episode_sim(e_), on ? 1 : 0, fz_rel, z_ground) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     std::vector<hsddp_episode_row_t> rows(std::vector<double>* x_now = nullptr) {
         std::vector<hsddp_episode_row_t> r((size_t)batch_);
         if (x_now) x_now->resize((size_t)batch_ * 36);

@@ -14,6 +14,8 @@
 
     res = solver.simulate(x0, n_steps=50, substeps=4)      # include/hsddp_substep.h: four Euler steps of dt / 4 per control knot, torque held
 
+    res = solver.simulate(x0, n_steps=50, contact=(0.0, 0.0))      # include/hsddp_contact.h: the ground only pushes; res["contact"]["n_release"], ["n_land"]
+
 Nothing here computes anything: the rollout is the k_sim_quad / k_sim_quad_mc kernel (csrc/wb_sim.hpp).  mc_normals states the generator of the
 disturbed runs in numpy, grf_rows the contact-force records and grf_rows_sub those of a sub-stepped run: the definitions the kernel mirrors."""
 import ctypes as C
@@ -113,6 +115,7 @@ class Simulation:
         self.lib = _abi.bind_sim(solver.lib)      # raises on a library without include/hsddp_sim.h (the CPU checker)
         self.disturbed = False
         self.grf_on = False
+        self.contact_on = False
         self.solver, self.R, self.n_steps, self.keep_traj = solver, int(n_samples), int(n_steps), bool(keep_traj)
         self.s = C.c_void_p()
         rc = self.lib.hsddp_sim_create(solver.h, self.R, self.n_steps, 1 if keep_traj else 0, C.byref(self.s))
@@ -186,6 +189,39 @@ class Simulation:
         if rc != 0:
             raise RuntimeError(f"hsddp_substep_set failed rc={rc}")
 
+    def set_contact(self, fz_rel=0.0, z_ground=0.0):
+        """Unilateral ground contact (include/hsddp_contact.h) for every later run: a stance foot whose normal force falls below fz_rel is
+        released and lands again on the flat ground at world height z_ground."""
+        rc = _abi.bind_contact(self.lib).hsddp_contact_set(self.s, 1, float(fz_rel), float(z_ground))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_contact_set failed rc={rc}")
+        self.contact_on = True
+
+    def clear_contact(self):
+        """Later runs glue the scheduled stance feet to the ground again (the kernels without the rule)."""
+        rc = _abi.bind_contact(self.lib).hsddp_contact_set(self.s, 0, 0.0, 0.0)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_contact_set failed rc={rc}")
+        self.contact_on = False
+
+    @property
+    def contact(self):
+        """(on, fz_rel, z_ground) as later runs use them (hsddp_contact_get_params)."""
+        on = C.c_int(); f = C.c_double(); z = C.c_double()
+        rc = _abi.bind_contact(self.lib).hsddp_contact_get_params(self.s, C.byref(on), C.byref(f), C.byref(z))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_contact_get_params failed rc={rc}")
+        return bool(on.value), f.value, z.value
+
+    def contact_rows(self, b0=0, nb=None):
+        """Structured array [nb, R] of hsddp_contact_row_t of the last run, which has to be one with the rule on."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0), self.R), dtype=_abi.CONTACT_ROW_DTYPE)
+        rc = _abi.bind_contact(self.lib).hsddp_contact_get(self.s, b0, nb, rows.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_contact_get failed rc={rc}")
+        return rows
+
     @property
     def substeps(self):
         """What later runs use, as the library reports it (hsddp_substep_get)."""
@@ -236,16 +272,19 @@ class Simulation:
         return float(ms.value)
 
 
-def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1):
+def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None):
     """One-off simulation on `solver`: dict with rows, x_final and, with keep_traj, X and U (see Simulation); a disturbed run (dist / kick given)
     returns extra too; grf = (mu, fz_min) adds the contact-force records grf and, with keep_traj, Y; substeps = S > 1 integrates every control
-    knot in S steps (include/hsddp_substep.h)."""
+    knot in S steps (include/hsddp_substep.h); contact = (fz_rel, z_ground) switches unilateral ground contact on (include/hsddp_contact.h) and
+    adds the rows contact."""
     sim = Simulation(solver, x0.shape[1], n_steps, keep_traj)
     try:
         if substeps != 1:
             sim.set_substeps(substeps)
         if grf is not None:
             sim.set_grf(*grf)
+        if contact is not None:
+            sim.set_contact(*contact)
         sim.run(x0, dist=dist, kick=kick)
         rows, xf = sim.rows()
         out = dict(rows=rows, x_final=xf)
@@ -258,6 +297,8 @@ def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=Non
                 out["grf"], out["Y"] = sim.grf()
             else:
                 out["grf"] = sim.grf()
+        if sim.contact_on:
+            out["contact"] = sim.contact_rows()
         return out
     finally:
         sim.close()
