@@ -321,6 +321,33 @@ def bind_contact(lib):
     return lib
 
 
+# include/hsddp_terrain.h: terrain height maps and early swing-foot touchdown in a simulation object (libhsddp_hip.so only).  A list and a binder of
+# their own, as above.
+TERRAIN_EXPORTS = ["hsddp_terrain_set", "hsddp_terrain_get_params", "hsddp_terrain_get"]
+# hsddp_terrain_row_t
+TERRAIN_ROW_DTYPE = np.dtype([("first_early", "<i4"), ("n_early", "<i4"), ("n_early_release", "<i4"), ("n_held", "<i4"), ("early_final", "<i4"), ("pad", "<i4"),
+                              ("max_pen", "<f8")])
+
+
+class TerrainParams(C.Structure):
+    """hsddp_terrain_t"""
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("n_maps", C.c_int), ("early", C.c_int),
+                ("x0", C.c_double), ("y0", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("w_td", C.c_double)]
+
+
+def bind_terrain(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_terrain.h (and of hsddp_contact.h, which they extend).  Raises if the library lacks any."""
+    missing = [s for s in TERRAIN_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the terrain entry points {missing}")
+    bind_contact(lib)
+    H = C.c_void_p
+    lib.hsddp_terrain_set.argtypes = [H, C.c_int, C.POINTER(TerrainParams), C.c_void_p, C.c_void_p]
+    lib.hsddp_terrain_get_params.argtypes = [H, IP, C.POINTER(TerrainParams)]
+    lib.hsddp_terrain_get.argtypes = [H, C.c_int, C.c_int, C.c_void_p]
+    return lib
+
+
 # include/hsddp_episode.h: batched closed-loop MPC episodes (libhsddp_hip.so only)
 EPISODE_EXPORTS = ["hsddp_episode_create", "hsddp_episode_destroy", "hsddp_episode_reset", "hsddp_episode_advance", "hsddp_episode_get_rows",
                    "hsddp_episode_get_log", "hsddp_episode_device_state", "hsddp_episode_sim", "hsddp_episode_status"]
@@ -613,7 +640,7 @@ class Solver:
                  "get_references")
         return out
 
-    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None):
+    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None):
         """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)
         over the first n_steps whole-body control knots (include/hsddp_sim.h): dict with rows (structured array [batch, R] of dev_q, dev_v,
         min_height, max_torque, first_bad), x_final [batch, R, 36] and, with keep_traj, X [batch, R, n_steps + 1, 36] and U [batch, R, n_steps, 12].
@@ -623,9 +650,11 @@ class Solver:
         [batch, R, n_steps, 12].  substeps = S > 1: every control knot is S forward-Euler steps of dt / S under the knot's torque
         (include/hsddp_substep.h); shapes and meanings stay, n_slip counts (foot, substep) pairs.  contact = (fz_rel, z_ground):
         unilateral ground contact (include/hsddp_contact.h), which also returns contact (structured array [batch, R] of first_release, n_release,
-        n_land, n_free, free_final, max_lift)."""
+        n_land, n_free, free_final, max_lift).  terrain = sim.Terrain(...), with contact: height maps and early swing-foot touchdown
+        (include/hsddp_terrain.h), which also returns terrain (structured array [batch, R] of first_early, n_early, n_early_release, n_held,
+        early_final, max_pen)."""
         from . import sim
-        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps, contact=contact)
+        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps, contact=contact, terrain=terrain)
 
     def episode(self, n_exec, max_ticks, keep_log=False):
         """An episode.Episode on this solver (include/hsddp_episode.h): batched closed-loop MPC ticks with the simulated state handed to the next

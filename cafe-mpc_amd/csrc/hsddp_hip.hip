@@ -22,6 +22,7 @@
 #include "hsddp_grf.h"
 #include "hsddp_substep.h"
 #include "hsddp_contact.h"
+#include "hsddp_terrain.h"
 #include "hsddp_mc.h"
 #include "hsddp_episode.h"
 #include "hs_types.hpp"
@@ -1684,6 +1685,16 @@ void wbs_uni_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const
 #else
 #include "hsddp_uni.hip"
 #endif
+// The kernels with terrain and early swing-foot touchdown and their launcher (hsddp_terrain.h): hsddp_ter.hip, likewise (-DHS_TER_SEPARATE here).
+#ifdef HS_TER_SEPARATE
+namespace hs {
+void wbs_ter_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
+                    double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un,
+                    const WbsTerArgs* te);
+}
+#else
+#include "hsddp_ter.hip"
+#endif
 struct hsddp_sim {
     hsddp_handle* h = nullptr;
     int R = 0, n_steps = 0, keep = 0, gen = 0;
@@ -1706,12 +1717,19 @@ struct hsddp_sim {
     double uni_fz_rel = 0.0, uni_z_ground = 0.0;
     WbsUniArgs* d_uni = nullptr; double *d_uni_rows = nullptr, *d_uni_F = nullptr, *d_uni_grows = nullptr; WbsGrfArgs* d_uni_grf = nullptr;
     const int* uni_hold = nullptr; int uni_hold_stride = 0;
+    // terrain and early touchdown (hsddp_terrain.h): allocated by hsddp_terrain_set calls that switch it on (the grid again when it grows: ter_cap
+    // doubles).  ter_on: what later runs ask for - it acts while uni_on is set too; last_ter: the last run launched the _ter kernels.  d_ter_E: the early
+    // flags an episode carries from tick to tick (uni_keep), under the hold of d_uni_F
+    bool ter_on = false, last_ter = false;
+    hsddp_terrain_t ter = {};
+    WbsTerArgs* d_ter = nullptr; double *d_ter_H = nullptr, *d_ter_rows = nullptr, *d_ter_E = nullptr; int* d_ter_map = nullptr; size_t ter_cap = 0;
 };
 static void sim_free(hsddp_sim* s) {
     if (!s) return;
     hipSetDevice(s->h->device);
     if (s->h->stream) hipStreamSynchronize(s->h->stream);
-    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf, s->d_sub, s->d_uni, s->d_uni_rows, s->d_uni_F, s->d_uni_grows, s->d_uni_grf};
+    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf, s->d_sub, s->d_uni, s->d_uni_rows, s->d_uni_F, s->d_uni_grows, s->d_uni_grf,
+                 s->d_ter, s->d_ter_H, s->d_ter_rows, s->d_ter_E, s->d_ter_map};
     for (void* q : p) if (q) hipFree(q);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -1777,7 +1795,12 @@ static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, b
     const size_t total = (size_t)h->batch * s->R;
     if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
     HIPCK(hipEventRecord(s->ev0, h->stream));
-    if (s->uni_on) {      // (for every S: the walk with the rule carries the sub-step loop and the records)
+    const bool ter = s->uni_on && s->ter_on;      // (hsddp_terrain.h: dormant while the contact rule is off)
+    if (ter) {
+        wbs_ter_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
+                       s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : (const WbsGrfArgs*)s->d_uni_grf,
+                       s->d_sub, s->d_uni, s->d_ter);
+    } else if (s->uni_on) {      // (for every S: the walk with the rule carries the sub-step loop and the records)
         wbs_uni_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
                        s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : (const WbsGrfArgs*)s->d_uni_grf,
                        s->d_sub, s->d_uni);
@@ -1803,7 +1826,7 @@ static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, b
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(s->ev1, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    s->timed = true; s->last_grf = s->grf_on; s->last_uni = s->uni_on;
+    s->timed = true; s->last_grf = s->grf_on; s->last_uni = s->uni_on; s->last_ter = ter;
     return HSDDP_OK;
 }
 
@@ -1990,6 +2013,67 @@ int hsddp_contact_get(hsddp_sim_t* s, int b0, int nb, hsddp_contact_row_t* rows)
     return HSDDP_OK;
 }
 
+int hsddp_terrain_set(hsddp_sim_t* s, int on, const hsddp_terrain_t* t, const double* H, const int* map_of) {
+    if (!s) return HSDDP_EINVAL;
+    if (!on) { s->ter_on = false; return HSDDP_OK; }      // later runs launch the kernels without the terrain; the buffers and the parameters are kept
+    if (!t || !H) return HSDDP_EINVAL;
+    if (!std::isfinite(t->x0) || !std::isfinite(t->y0) || !std::isfinite(t->cx) || !std::isfinite(t->cy) || !std::isfinite(t->w_td)) return HSDDP_EINVAL;
+    if (!(t->cx > 0.0) || !(t->cy > 0.0) || t->w_td < 0.0) return HSDDP_EINVAL;
+    if (t->nx < 1 || t->nx > 1024 || t->ny < 1 || t->ny > 1024 || t->n_maps < 1 || t->n_maps > 4096) return HSDDP_EINVAL;
+    const size_t cells = (size_t)t->n_maps * (size_t)t->nx * (size_t)t->ny;
+    if (cells > ((size_t)1 << 22)) return HSDDP_EINVAL;
+    for (size_t i = 0; i < cells; i++) if (!std::isfinite(H[i])) return HSDDP_EINVAL;
+    hsddp_handle* h = s->h;
+    const size_t total = (size_t)h->batch * s->R;
+    if (map_of) for (size_t i = 0; i < total; i++) if (map_of[i] < 0 || map_of[i] >= t->n_maps) return HSDDP_EINVAL;
+    if (h->f32) return HSDDP_ENOTSUP;
+    HIPCK(hipSetDevice(h->device));
+    // (as UNI_CK of hsddp_contact_set: an allocation that fails returns its code at once, what was made before it is kept, and the terrain stays as it was)
+#define TER_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
+    if (!s->d_ter) TER_CK(hipMalloc((void**)&s->d_ter, sizeof(WbsTerArgs)));
+    if (!s->d_ter_rows) TER_CK(hipMalloc((void**)&s->d_ter_rows, total * SIM_TER_ROW * 8));
+    if (!s->d_ter_map) TER_CK(hipMalloc((void**)&s->d_ter_map, total * sizeof(int)));
+    if (s->uni_keep && !s->d_ter_E) { TER_CK(hipMalloc((void**)&s->d_ter_E, total * 4 * 8)); HIPCK(hipMemsetAsync(s->d_ter_E, 0, total * 4 * 8, h->stream)); }
+    if (cells > s->ter_cap) {      // the grid grows: the new block first, so that a failure leaves the old one in place
+        double* nb = nullptr;
+        TER_CK(hipMalloc((void**)&nb, cells * 8));
+        HIPCK(hipStreamSynchronize(h->stream));
+        if (s->d_ter_H) hipFree(s->d_ter_H);
+        s->d_ter_H = nb; s->ter_cap = cells;
+    }
+#undef TER_CK
+    HIPCK(hipMemcpyAsync(s->d_ter_H, H, cells * 8, hipMemcpyHostToDevice, h->stream));
+    if (map_of) HIPCK(hipMemcpyAsync(s->d_ter_map, map_of, total * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    else HIPCK(hipMemsetAsync(s->d_ter_map, 0, total * sizeof(int), h->stream));
+    WbsTerArgs a;
+    a.H = s->d_ter_H; a.map_of = s->d_ter_map; a.nx = t->nx; a.ny = t->ny; a.n_maps = t->n_maps; a.early = t->early ? 1 : 0;
+    a.x0 = t->x0; a.y0 = t->y0; a.cx = t->cx; a.cy = t->cy; a.w_td = t->w_td; a.rows = s->d_ter_rows; a.E = s->d_ter_E;
+    HIPCK(hipMemcpyAsync(s->d_ter, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));      // H and map_of are the caller's: they may go once the call returns
+    s->ter_on = true; s->ter = *t; s->ter.early = a.early;
+    return HSDDP_OK;
+}
+
+int hsddp_terrain_get_params(hsddp_sim_t* s, int* on, hsddp_terrain_t* t) {
+    if (!s || !on || !t) return HSDDP_EINVAL;
+    *on = s->ter_on ? 1 : 0; *t = s->ter;
+    return HSDDP_OK;
+}
+
+int hsddp_terrain_get(hsddp_sim_t* s, int b0, int nb, hsddp_terrain_row_t* rows) {
+    if (!sim_range_ok(s, b0, nb) || !rows || !s->last_ter) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(s->h->device));
+    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R;
+    std::vector<double> r(cnt * SIM_TER_ROW);
+    HIPCK(hipMemcpy(r.data(), s->d_ter_rows + off * SIM_TER_ROW, r.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < cnt; i++) {
+        const double* q = &r[i * SIM_TER_ROW];
+        rows[i].first_early = (int)q[0]; rows[i].n_early = (int)q[1]; rows[i].n_early_release = (int)q[2]; rows[i].n_held = (int)q[3]; rows[i].early_final = (int)q[4]; rows[i].pad = 0;
+        rows[i].max_pen = q[5];
+    }
+    return HSDDP_OK;
+}
+
 const double* hsddp_sim_device_final(hsddp_sim_t* s) { return s ? s->d_final : nullptr; }
 
 int hsddp_sim_get_kernel_time_ms(hsddp_sim_t* s, float* ms) {
@@ -2077,6 +2161,7 @@ int hsddp_episode_reset(hsddp_episode_t* e, const double* x0, int src_device) {
         HIPCK(hipMemsetAsync(e->d_Y, 0, B * steps * 12 * 8, h->stream));
     }
     if (e->sim->d_uni_F) HIPCK(hipMemsetAsync(e->sim->d_uni_F, 0, B * 4 * 8, h->stream));      // (hsddp_contact.h) every foot attached again
+    if (e->sim->d_ter_E) HIPCK(hipMemsetAsync(e->sim->d_ter_E, 0, B * 4 * 8, h->stream));      // (hsddp_terrain.h) no swing foot held
     HIPCK(hipStreamSynchronize(h->stream));
     e->tick = 0; e->n_impacts = 0; e->started = true;
     return HSDDP_OK;

@@ -68,6 +68,12 @@ template <class T> struct wbs_is_uni_io { static constexpr bool value = false; }
 template <class S> struct wbs_is_uni_io<WbsUniIO<S>> { static constexpr bool value = true; };
 template <class Q, class S, class... LO> HD S wbs_lane_flag(int cmask, LO*...) { return Q::legc((cmask & 1) ? 1.0 : 0.0, (cmask & 2) ? 1.0 : 0.0, (cmask & 4) ? 1.0 : 0.0, (cmask & 8) ? 1.0 : 0.0); }
 template <class Q, class S> HD S wbs_lane_flag(int, WbsUniIO<S>* io) { return io->cl; }
+// Terrain (include/hsddp_terrain.h): the same exchange plus the x and y of the lane's foot point (fpos, computed for the bias pass anyway), which the
+// height lookup needs.  An element type of its own, so that a solve with WbsUniIO instantiates what it instantiated before this one existed.
+template <class S> struct WbsTerIO { S cl, pz, wz, px, py; V3<S> lam; };
+template <class T> struct wbs_is_ter_io { static constexpr bool value = false; };
+template <class S> struct wbs_is_ter_io<WbsTerIO<S>> { static constexpr bool value = true; };
+template <class Q, class S> HD S wbs_lane_flag(int, WbsTerIO<S>* io) { return io->cl; }
 template <class Q, class S = typename Q::S, class... LO>
 HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double damping, double bg_alpha, const S (&qb)[6], const S (&vb)[6], const S (&ql)[3],
                              const S (&vl_)[3], const S (&ul)[3], S (&out_b)[6], V3<S>& out_l, LO*... lam_out) {
@@ -359,7 +365,8 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         rhs = {pick(lam0.x, lam1.x, lam2.x, lam3.x), pick(lam0.y, lam1.y, lam2.y, lam3.y), pick(lam0.z, lam1.z, lam2.z, lam3.z)};
     }
     const V3<S> lam = scale(cl, rhs);      // contact force of the lane's foot (world axes); zero for a swing leg
-    if constexpr ((wbs_is_uni_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z), ...); }
+    if constexpr ((wbs_is_ter_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z, lam_out->px = fpos.x, lam_out->py = fpos.y), ...); }
+    else if constexpr ((wbs_is_uni_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z), ...); }
     else if constexpr (sizeof...(LO) > 0) { ((lam_out != nullptr ? (void)(*lam_out = lam) : (void)0), ...); }
     // qdd = L^-T (y + X lam): base part replicated, leg part in the lane
     S qddb[6]; V3<S> qddl;
@@ -400,8 +407,8 @@ struct WbsMcArgs {
 // NOISE 0: the walk of a run whose three sigmas are zero, compiled without the generator.  Measured (MI355X, config 3 x 16 samples x 200 steps, plain
 // run 9.88 ms): with the generator compiled in and branched over, a run with only u_max set took 11.74 ms - the register allocation of the whole
 // loop pays for code that does not run; without it 9.83 ms.  So the host picks the instantiation, and every other switch stays a run-time branch.
-struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0, UNI = 0; };
-template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0, UNI = 0; const WbsMcArgs* a; };
+struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0, UNI = 0, TER = 0; };
+template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0, UNI = 0, TER = 0; const WbsMcArgs* a; };
 constexpr int SIM_PARK_MC = SIM_PARK + 2;       // ... and n_sat, first_fall
 // Contact-force records (include/hsddp_grf.h): GRF 1 in the policy.  The walk takes the lane's multiplier of every mode-0 solve, keeps five running
 // values per lane (lane = leg) - smallest / largest stance fz, smallest cone margin, first violating step, violations - and joins them over the
@@ -414,8 +421,8 @@ struct WbsGrfArgs {
 constexpr int SIM_GRF_ROW = 5;     // min_fz | min_cone | max_fz | first_slip | n_slip
 constexpr int SIM_GRF_PARK = 5;    // the lane's running values, parked behind the others
 constexpr double SIM_GRF_NONE = 1e18;      // first_slip of a lane without a violation while the walk runs: above every step index
-struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0, UNI = 0; const WbsGrfArgs* gr; };
-template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0, UNI = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
+struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0, UNI = 0, TER = 0; const WbsGrfArgs* gr; };
+template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0, UNI = 0, TER = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
 // Sub-stepped integration (include/hsddp_substep.h): SUB 1 in the policy.  A control knot is S forward-Euler steps of dt / S under the knot's torque
 // (zero-order hold): the feedback, the noise and every record of the state stay once per control step, the contact solve, the divergence test and
 // the force records run once per substep.  S is a run-time trip count read from device memory through a laundered pointer, as the other switches
@@ -423,10 +430,10 @@ template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOI
 // constexpr (D::SUB)` below is this code, and the six policies above compile to what they compiled to without it.
 struct WbsSubArgs { int substeps, pad; };      // 2 .. 64 (the host launches the kernels above for 1)
 constexpr int SIM_SUB_PARK = 3;
-struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1, UNI = 0; const WbsSubArgs* sb; };
-template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1, UNI = 0; const WbsMcArgs* a; const WbsSubArgs* sb; };
-struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
-template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1, UNI = 0, TER = 0; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1, UNI = 0, TER = 0; const WbsMcArgs* a; const WbsSubArgs* sb; };
+struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0, TER = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0, TER = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
 // Unilateral ground contact (include/hsddp_contact.h): UNI 1 in the policy, always with the records and the sub-step loop (GRF 1, SUB 1; S = 1 too).
 // The lane (= leg) carries F, 1 if its foot is a scheduled stance foot that is FREE, and the contact flag of every solve is the lane's own: attached =
 // scheduled and not free.  The trip loop of a control step becomes a small state machine around the ONE call site of the solve -
@@ -443,8 +450,34 @@ struct WbsUniArgs {
 };
 constexpr int SIM_UNI_ROW = 6;      // first_release | n_release | n_land | n_free | free_final | max_lift
 constexpr int SIM_UNI_PARK = 7;     // F, T, first_release, n_release, n_land, n_free, max_lift of the lane, parked behind everything else
-struct WbsUni { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
-template <int NOISE_> struct WbsMcUni { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
+struct WbsUni { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
+template <int NOISE_> struct WbsMcUni { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
+// Terrain and early swing-foot touchdown (include/hsddp_terrain.h): TER 1 in the policy, on top of UNI = GRF = SUB = 1.  The landing test compares with
+// a looked-up height instead of a constant, the tested set grows by the swing feet, and the attached set of a solve by the swing feet that landed: the
+// lane carries E, 1 if its foot is a SWING foot that is attached.  The solve hands the foot's x and y back through WbsTerIO; the lookup is one per-lane
+// load behind the solve of stage 0.  E, the four counters and max_pen are parked behind everything else.  Every `if constexpr (D::TER)` below is this
+// code, and the fifteen policies above compile to what they compiled to without it.
+struct WbsTerArgs {
+    const double* H;              // [n_maps][ny][nx]
+    const int* map_of;            // [B R] the map of a sample
+    int nx, ny, n_maps, early;
+    double x0, y0, cx, cy, w_td;
+    double* rows;                 // [B R][SIM_TER_ROW]
+    double* E;                    // [B R][4] the early flags carried from run to run (episodes), as WbsUniArgs::F (and under its hold); null: E starts empty
+};
+constexpr int SIM_TER_ROW = 6;      // first_early | n_early | n_early_release | n_held | early_final | max_pen
+constexpr int SIM_TER_PARK = 6;     // E, first_early, n_early, n_early_release, n_held, max_pen of the lane
+struct WbsTer { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
+template <int NOISE_> struct WbsMcTer { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
+template <bool TER, class S> struct wbs_io_of { using type = WbsUniIO<S>; };
+template <class S> struct wbs_io_of<true, S> { using type = WbsTerIO<S>; };
+// Height of map m at the foot point (px, py), relative to z_ground (sim.terrain_height is the definition).  The cell index is clamped as a double - fmax
+// sends a NaN to 0, fmin an infinity to the last cell - BEFORE it becomes an integer: no address outside the grid can be formed, whatever the state holds.
+HD double wbs_ter_height_lane(const WbsTerArgs& t, int m, double px, double py) {
+    const double fx = fmin(fmax(floor((px - t.x0) / t.cx), 0.0), (double)(t.nx - 1));
+    const double fy = fmin(fmax(floor((py - t.y0) / t.cy), 0.0), (double)(t.ny - 1));
+    return t.H[((size_t)m * (size_t)t.ny + (size_t)(int)fy) * (size_t)t.nx + (size_t)(int)fx];
+}
 
 // The generator (sim.mc_normals is its definition): draw(n) is output n >= 1 of SplitMix64(seed), whose state is the counter seed + n G; the normal of
 // coordinate c of (global problem, sample, step) is Box-Muller on draws n0 + 1 and n0 + 2, n0 = 2 (((problem 65536 + sample) 65536 + step) 48 + c).
@@ -478,6 +511,8 @@ inline const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { return p; }
 inline const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { return p; }
 inline const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { return p; }
 inline const WbsUniArgs* wbs_uni_fresh(const WbsUniArgs* p) { return p; }
+inline const WbsTerArgs* wbs_ter_fresh(const WbsTerArgs* p) { return p; }
+inline Q4 wbs_ter_height(const WbsTerArgs& t, int m, const Q4& px, const Q4& py) { return Q4(wbs_ter_height_lane(t, m, px.v[0], py.v[0]), wbs_ter_height_lane(t, m, px.v[1], py.v[1]), wbs_ter_height_lane(t, m, px.v[2], py.v[2]), wbs_ter_height_lane(t, m, px.v[3], py.v[3])); }
 inline bool wbs_any(const Q4& f) { return f.v[0] > 0.5 || f.v[1] > 0.5 || f.v[2] > 0.5 || f.v[3] > 0.5; }      // (host: the quad is the whole wave)
 #else
 HD void wbs_mc_normal3(unsigned long long seed, unsigned long long base, const double& c, double (&z)[3]) { wbs_mc_normal3_lane(seed, base, (int)c, z); }
@@ -487,6 +522,8 @@ HD const WbsMcArgs* wbs_mc_fresh(const WbsMcArgs* p) { asm volatile("" : "+s"(p)
 HD const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsUniArgs* wbs_uni_fresh(const WbsUniArgs* p) { asm volatile("" : "+s"(p)); return p; }
+HD const WbsTerArgs* wbs_ter_fresh(const WbsTerArgs* p) { asm volatile("" : "+s"(p)); return p; }
+HD double wbs_ter_height(const WbsTerArgs& t, int m, double px, double py) { return wbs_ter_height_lane(t, m, px, py); }
 // true if the 0 / 1 flag is set in ANY active lane of the wave: a ballot, so the answer is wave-uniform and the branch on it a scalar one
 HD bool wbs_any(double f) { return __builtin_amdgcn_ballot_w64(f > 0.5) != 0ull; }
 #endif
@@ -509,6 +546,10 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
     // (foot, substep) pairs of the lane's foot; largest height of the foot above the ground at a landing test
     S fr = zero, tl = zero, ufirst = S(-1.0), nrel = zero, nland = zero, nfree = zero, mlift = S(-HUGE_VAL);
     if constexpr (D::UNI) { const WbsUniArgs ua = *wbs_uni_fresh(dist.un); if (ua.F != nullptr) fr = Q::ld(ua.F, g * 4, 1); }
+    // (terrain only) E of the lane's foot, 0 / 1; first control step with an early touchdown (the quad's, replicated); early touchdowns, releases from E
+    // and held (foot, substep) pairs of the lane's foot; largest depth of the foot below the ground at a landing
+    S er = zero, efirst = S(-1.0), nearly = zero, nerel = zero, nheld = zero, mpen = S(-HUGE_VAL);
+    if constexpr (D::TER) { const WbsTerArgs ta = *wbs_ter_fresh(dist.te); if (ta.E != nullptr) er = Q::ld(ta.E, g * 4, 1); }
     // deviation of the state from row `kx` of a phase's Xbar: base part replicated, the lane's leg
     auto deviation = [&](PhaseC& P, size_t kx, S (&eb)[6], S (&wb)[6], S (&el)[3], S (&wl)[3]) {
         _Pragma("unroll") for (int i = 0; i < 6; i++) { eb[i] = qb[i] - Q::ld(P.Xbar, kx + i, 0); wb[i] = vb[i] - Q::ld(P.Xbar, kx + 18 + i, 0); }
@@ -540,16 +581,19 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         constexpr int G0 = D::MC ? SIM_PARK_MC : SIM_PARK;      // (records) the five running values behind the others
         constexpr int U0 = G0 + (D::GRF ? SIM_GRF_PARK : 0);    // (substeps) the torques behind those
         constexpr int N0 = U0 + (D::SUB ? SIM_SUB_PARK : 0);    // (unilateral contact) F, T, the counters and max_lift behind those
+        constexpr int T0 = N0 + (D::UNI ? SIM_UNI_PARK : 0);    // (terrain) E, its counters and max_pen behind those
         if (out) {
             _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; if constexpr (D::MC) { c[64 * 24] = nsat; c[64 * 25] = ffall; }
             if constexpr (D::GRF) { c[64 * G0] = gfmin; c[64 * (G0 + 1)] = gcmin; c[64 * (G0 + 2)] = gfmax; c[64 * (G0 + 3)] = gfirst; c[64 * (G0 + 4)] = gslip; }
             if constexpr (D::SUB) { c[64 * U0] = u3[0]; c[64 * (U0 + 1)] = u3[1]; c[64 * (U0 + 2)] = u3[2]; }
             if constexpr (D::UNI) { c[64 * N0] = fr; c[64 * (N0 + 1)] = tl; c[64 * (N0 + 2)] = ufirst; c[64 * (N0 + 3)] = nrel; c[64 * (N0 + 4)] = nland; c[64 * (N0 + 5)] = nfree; c[64 * (N0 + 6)] = mlift; }
+            if constexpr (D::TER) { c[64 * T0] = er; c[64 * (T0 + 1)] = efirst; c[64 * (T0 + 2)] = nearly; c[64 * (T0 + 3)] = nerel; c[64 * (T0 + 4)] = nheld; c[64 * (T0 + 5)] = mpen; }
         } else {
             asm volatile("" ::: "memory"); _Pragma("unroll") for (int i = 0; i < 24; i++) *v[i] = c[64 * i]; if constexpr (D::MC) { nsat = c[64 * 24]; ffall = c[64 * 25]; }
             if constexpr (D::GRF) { gfmin = c[64 * G0]; gcmin = c[64 * (G0 + 1)]; gfmax = c[64 * (G0 + 2)]; gfirst = c[64 * (G0 + 3)]; gslip = c[64 * (G0 + 4)]; }
             if constexpr (D::SUB) { u3[0] = c[64 * U0]; u3[1] = c[64 * (U0 + 1)]; u3[2] = c[64 * (U0 + 2)]; }
             if constexpr (D::UNI) { fr = c[64 * N0]; tl = c[64 * (N0 + 1)]; ufirst = c[64 * (N0 + 2)]; nrel = c[64 * (N0 + 3)]; nland = c[64 * (N0 + 4)]; nfree = c[64 * (N0 + 5)]; mlift = c[64 * (N0 + 6)]; }
+            if constexpr (D::TER) { er = c[64 * T0]; efirst = c[64 * (T0 + 1)]; nearly = c[64 * (T0 + 2)]; nerel = c[64 * (T0 + 3)]; nheld = c[64 * (T0 + 4)]; mpen = c[64 * (T0 + 5)]; }
         }
     };
 #endif
@@ -658,12 +702,14 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
             // landing impact, 2 a solve again, 3 the scheduled reset map.  stg and sub are wave-uniform: they change on ballots only.
             auto flag = [](int m) { return Q::legc((m & 1) ? 1.0 : 0.0, (m & 2) ? 1.0 : 0.0, (m & 4) ? 1.0 : 0.0, (m & 8) ? 1.0 : 0.0); };      // the lane's bit of a wave-uniform mask, formed at every use
             fr = Q::sel(Q::gt(alive, S(0.5)), fr * flag(cm_dyn), fr);      // F <- F n C: does something at a phase change only
+            if constexpr (D::TER) er = Q::sel(Q::gt(alive, S(0.5)), er * (one - flag(cm_dyn)), er);      // E <- E \ C: such a foot is an ordinary attached stance foot now
             int sub = 0, stg = 0;
             _Pragma("nounroll")
             for (;;) {
                 const int mode = (stg == 1 || stg == 3) ? 1 : 0;
-                WbsUniIO<S> io;
+                typename wbs_io_of<D::TER != 0, S>::type io;
                 io.cl = stg == 1 ? tl : stg == 3 ? flag(cm_td) : flag(cm_dyn) * (one - fr);
+                if constexpr (D::TER) { if (mode == 0) io.cl = io.cl + (one - flag(cm_dyn)) * er; }      // A = (C \ F) u E
                 S ob[6]; V3<S> ol;
                 park(true, ul);
                 wbs_contact_dynamics<Q>(md, 0, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol, &io);
@@ -674,17 +720,34 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                     _Pragma("unroll") for (int i = 0; i < 6; i++) vb[i] = Q::sel(on, ob[i], vb[i]);
                     _Pragma("unroll") for (int j = 0; j < 3; j++) vl[j] = Q::sel(on, o3[j], vl[j]);
                     if (stg == 3) break;
+                    if constexpr (D::TER) {      // T n C leaves F as before; T \ C joins E
+                        const S ts = tl * flag(cm_dyn), te = tl - ts;
+                        fr = fr - ts; nland = nland + ts; er = er + te; nearly = nearly + te;
+                        efirst = Q::sel(Q::gt(Q::sum(te) * Q::sel(Q::gt(zero, efirst), one, zero), S(0.5)), S((double)s), efirst);
+                    } else {
                     fr = fr - tl; nland = nland + tl;      // (T holds feet of live samples only)
+                    }
                     stg = 2;
                     continue;
                 }
                 const WbsUniArgs ua = *wbs_uni_fresh(dist.un);
-                const S att = flag(cm_dyn) * (one - fr);      // the set this solve ran on
+                S att = flag(cm_dyn) * (one - fr);      // the set this solve ran on
+                if constexpr (D::TER) att = att + (one - flag(cm_dyn)) * er;
                 if (stg == 0) {      // landing test at the substep's start state, over the free scheduled stance feet of a live sample
                     const S fc = alive * fr;
                     const typename Q::B isf = Q::gt(fc, S(0.5));
+                    if constexpr (!D::TER) {
                     mlift = Q::sel(isf, wbs_max<Q, S>(mlift, io.pz - ua.z_ground), mlift);
                     tl = fc * Q::sel(Q::gt(io.pz, S(ua.z_ground)), zero, one) * Q::sel(Q::gt(zero, io.wz), one, zero);
+                    } else {      // the same test against the looked-up height, and over the swing feet outside E with the threshold -w_td
+                        const WbsTerArgs ta = *wbs_ter_fresh(dist.te);
+                        const S zg = ua.z_ground + wbs_ter_height(ta, ta.map_of[g], io.px, io.py);
+                        const S sw = alive * (ta.early != 0 ? one : zero) * (one - flag(cm_dyn)) * (one - er);
+                        const S below = Q::sel(Q::gt(io.pz, zg), zero, one);
+                        mlift = Q::sel(isf, wbs_max<Q, S>(mlift, io.pz - zg), mlift);
+                        tl = fc * below * Q::sel(Q::gt(zero, io.wz), one, zero) + sw * below * Q::sel(Q::gt(S(-ta.w_td), io.wz), one, zero);
+                        mpen = Q::sel(Q::gt(tl, S(0.5)), wbs_max<Q, S>(mpen, zg - io.pz), mpen);
+                    }
                     if (wbs_any(Q::sum(tl))) { stg = 1; continue; }
                 }
                 {   // lift-off test: the attached foot with the smallest normal force, lowest leg on a tie, if that force is below fz_rel
@@ -694,8 +757,14 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                         const S lane = Q::legc(0.0, 1.0, 2.0, 3.0);
                         const S pick = Q::vmin(Q::sel(Q::gt(lz, mz), S(4.0), lane));
                         const S rel = need * Q::sel(Q::gt(wbs_abs<Q, S>(lane - pick), S(0.5)), zero, one);
+                        if constexpr (D::TER) {      // a stance foot goes into F, a foot of E simply leaves E
+                            const S rs = rel * flag(cm_dyn), re = rel - rs;
+                            fr = fr + rs; nrel = nrel + rs; er = er - re; nerel = nerel + re;
+                            ufirst = Q::sel(Q::gt(Q::sum(rs) * Q::sel(Q::gt(zero, ufirst), one, zero), S(0.5)), S((double)s), ufirst);
+                        } else {
                         fr = fr + rel; nrel = nrel + rel;
                         ufirst = Q::sel(Q::gt(need * Q::sel(Q::gt(zero, ufirst), one, zero), S(0.5)), S((double)s), ufirst);
+                        }
                         stg = 2;
                         continue;
                     }
@@ -711,6 +780,7 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                     gfmin = Q::sel(on, Q::min(gfmin, lam.z), gfmin); gcmin = Q::sel(on, Q::min(gcmin, cone), gcmin); gfmax = Q::sel(on, wbs_max<Q, S>(gfmax, lam.z), gfmax);
                     gfirst = Q::sel(slip, Q::min(gfirst, S((double)s)), gfirst); gslip = gslip + Q::sel(slip, one, zero);
                     nfree = nfree + alive * fr;
+                    if constexpr (D::TER) nheld = nheld + alive * er;
                     if (ga.Y != nullptr && sub == 0) { Q::st(ga.Y, (g * (size_t)n_steps + s) * 12, 3, lam.x); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 1, 3, lam.y); Q::st(ga.Y, (g * (size_t)n_steps + s) * 12 + 2, 3, lam.z); }
                 }
                 const int nsub = wbs_uniform(wbs_sub_fresh(dist.sb)->substeps);
@@ -810,6 +880,14 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         Q::st0(ua.rows, g * SIM_UNI_ROW + 3, Q::sum(nfree)); Q::st0(ua.rows, g * SIM_UNI_ROW + 4, Q::sum(fr * Q::legc(1.0, 2.0, 4.0, 8.0)));
         Q::st0(ua.rows, g * SIM_UNI_ROW + 5, Q::sel(Q::gt(S(-1e300), top), zero, top));
         if (ua.F != nullptr && (ua.hold == nullptr || ua.hold[g * (size_t)ua.hold_stride] == 0)) Q::st(ua.F, g * 4, 1, fr);
+        if constexpr (D::TER) {      // the terrain row, and E back to where it came from under the same hold
+            const WbsTerArgs ta = *wbs_ter_fresh(dist.te);
+            const S deep = wbs_qmax<Q, S>(mpen);
+            Q::st0(ta.rows, g * SIM_TER_ROW, efirst); Q::st0(ta.rows, g * SIM_TER_ROW + 1, Q::sum(nearly)); Q::st0(ta.rows, g * SIM_TER_ROW + 2, Q::sum(nerel));
+            Q::st0(ta.rows, g * SIM_TER_ROW + 3, Q::sum(nheld)); Q::st0(ta.rows, g * SIM_TER_ROW + 4, Q::sum(er * Q::legc(1.0, 2.0, 4.0, 8.0)));
+            Q::st0(ta.rows, g * SIM_TER_ROW + 5, Q::sel(Q::gt(S(-1e300), deep), zero, deep));
+            if (ta.E != nullptr && (ua.hold == nullptr || ua.hold[g * (size_t)ua.hold_stride] == 0)) Q::st(ta.E, g * 4, 1, er);
+        }
     }
     if (trajX != nullptr) store_state((g * (size_t)(n_steps + 1) + n_steps) * 36);
     _Pragma("unroll") for (int i = 0; i < 6; i++) { Q::st0(xfinal, g * 36 + i, qb[i]); Q::st0(xfinal, g * 36 + 18 + i, vb[i]); }

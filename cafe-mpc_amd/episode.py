@@ -5,6 +5,7 @@ whole-body dynamics, with the simulated state handed to the next solve on the de
     ep.set_grf(0.6)                                                 # optional: contact-force records (include/hsddp_grf.h)
     ep.set_substeps(4)                                              # optional: sub-stepped integration (include/hsddp_substep.h)
     ep.set_contact(0.0, 0.0)                                        # optional: unilateral ground contact (include/hsddp_contact.h)
+    ep.set_terrain(sim.Terrain(H=heights, cx=0.05, cy=0.05, early=True, w_td=0.05))      # optional, with it: terrain and early touchdown (include/hsddp_terrain.h)
     ep.reset(x0)                                                    # [B, 36]; also the solver's initial condition
     solver.solve(opt)
     out = run_mhpc(solver, pd, phases, opt_rt, 50, dist=Disturbance(seed=7, sigma_u=0.2, fall_height=0.12), episode=ep)
@@ -165,6 +166,32 @@ class Episode:
         rc = _abi.bind_contact(self.lib).hsddp_contact_get(self.lib.hsddp_episode_sim(self.e), b0, nb, rows.ctypes.data)
         if rc != 0:
             raise RuntimeError(f"hsddp_contact_get failed rc={rc}")
+        return rows
+
+    def set_terrain(self, terrain, on=True):
+        """Terrain height maps and early swing-foot touchdown (include/hsddp_terrain.h) for every later tick with the contact rule on; `terrain`: a
+        sim.Terrain whose map_of, if given, is int [batch] or [batch, 1].  The swing feet a robot holds are carried from tick to tick and cleared
+        by reset.  on = False: the plane and the scheduled stance feet alone again."""
+        lib = _abi.bind_terrain(self.lib)
+        if not on:
+            rc = lib.hsddp_terrain_set(self.lib.hsddp_episode_sim(self.e), 0, None, None, None)
+        else:
+            H = terrain.grid()
+            mo = None if terrain.map_of is None else np.ascontiguousarray(terrain.map_of, dtype=np.int32).reshape(-1)
+            if mo is not None and mo.shape != (self.solver.batch,):
+                raise ValueError(f"Terrain.map_of has {mo.size} entries, not {self.solver.batch}")
+            t = terrain.to_c()
+            rc = lib.hsddp_terrain_set(self.lib.hsddp_episode_sim(self.e), 1, C.byref(t), H.ctypes.data, None if mo is None else mo.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_terrain_set failed rc={rc}")
+
+    def terrain_rows(self, b0=0, nb=None):
+        """Structured array [nb] of hsddp_terrain_row_t of the last tick, which has to be one with the contact rule and the terrain on."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0),), dtype=_abi.TERRAIN_ROW_DTYPE)
+        rc = _abi.bind_terrain(self.lib).hsddp_terrain_get(self.lib.hsddp_episode_sim(self.e), b0, nb, rows.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_terrain_get failed rc={rc}")
         return rows
 
     @property

@@ -23,6 +23,7 @@
 #include "hsddp_grf.h"
 #include "hsddp_substep.h"
 #include "hsddp_contact.h"
+#include "hsddp_terrain.h"
 #include "hsddp_episode.h"
 
 namespace hsddp {
@@ -75,6 +76,11 @@ public:
     bool set_contact(bool on, double fz_rel = 0.0, double z_ground = 0.0) { rc_ = s_ ? hsddp_contact_set(s_, on ? 1 : 0, fz_rel, z_ground) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // rows of the last run, which has to be one with the rule on: batch x n_samples
     bool contact(hsddp_contact_row_t* rows) { rc_ = s_ ? hsddp_contact_get(s_, 0, batch_, rows) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // terrain height maps and early swing-foot touchdown for every later run with the contact rule on (include/hsddp_terrain.h): H [n_maps][ny][nx] and
+    // map_of [batch][n_samples] (or null: map 0) are host arrays, copied by the call; on = false ignores the rest
+    bool set_terrain(bool on, const hsddp_terrain_t* t = nullptr, const double* H = nullptr, const int* map_of = nullptr) { rc_ = s_ ? hsddp_terrain_set(s_, on ? 1 : 0, t, H, map_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // rows of the last run, which has to be one with the contact rule and the terrain on: batch x n_samples
+    bool terrain(hsddp_terrain_row_t* rows) { rc_ = s_ ? hsddp_terrain_get(s_, 0, batch_, rows) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // the records of the last run alone (result() holds them too): rows batch x n_samples, Y batch x n_samples x n_steps x 12 or null
     bool grf(hsddp_grf_row_t* rows, double* Y = nullptr) { rc_ = s_ ? hsddp_grf_get(s_, 0, batch_, rows, Y) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     SimResult result() {
@@ -126,6 +132,8 @@ public:
     bool set_substeps(int substeps) { rc_ = e_ ? hsddp_substep_set(hsddp_episode_sim(e_), substeps) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // unilateral ground contact for every later tick; the free feet are carried from tick to tick (include/hsddp_contact.h)
     bool set_contact(bool on, double fz_rel = 0.0, double z_ground = 0.0) { rc_ = e_ ? hsddp_contact_set(hsddp_episode_sim(e_), on ? 1 : 0, fz_rel, z_ground) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // terrain and early touchdown for every later tick; the swing feet a robot holds are carried from tick to tick (include/hsddp_terrain.h)
+    bool set_terrain(bool on, const hsddp_terrain_t* t = nullptr, const double* H = nullptr, const int* map_of = nullptr) { rc_ = e_ ? hsddp_terrain_set(hsddp_episode_sim(e_), on ? 1 : 0, t, H, map_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     std::vector<hsddp_episode_row_t> rows(std::vector<double>* x_now = nullptr) {
         std::vector<hsddp_episode_row_t> r((size_t)batch_);
         if (x_now) x_now->resize((size_t)batch_ * 36);

@@ -16,8 +16,11 @@
 
     res = solver.simulate(x0, n_steps=50, contact=(0.0, 0.0))      # include/hsddp_contact.h: the ground only pushes; res["contact"]["n_release"], ["n_land"]
 
+    ter = Terrain(H=heights, x0=-1.0, y0=-1.0, cx=0.05, cy=0.05, early=True, w_td=0.05, map_of=maps)      # include/hsddp_terrain.h: H [n_maps, ny, nx]
+    res = solver.simulate(x0, n_steps=50, contact=(0.0, 0.0), terrain=ter)      # res["terrain"]["n_early"], ["max_pen"]
+
 Nothing here computes anything: the rollout is the k_sim_quad / k_sim_quad_mc kernel (csrc/wb_sim.hpp).  mc_normals states the generator of the
-disturbed runs in numpy, grf_rows the contact-force records and grf_rows_sub those of a sub-stepped run: the definitions the kernel mirrors."""
+disturbed runs in numpy, grf_rows the contact-force records and grf_rows_sub those of a sub-stepped run, terrain_height the height lookup of a terrain: the definitions the kernel mirrors."""
 import ctypes as C
 import dataclasses
 
@@ -41,6 +44,43 @@ class Disturbance:
 
     def to_c(self):
         return _abi.McDist(self.seed & ((1 << 64) - 1), self.sigma_u, self.sigma_q, self.sigma_v, self.u_max, self.fall_height, self.kick_step, self.first_problem)
+
+
+@dataclasses.dataclass
+class Terrain:
+    """hsddp_terrain_t with its grid (include/hsddp_terrain.h): H [n_maps, ny, nx] heights above z_ground (a [ny, nx] array is one map), origin
+    (x0, y0), cell size (cx, cy); early: swing feet land when they reach the ground, moving down faster than w_td; map_of: None (map 0 for every
+    sample) or int [batch, n_samples]."""
+    H: np.ndarray
+    x0: float = 0.0
+    y0: float = 0.0
+    cx: float = 1.0
+    cy: float = 1.0
+    early: bool = False
+    w_td: float = 0.0
+    map_of: np.ndarray = None
+
+    def grid(self):
+        H = np.ascontiguousarray(self.H, dtype=np.float64)
+        return H[None] if H.ndim == 2 else H
+
+    def to_c(self):
+        H = self.grid()
+        if H.ndim != 3:
+            raise ValueError(f"Terrain: H has shape {H.shape}")
+        return _abi.TerrainParams(H.shape[2], H.shape[1], H.shape[0], 1 if self.early else 0, self.x0, self.y0, self.cx, self.cy, self.w_td)
+
+
+def terrain_height(terrain, p_xy, m=0):
+    """Height of map m of `terrain` above z_ground at the points p_xy [..., 2]: the definition of the lookup.  ix = clamp(floor((p_x - x0) / cx), 0,
+    nx - 1), iy likewise, H[m, iy, ix]: outside the grid the edge cell holds, and a NaN coordinate reads cell 0 (fmax / fmin drop a NaN).  m: an int
+    or an int array broadcastable to p_xy's leading shape."""
+    H = terrain.grid()
+    p = np.asarray(p_xy, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ix = np.fmin(np.fmax(np.floor((p[..., 0] - terrain.x0) / terrain.cx), 0.0), H.shape[2] - 1.0).astype(np.int64)
+        iy = np.fmin(np.fmax(np.floor((p[..., 1] - terrain.y0) / terrain.cy), 0.0), H.shape[1] - 1.0).astype(np.int64)
+    return H[np.asarray(m, dtype=np.int64), iy, ix]
 
 
 def mc_normals(seed, problem, r, s):
@@ -116,6 +156,7 @@ class Simulation:
         self.disturbed = False
         self.grf_on = False
         self.contact_on = False
+        self.terrain_on = False
         self.solver, self.R, self.n_steps, self.keep_traj = solver, int(n_samples), int(n_steps), bool(keep_traj)
         self.s = C.c_void_p()
         rc = self.lib.hsddp_sim_create(solver.h, self.R, self.n_steps, 1 if keep_traj else 0, C.byref(self.s))
@@ -222,6 +263,44 @@ class Simulation:
             raise RuntimeError(f"hsddp_contact_get failed rc={rc}")
         return rows
 
+    def set_terrain(self, terrain):
+        """Terrain height maps and early swing-foot touchdown (include/hsddp_terrain.h) for every later run with the contact rule on; `terrain`: a
+        Terrain.  The grid and the map table are copied."""
+        H = terrain.grid()
+        mo = None if terrain.map_of is None else np.ascontiguousarray(terrain.map_of, dtype=np.int32)
+        if mo is not None and mo.shape != (self.solver.batch, self.R):
+            raise ValueError(f"Terrain.map_of has shape {mo.shape}, not {(self.solver.batch, self.R)}")
+        t = terrain.to_c()
+        rc = _abi.bind_terrain(self.lib).hsddp_terrain_set(self.s, 1, C.byref(t), H.ctypes.data, None if mo is None else mo.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_terrain_set failed rc={rc}")
+        self.terrain_on = True
+
+    def clear_terrain(self):
+        """Later runs stand on the plane z_ground again and test scheduled stance feet only (the kernels without the terrain)."""
+        rc = _abi.bind_terrain(self.lib).hsddp_terrain_set(self.s, 0, None, None, None)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_terrain_set failed rc={rc}")
+        self.terrain_on = False
+
+    @property
+    def terrain(self):
+        """(on, dict of nx, ny, n_maps, early, x0, y0, cx, cy, w_td) as later runs use them (hsddp_terrain_get_params)."""
+        on = C.c_int(); t = _abi.TerrainParams()
+        rc = _abi.bind_terrain(self.lib).hsddp_terrain_get_params(self.s, C.byref(on), C.byref(t))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_terrain_get_params failed rc={rc}")
+        return bool(on.value), {f: getattr(t, f) for f, _ in _abi.TerrainParams._fields_}
+
+    def terrain_rows(self, b0=0, nb=None):
+        """Structured array [nb, R] of hsddp_terrain_row_t of the last run, which has to be one with the contact rule and the terrain on."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0), self.R), dtype=_abi.TERRAIN_ROW_DTYPE)
+        rc = _abi.bind_terrain(self.lib).hsddp_terrain_get(self.s, b0, nb, rows.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_terrain_get failed rc={rc}")
+        return rows
+
     @property
     def substeps(self):
         """What later runs use, as the library reports it (hsddp_substep_get)."""
@@ -272,11 +351,12 @@ class Simulation:
         return float(ms.value)
 
 
-def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None):
+def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None):
     """One-off simulation on `solver`: dict with rows, x_final and, with keep_traj, X and U (see Simulation); a disturbed run (dist / kick given)
     returns extra too; grf = (mu, fz_min) adds the contact-force records grf and, with keep_traj, Y; substeps = S > 1 integrates every control
     knot in S steps (include/hsddp_substep.h); contact = (fz_rel, z_ground) switches unilateral ground contact on (include/hsddp_contact.h) and
-    adds the rows contact."""
+    adds the rows contact; terrain = Terrain(...) beside it switches height maps and early touchdown on (include/hsddp_terrain.h) and adds the rows
+    terrain."""
     sim = Simulation(solver, x0.shape[1], n_steps, keep_traj)
     try:
         if substeps != 1:
@@ -285,6 +365,8 @@ def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=Non
             sim.set_grf(*grf)
         if contact is not None:
             sim.set_contact(*contact)
+        if terrain is not None:
+            sim.set_terrain(terrain)
         sim.run(x0, dist=dist, kick=kick)
         rows, xf = sim.rows()
         out = dict(rows=rows, x_final=xf)
@@ -299,6 +381,8 @@ def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=Non
                 out["grf"] = sim.grf()
         if sim.contact_on:
             out["contact"] = sim.contact_rows()
+        if sim.contact_on and sim.terrain_on:
+            out["terrain"] = sim.terrain_rows()
         return out
     finally:
         sim.close()

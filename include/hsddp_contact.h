@@ -49,9 +49,10 @@
  *   - hsddp_contact_get returns the rows of the LAST run; HSDDP_EINVAL if that run had the rule off, for a bad range or a NULL argument.
  *   - hsddp_episode_sim(e) is accepted, as for hsddp_grf_set and hsddp_substep_set.  Its rows are those of the last tick.
  *
- * Out of scope: sliding friction (cone violations are still only counted, the foot does not slide); early touchdown of a SWING foot (only
- * scheduled stance feet are tested against the ground); terrain (the ground is one plane); negative impulses in impacts (the impact map is the
- * bilateral one on T, whatever sign its impulse has); fp32 handles and windows that do not lead with whole-body knots.
+ * Out of scope: sliding friction (cone violations are still only counted, the foot does not slide); negative impulses in impacts (the impact map is
+ * the bilateral one on T, whatever sign its impulse has); fp32 handles and windows that do not lead with whole-body knots.  Early touchdown of a SWING
+ * foot (here only scheduled stance feet are tested against the ground) and terrain (here the ground is one plane) are include/hsddp_terrain.h, which
+ * extends the rules above.
  */
 #ifndef HSDDP_CONTACT_H
 #define HSDDP_CONTACT_H
