@@ -16,7 +16,7 @@ from . import ensemble  # noqa: F401
 from .ensemble import ScheduleEnsemble, select_rows  # noqa: F401
 from . import hkd_command  # noqa: F401
 from . import sim  # noqa: F401
-from .sim import Simulation, Terrain  # noqa: F401
+from .sim import Simulation, Terrain, Plant  # noqa: F401
 from . import episode  # noqa: F401
 from .episode import Episode  # noqa: F401
 

@@ -348,6 +348,28 @@ def bind_terrain(lib):
     return lib
 
 
+# include/hsddp_plant.h: per-sample plant-model mismatch in a simulation object (libhsddp_hip.so only).  A list and a binder of their own, as above.
+PLANT_EXPORTS = ["hsddp_plant_set", "hsddp_plant_get_params", "hsddp_plant_get_table"]
+PLANT_ROW = 46        # HSDDP_PLANT_ROW
+PLANT_MAX = 65536     # HSDDP_PLANT_MAX
+# the slices of a row: trunk mass | trunk CoM | trunk inertia about the CoM (xx, xy, xz, yy, yz, zz) | link_scale | tau_gain | damping
+PLANT_SLICES = dict(mass=slice(0, 1), com=slice(1, 4), inertia=slice(4, 10), link_scale=slice(10, 22), tau_gain=slice(22, 34), damping=slice(34, 46))
+PLANT_NOMINAL = (3.3, 0.0, 0.0, 0.0, 0.011253, 0.0, 0.0, 0.036203, 0.0, 0.042673) + (1.0,) * 24 + (0.0,) * 12
+
+
+def bind_plant(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_plant.h (and of hsddp_terrain.h, which it includes).  Raises if the library lacks any."""
+    missing = [s for s in PLANT_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the plant entry points {missing}")
+    bind_terrain(lib)
+    H = C.c_void_p
+    lib.hsddp_plant_set.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.hsddp_plant_get_params.argtypes = [H, IP, IP]
+    lib.hsddp_plant_get_table.argtypes = [H, C.c_int, C.c_int, C.c_void_p]
+    return lib
+
+
 # include/hsddp_episode.h: batched closed-loop MPC episodes (libhsddp_hip.so only)
 EPISODE_EXPORTS = ["hsddp_episode_create", "hsddp_episode_destroy", "hsddp_episode_reset", "hsddp_episode_advance", "hsddp_episode_get_rows",
                    "hsddp_episode_get_log", "hsddp_episode_device_state", "hsddp_episode_sim", "hsddp_episode_status"]
@@ -640,7 +662,7 @@ class Solver:
                  "get_references")
         return out
 
-    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None):
+    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None, plant=None):
         """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)
         over the first n_steps whole-body control knots (include/hsddp_sim.h): dict with rows (structured array [batch, R] of dev_q, dev_v,
         min_height, max_torque, first_bad), x_final [batch, R, 36] and, with keep_traj, X [batch, R, n_steps + 1, 36] and U [batch, R, n_steps, 12].
@@ -652,9 +674,10 @@ class Solver:
         unilateral ground contact (include/hsddp_contact.h), which also returns contact (structured array [batch, R] of first_release, n_release,
         n_land, n_free, free_final, max_lift).  terrain = sim.Terrain(...), with contact: height maps and early swing-foot touchdown
         (include/hsddp_terrain.h), which also returns terrain (structured array [batch, R] of first_early, n_early, n_early_release, n_held,
-        early_final, max_pen)."""
+        early_final, max_pen).  plant = sim.Plant(...): a plant row per sample - trunk and link inertias, torque gain, joint friction
+        (include/hsddp_plant.h); no new output, the existing ones show the effect."""
         from . import sim
-        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps, contact=contact, terrain=terrain)
+        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps, contact=contact, terrain=terrain, plant=plant)
 
     def episode(self, n_exec, max_ticks, keep_log=False):
         """An episode.Episode on this solver (include/hsddp_episode.h): batched closed-loop MPC ticks with the simulated state handed to the next

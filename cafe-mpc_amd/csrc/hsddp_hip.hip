@@ -23,6 +23,7 @@
 #include "hsddp_substep.h"
 #include "hsddp_contact.h"
 #include "hsddp_terrain.h"
+#include "hsddp_plant.h"
 #include "hsddp_mc.h"
 #include "hsddp_episode.h"
 #include "hs_types.hpp"
@@ -1695,6 +1696,19 @@ void wbs_ter_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const
 #else
 #include "hsddp_ter.hip"
 #endif
+// The kernels with a per-sample plant and their launchers (hsddp_plant.h): hsddp_plant.hip, likewise (-DHS_PLANT_SEPARATE here).
+#include "plant_host.hpp"
+#ifdef HS_PLANT_SEPARATE
+namespace hs {
+void wbs_plant_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
+                      double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un,
+                      const WbsTerArgs* te, const WbsPlantArgs* pl);
+void wbs_plant_impact_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, int pi, int total, const int* frozen, int stride, double* state, double* x0,
+                             const WbsPlantArgs* pl);
+}
+#else
+#include "hsddp_plant.hip"
+#endif
 struct hsddp_sim {
     hsddp_handle* h = nullptr;
     int R = 0, n_steps = 0, keep = 0, gen = 0;
@@ -1723,13 +1737,20 @@ struct hsddp_sim {
     bool ter_on = false, last_ter = false;
     hsddp_terrain_t ter = {};
     WbsTerArgs* d_ter = nullptr; double *d_ter_H = nullptr, *d_ter_rows = nullptr, *d_ter_E = nullptr; int* d_ter_map = nullptr; size_t ter_cap = 0;
+    // per-sample plant (hsddp_plant.h): allocated by hsddp_plant_set calls that switch it on (the table again when it grows: plant_cap rows).  plant_on:
+    // what later runs do.  plant_rows: the host's copy of the table, for hsddp_plant_get_table.  The _plant walks always keep the force records and read
+    // the trip count from the device: while hsddp_grf_set has the records off they go to d_uni_grows through d_uni_grf (the buffer the walks with the
+    // contact rule use for the same purpose), and d_sub is made current by the set call as hsddp_contact_set does
+    bool plant_on = false; int n_plants = 0;
+    WbsPlantArgs* d_plant = nullptr; double* d_plant_P = nullptr; int* d_plant_of = nullptr; size_t plant_cap = 0;
+    std::vector<double> plant_rows;
 };
 static void sim_free(hsddp_sim* s) {
     if (!s) return;
     hipSetDevice(s->h->device);
     if (s->h->stream) hipStreamSynchronize(s->h->stream);
     void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf, s->d_sub, s->d_uni, s->d_uni_rows, s->d_uni_F, s->d_uni_grows, s->d_uni_grf,
-                 s->d_ter, s->d_ter_H, s->d_ter_rows, s->d_ter_E, s->d_ter_map};
+                 s->d_ter, s->d_ter_H, s->d_ter_rows, s->d_ter_E, s->d_ter_map, s->d_plant, s->d_plant_P, s->d_plant_of};
     for (void* q : p) if (q) hipFree(q);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -1796,7 +1817,11 @@ static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, b
     if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
     HIPCK(hipEventRecord(s->ev0, h->stream));
     const bool ter = s->uni_on && s->ter_on;      // (hsddp_terrain.h: dormant while the contact rule is off)
-    if (ter) {
+    if (s->plant_on) {      // (hsddp_plant.h) the _plant twin of the family the other switches select; records and trip count always
+        wbs_plant_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
+                         s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : (const WbsGrfArgs*)s->d_uni_grf,
+                         s->d_sub, s->uni_on ? (const WbsUniArgs*)s->d_uni : nullptr, ter ? (const WbsTerArgs*)s->d_ter : nullptr, s->d_plant);
+    } else if (ter) {
         wbs_ter_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
                        s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : (const WbsGrfArgs*)s->d_uni_grf,
                        s->d_sub, s->d_uni, s->d_ter);
@@ -2074,6 +2099,63 @@ int hsddp_terrain_get(hsddp_sim_t* s, int b0, int nb, hsddp_terrain_row_t* rows)
     return HSDDP_OK;
 }
 
+int hsddp_plant_set(hsddp_sim_t* s, int on, int n_plants, const double* P, const int* plant_of) {
+    if (!s) return HSDDP_EINVAL;
+    if (!on) { s->plant_on = false; return HSDDP_OK; }      // later runs launch the kernels without the plant; the buffers and the table are kept
+    hsddp_handle* h = s->h;
+    const size_t total = (size_t)h->batch * s->R;
+    if (!plant_table_ok(n_plants, P, plant_of, total)) return HSDDP_EINVAL;
+    if (h->f32) return HSDDP_ENOTSUP;
+    HIPCK(hipSetDevice(h->device));
+    std::vector<double> rows; std::vector<int> idx;
+    plant_table_pack(n_plants, P, plant_of, total, rows, idx);
+    // (as TER_CK of hsddp_terrain_set: an allocation that fails returns its code at once, what was made before it is kept, and the plant stays as it was)
+#define PLANT_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
+    if (!s->d_plant) PLANT_CK(hipMalloc((void**)&s->d_plant, sizeof(WbsPlantArgs)));
+    if (!s->d_plant_of) PLANT_CK(hipMalloc((void**)&s->d_plant_of, total * sizeof(int)));
+    if (!s->d_uni_grows) PLANT_CK(hipMalloc((void**)&s->d_uni_grows, total * SIM_GRF_ROW * 8));
+    if (!s->d_uni_grf) {
+        PLANT_CK(hipMalloc((void**)&s->d_uni_grf, sizeof(WbsGrfArgs)));
+        WbsGrfArgs g;
+        g.mu = 1.0; g.fz_min = 0.0; g.rows = s->d_uni_grows; g.Y = nullptr;      // (nobody reads these records: hsddp_grf_get refuses while the records are off)
+        HIPCK(hipMemcpyAsync(s->d_uni_grf, &g, sizeof(g), hipMemcpyHostToDevice, h->stream));
+    }
+    if (!s->d_sub) {      // the walk reads its trip count from here for S = 1 too; from now on hsddp_substep_set keeps it current
+        PLANT_CK(hipMalloc((void**)&s->d_sub, sizeof(WbsSubArgs)));
+        WbsSubArgs b;
+        b.substeps = s->substeps; b.pad = 0;
+        HIPCK(hipMemcpyAsync(s->d_sub, &b, sizeof(b), hipMemcpyHostToDevice, h->stream));
+    }
+    if ((size_t)n_plants > s->plant_cap) {      // the table grows: the new block first, so that a failure leaves the old one in place
+        double* nb = nullptr;
+        PLANT_CK(hipMalloc((void**)&nb, (size_t)n_plants * SIM_PLANT_ROW * 8));
+        HIPCK(hipStreamSynchronize(h->stream));
+        if (s->d_plant_P) hipFree(s->d_plant_P);
+        s->d_plant_P = nb; s->plant_cap = (size_t)n_plants;
+    }
+#undef PLANT_CK
+    HIPCK(hipMemcpyAsync(s->d_plant_P, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipMemcpyAsync(s->d_plant_of, idx.data(), total * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    WbsPlantArgs a;
+    a.P = s->d_plant_P; a.plant_of = s->d_plant_of; a.n_plants = n_plants; a.pad = 0;
+    HIPCK(hipMemcpyAsync(s->d_plant, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));      // the sources are locals and the caller's: they may go once the call returns
+    s->plant_on = true; s->n_plants = n_plants; s->plant_rows.swap(rows);
+    return HSDDP_OK;
+}
+
+int hsddp_plant_get_params(hsddp_sim_t* s, int* on, int* n_plants) {
+    if (!s || !on || !n_plants) return HSDDP_EINVAL;
+    *on = s->plant_on ? 1 : 0; *n_plants = s->n_plants;
+    return HSDDP_OK;
+}
+
+int hsddp_plant_get_table(hsddp_sim_t* s, int p0, int np, double* P) {
+    if (!s || !P || np <= 0 || p0 < 0 || p0 > s->n_plants - np) return HSDDP_EINVAL;
+    memcpy(P, s->plant_rows.data() + (size_t)p0 * SIM_PLANT_ROW, (size_t)np * SIM_PLANT_ROW * 8);
+    return HSDDP_OK;
+}
+
 const double* hsddp_sim_device_final(hsddp_sim_t* s) { return s ? s->d_final : nullptr; }
 
 int hsddp_sim_get_kernel_time_ms(hsddp_sim_t* s, float* ms) {
@@ -2199,7 +2281,10 @@ int hsddp_episode_advance(hsddp_episode_t* e, const hsddp_mc_dist_t* dist, const
     // (both kernels are timed into the handle's kernel table, hsddp_get_kernel_times, like the solver's; the walk's time is the simulation object's)
     { Timed t(h, "k_episode_commit"); hipLaunchKernelGGL(k_episode_commit, dim3((unsigned)h->batch), dim3(64), 0, h->stream, h->d_ph, a); }
     if (e->pending >= 0) {      // the tick ended on a touchdown: the reset map the moved window no longer holds
-        Timed t(h, "k_episode_impact");
+        Timed t(h, s->plant_on ? "k_episode_impact_plant" : "k_episode_impact");
+        if (s->plant_on)      // (hsddp_plant.h) the same map with each robot's own inertias
+            wbs_plant_impact_launch(h->stream, (unsigned)((h->batch + 15) / 16), h->d_ph, h->md, e->pending, h->batch, &e->d_rows[0].end_reason, (int)(sizeof(EpiRow) / sizeof(int)), e->d_state, h->d_x0, s->d_plant);
+        else
         hipLaunchKernelGGL(k_episode_impact, dim3((unsigned)((h->batch + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, e->pending, h->batch, (const EpiRow*)e->d_rows, e->d_state, h->d_x0);
         e->n_impacts++;
     }

@@ -74,6 +74,36 @@ template <class S> struct WbsTerIO { S cl, pz, wz, px, py; V3<S> lam; };
 template <class T> struct wbs_is_ter_io { static constexpr bool value = false; };
 template <class S> struct wbs_is_ter_io<WbsTerIO<S>> { static constexpr bool value = true; };
 template <class Q, class S> HD S wbs_lane_flag(int, WbsTerIO<S>* io) { return io->cl; }
+// Plant-model mismatch (include/hsddp_plant.h): the exchange of WbsTerIO plus `row`, the quad's row of the plant table (HSDDP_PLANT_ROW doubles).  A solve
+// with this element reads the trunk's and the links' inertias from the row WHERE IT USES THEM (the trunk's ten values at the IT sum and at the trunk's own
+// link_force, the lane's three link scales at the composite inertias and again at the bias pass) instead of the literals; gain and friction are the
+// walk's business.  An element type of its own again: every solve without it instantiates what it instantiated before this one existed.
+template <class S> struct WbsPlantIO { S cl, pz, wz, px, py; V3<S> lam; const double* row; };
+template <class T> struct wbs_is_plant_io { static constexpr bool value = false; };
+template <class S> struct wbs_is_plant_io<WbsPlantIO<S>> { static constexpr bool value = true; };
+template <class Q, class S> HD S wbs_lane_flag(int, WbsPlantIO<S>* io) { return io->cl; }
+template <class... LO> HD const double* wbs_plant_row(LO*...) { return nullptr; }
+template <class S> HD const double* wbs_plant_row(WbsPlantIO<S>* io) { return io->row; }
+// rbi_link with a mass that is a value of the lane (wb_quad.hpp's takes a literal): the same operations in the same order
+template <class S> HD RBI<S> wbs_plant_link(S m, S cx, S cy, S cz, S ixx, S ixy, S ixz, S iyy, S iyz, S izz) {
+    RBI<S> R; R.m = m; R.h = {m * cx, m * cy, m * cz};
+    const S cc = cx * cx + cy * cy + cz * cz;
+    R.I = {ixx + m * (cc - cx * cx), ixy - m * (cx * cy), ixz - m * (cx * cz), iyy + m * (cc - cy * cy), iyz - m * (cy * cz), izz + m * (cc - cz * cz)};
+    return R;
+}
+// wbs_pick<true>(a, b) is a, wbs_pick<false>(a, b) is b: a solve without the plant keeps every statement it had, where it had it
+template <bool FIRST, class T> HD const T& wbs_pick(const T& a, const T& b) { if constexpr (FIRST) return a; else return b; }
+// the trunk of a plant row about the trunk origin: entries 0 .. 9 (mass, CoM, inertia about the CoM), the same address in every lane
+template <class Q, class S> HD RBI<S> wbs_plant_trunk(const double* pr) {
+    return wbs_plant_link<S>(Q::ld(pr, 0, 0), Q::ld(pr, 1, 0), Q::ld(pr, 2, 0), Q::ld(pr, 3, 0), Q::ld(pr, 4, 0), Q::ld(pr, 5, 0), Q::ld(pr, 6, 0), Q::ld(pr, 7, 0), Q::ld(pr, 8, 0), Q::ld(pr, 9, 0));
+}
+// the lane's three links with mass and CoM inertia scaled by entries 10 + 3 leg + (0, 1, 2) of the row; CoM and geometry stay
+template <class Q, class S> HD void wbs_plant_leg_links(const double* pr, const S& sy, RBI<S>& Iab, RBI<S>& Ith, RBI<S>& Ikn) {
+    const S zero = S(0.0), sa = Q::ld(pr, 10, 3), sh = Q::ld(pr, 11, 3), sk = Q::ld(pr, 12, 3);
+    Iab = wbs_plant_link<S>(sa * 0.54, zero, sy * 0.036, zero, sa * 0.000381, sa * (sy * 0.000058), sa * 0.00000045, sa * 0.000560, sa * (sy * 0.00000095), sa * 0.000444);
+    Ith = wbs_plant_link<S>(sh * 0.634, zero, sy * 0.016, S(-0.02), sh * 0.001983, sh * (sy * 0.000245), sh * 0.000013, sh * 0.002103, sh * (sy * 0.0000015), sh * 0.000408);
+    Ikn = wbs_plant_link<S>(sk * 0.064, zero, zero, S(-0.061), sk * 0.000245, zero, zero, sk * 0.000248, zero, sk * 0.000006);
+}
 template <class Q, class S = typename Q::S, class... LO>
 HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double damping, double bg_alpha, const S (&qb)[6], const S (&vb)[6], const S (&ql)[3],
                              const S (&vl_)[3], const S (&ul)[3], S (&out_b)[6], V3<S>& out_l, LO*... lam_out) {
@@ -91,16 +121,24 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
     const V3<S> pa = {sx * 0.19, sy * 0.049, S(0.0)}, ph = {S(0.0), sy * 0.062, S(0.0)}, pk = {S(0.0), S(0.0), S(-0.209)};
 
     // ---- composite inertias, leg -> trunk (frames: K shank, H thigh, A abad, B trunk; v_H = Ry(qk) v_K, v_A = Rz(psi) Ry(qh) v_H, v_B = Rx(qa) v_A)
-    const RBI<S> IK = rbi_link<S>(0.064, zero, zero, S(-0.061), S(0.000245), zero, zero, S(0.000248), zero, S(0.000006));
-    RBI<S> IH = rbi_link<S>(0.634, zero, sy * 0.016, S(-0.02), S(0.001983), sy * 0.000245, S(0.000013), S(0.002103), sy * 0.0000015, S(0.000408));
+    constexpr bool PLANT = (wbs_is_plant_io<LO>::value || ...);      // (hsddp_plant.h) the inertias come from the quad's plant row
+    RBI<S> pA, pH, pK;      // (plant only) the lane's three links of the row; wbs_pick takes them instead of the literals' links
+    if constexpr (PLANT) wbs_plant_leg_links<Q, S>(wbs_plant_row(lam_out...), sy, pA, pH, pK);
+    const RBI<S> IK = wbs_pick<PLANT>(pK, rbi_link<S>(0.064, zero, zero, S(-0.061), S(0.000245), zero, zero, S(0.000248), zero, S(0.000006)));
+    RBI<S> IH = wbs_pick<PLANT>(pH, rbi_link<S>(0.634, zero, sy * 0.016, S(-0.02), S(0.001983), sy * 0.000245, S(0.000013), S(0.002103), sy * 0.0000015, S(0.000408)));
     IH = rbi_add(IH, rbi_shift(IK.m, rot<1>(ck, sk, IK.h), sym_rot<1>(ck, sk, IK.I), pk));
-    RBI<S> IA = rbi_link<S>(0.54, zero, sy * 0.036, zero, S(0.000381), sy * 0.000058, S(0.00000045), S(0.000560), sy * 0.00000095, S(0.000444));
+    RBI<S> IA = wbs_pick<PLANT>(pA, rbi_link<S>(0.54, zero, sy * 0.036, zero, S(0.000381), sy * 0.000058, S(0.00000045), S(0.000560), sy * 0.00000095, S(0.000444)));
     IA = rbi_add(IA, rbi_shift(IH.m, rot<2>(S(cps), S(sps), rot<1>(ch, sh, IH.h)), sym_rot<2>(S(cps), S(sps), sym_rot<1>(ch, sh, IH.I)), ph));
     const RBI<S> IBl = rbi_shift(IA.m, rot<0>(ca, sa, IA.h), sym_rot<0>(ca, sa, IA.I), pa);
     // whole robot about the trunk origin: trunk + the four legs (sums over the quad)
     RBI<S> IT;
     IT.m = Q::sum(IBl.m) + 3.3; IT.h = {Q::sum(IBl.h.x), Q::sum(IBl.h.y), Q::sum(IBl.h.z)};
     IT.I = {Q::sum(IBl.I.xx) + 0.011253, Q::sum(IBl.I.xy), Q::sum(IBl.I.xz), Q::sum(IBl.I.yy) + 0.036203, Q::sum(IBl.I.yz), Q::sum(IBl.I.zz) + 0.042673};
+    if constexpr (PLANT) {      // the row's trunk instead of the literals' (which the compiler drops)
+        const RBI<S> It0 = wbs_plant_trunk<Q, S>(wbs_plant_row(lam_out...));
+        IT.m = Q::sum(IBl.m) + It0.m; IT.h = {Q::sum(IBl.h.x) + It0.h.x, Q::sum(IBl.h.y) + It0.h.y, Q::sum(IBl.h.z) + It0.h.z};
+        IT.I = {Q::sum(IBl.I.xx) + It0.I.xx, Q::sum(IBl.I.xy) + It0.I.xy, Q::sum(IBl.I.xz) + It0.I.xz, Q::sum(IBl.I.yy) + It0.I.yy, Q::sum(IBl.I.yz) + It0.I.yz, Q::sum(IBl.I.zz) + It0.I.zz};
+    }
     // ---- mass-matrix blocks of the leg: D (3x3, joints abad / hip / knee) and Ct[c][j] = M(base joint c, leg joint j)
     S Ct[6][3], d_aa, d_ha, d_hh, d_ka, d_kh, d_kk;
     {
@@ -174,19 +212,21 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
             n = n + cross(o, ha) + cross(v, hl_);
         };
         // trunk (own link only; its wrench joins the legs' in the quad sum, so only lane 0's copy is counted)
-        const RBI<S> Itr = rbi_link<S>(3.3, zero, zero, zero, S(0.011253), zero, zero, S(0.036203), zero, S(0.042673));
+        RBI<S> pT, qA, qH, qK;      // (plant only) the trunk and the lane's links, formed again from the row: cheaper than carrying them from the composite pass
+        if constexpr (PLANT) { pT = wbs_plant_trunk<Q, S>(wbs_plant_row(lam_out...)); wbs_plant_leg_links<Q, S>(wbs_plant_row(lam_out...), sy, qA, qH, qK); }
+        const RBI<S> Itr = wbs_pick<PLANT>(pT, rbi_link<S>(3.3, zero, zero, zero, S(0.011253), zero, zero, S(0.036203), zero, S(0.042673)));
         V3<S> nb, fb; link_force(Itr, om, vl, aa, al, nb, fb);
         const S l0 = Q::legc(1.0, 0.0, 0.0, 0.0);
         nb = scale(l0, nb); fb = scale(l0, fb);
         // down the leg
         V3<S> o1 = om, a1 = aa, v1 = vl + cross(om, pa), l1 = al + cross(aa, pa);
         revj(A0{}, ca, sa, vl_[0], o1, v1, a1, l1);
-        const RBI<S> Iab = rbi_link<S>(0.54, zero, sy * 0.036, zero, S(0.000381), sy * 0.000058, S(0.00000045), S(0.000560), sy * 0.00000095, S(0.000444));
+        const RBI<S> Iab = wbs_pick<PLANT>(qA, rbi_link<S>(0.54, zero, sy * 0.036, zero, S(0.000381), sy * 0.000058, S(0.00000045), S(0.000560), sy * 0.00000095, S(0.000444)));
         V3<S> n1, f1; link_force(Iab, o1, v1, a1, l1, n1, f1);
         V3<S> o2 = o1, a2 = a1, v2 = v1 + cross(o1, ph), l2 = l1 + cross(a1, ph);
         o2 = rotT<2>(S(cps), S(sps), o2); v2 = rotT<2>(S(cps), S(sps), v2); a2 = rotT<2>(S(cps), S(sps), a2); l2 = rotT<2>(S(cps), S(sps), l2);
         revj(A1{}, ch, sh, vl_[1], o2, v2, a2, l2);
-        const RBI<S> Ith = rbi_link<S>(0.634, zero, sy * 0.016, S(-0.02), S(0.001983), sy * 0.000245, S(0.000013), S(0.002103), sy * 0.0000015, S(0.000408));
+        const RBI<S> Ith = wbs_pick<PLANT>(qH, rbi_link<S>(0.634, zero, sy * 0.016, S(-0.02), S(0.001983), sy * 0.000245, S(0.000013), S(0.002103), sy * 0.0000015, S(0.000408)));
         V3<S> n2, f2; link_force(Ith, o2, v2, a2, l2, n2, f2);
         V3<S> o3 = o2, a3 = a2, v3 = v2 + cross(o2, pk), l3 = l2 + cross(a2, pk);
         revj(A1{}, ck, sk, vl_[2], o3, v3, a3, l3);
@@ -365,7 +405,7 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         rhs = {pick(lam0.x, lam1.x, lam2.x, lam3.x), pick(lam0.y, lam1.y, lam2.y, lam3.y), pick(lam0.z, lam1.z, lam2.z, lam3.z)};
     }
     const V3<S> lam = scale(cl, rhs);      // contact force of the lane's foot (world axes); zero for a swing leg
-    if constexpr ((wbs_is_ter_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z, lam_out->px = fpos.x, lam_out->py = fpos.y), ...); }
+    if constexpr (PLANT || (wbs_is_ter_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z, lam_out->px = fpos.x, lam_out->py = fpos.y), ...); }
     else if constexpr ((wbs_is_uni_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z), ...); }
     else if constexpr (sizeof...(LO) > 0) { ((lam_out != nullptr ? (void)(*lam_out = lam) : (void)0), ...); }
     // qdd = L^-T (y + X lam): base part replicated, leg part in the lane
@@ -407,8 +447,8 @@ struct WbsMcArgs {
 // NOISE 0: the walk of a run whose three sigmas are zero, compiled without the generator.  Measured (MI355X, config 3 x 16 samples x 200 steps, plain
 // run 9.88 ms): with the generator compiled in and branched over, a run with only u_max set took 11.74 ms - the register allocation of the whole
 // loop pays for code that does not run; without it 9.83 ms.  So the host picks the instantiation, and every other switch stays a run-time branch.
-struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0, UNI = 0, TER = 0; };
-template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0, UNI = 0, TER = 0; const WbsMcArgs* a; };
+struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0, UNI = 0, TER = 0, PLANT = 0; };
+template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0, UNI = 0, TER = 0, PLANT = 0; const WbsMcArgs* a; };
 constexpr int SIM_PARK_MC = SIM_PARK + 2;       // ... and n_sat, first_fall
 // Contact-force records (include/hsddp_grf.h): GRF 1 in the policy.  The walk takes the lane's multiplier of every mode-0 solve, keeps five running
 // values per lane (lane = leg) - smallest / largest stance fz, smallest cone margin, first violating step, violations - and joins them over the
@@ -421,8 +461,8 @@ struct WbsGrfArgs {
 constexpr int SIM_GRF_ROW = 5;     // min_fz | min_cone | max_fz | first_slip | n_slip
 constexpr int SIM_GRF_PARK = 5;    // the lane's running values, parked behind the others
 constexpr double SIM_GRF_NONE = 1e18;      // first_slip of a lane without a violation while the walk runs: above every step index
-struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0, UNI = 0, TER = 0; const WbsGrfArgs* gr; };
-template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0, UNI = 0, TER = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
+struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0, UNI = 0, TER = 0, PLANT = 0; const WbsGrfArgs* gr; };
+template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0, UNI = 0, TER = 0, PLANT = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
 // Sub-stepped integration (include/hsddp_substep.h): SUB 1 in the policy.  A control knot is S forward-Euler steps of dt / S under the knot's torque
 // (zero-order hold): the feedback, the noise and every record of the state stay once per control step, the contact solve, the divergence test and
 // the force records run once per substep.  S is a run-time trip count read from device memory through a laundered pointer, as the other switches
@@ -430,10 +470,10 @@ template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOI
 // constexpr (D::SUB)` below is this code, and the six policies above compile to what they compiled to without it.
 struct WbsSubArgs { int substeps, pad; };      // 2 .. 64 (the host launches the kernels above for 1)
 constexpr int SIM_SUB_PARK = 3;
-struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1, UNI = 0, TER = 0; const WbsSubArgs* sb; };
-template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1, UNI = 0, TER = 0; const WbsMcArgs* a; const WbsSubArgs* sb; };
-struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0, TER = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
-template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0, TER = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1, UNI = 0, TER = 0, PLANT = 0; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1, UNI = 0, TER = 0, PLANT = 0; const WbsMcArgs* a; const WbsSubArgs* sb; };
+struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
 // Unilateral ground contact (include/hsddp_contact.h): UNI 1 in the policy, always with the records and the sub-step loop (GRF 1, SUB 1; S = 1 too).
 // The lane (= leg) carries F, 1 if its foot is a scheduled stance foot that is FREE, and the contact flag of every solve is the lane's own: attached =
 // scheduled and not free.  The trip loop of a control step becomes a small state machine around the ONE call site of the solve -
@@ -450,8 +490,8 @@ struct WbsUniArgs {
 };
 constexpr int SIM_UNI_ROW = 6;      // first_release | n_release | n_land | n_free | free_final | max_lift
 constexpr int SIM_UNI_PARK = 7;     // F, T, first_release, n_release, n_land, n_free, max_lift of the lane, parked behind everything else
-struct WbsUni { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
-template <int NOISE_> struct WbsMcUni { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
+struct WbsUni { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
+template <int NOISE_> struct WbsMcUni { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
 // Terrain and early swing-foot touchdown (include/hsddp_terrain.h): TER 1 in the policy, on top of UNI = GRF = SUB = 1.  The landing test compares with
 // a looked-up height instead of a constant, the tested set grows by the swing feet, and the attached set of a solve by the swing feet that landed: the
 // lane carries E, 1 if its foot is a SWING foot that is attached.  The solve hands the foot's x and y back through WbsTerIO; the lookup is one per-lane
@@ -467,10 +507,30 @@ struct WbsTerArgs {
 };
 constexpr int SIM_TER_ROW = 6;      // first_early | n_early | n_early_release | n_held | early_final | max_pen
 constexpr int SIM_TER_PARK = 6;     // E, first_early, n_early, n_early_release, n_held, max_pen of the lane
-struct WbsTer { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
-template <int NOISE_> struct WbsMcTer { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
+struct WbsTer { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
+template <int NOISE_> struct WbsMcTer { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
 template <bool TER, class S> struct wbs_io_of { using type = WbsUniIO<S>; };
 template <class S> struct wbs_io_of<true, S> { using type = WbsTerIO<S>; };
+// Plant-model mismatch (include/hsddp_plant.h): PLANT 1 in the policy, always with the records and the sub-step loop (GRF 1, SUB 1; S = 1 too), on top of
+// any of the three families - the bilateral walk, the unilateral one, the one with terrain.  The quad reads its row of the table through plant_of[g] in
+// front of every solve: the solve takes the inertias from it (WbsPlantIO), and the torque it is given is  gain o u - damping o qdot_leg  of the state that
+// solve starts from, formed from six per-lane loads at the call.  ul stays the commanded torque: it is what U, max_torque and n_sat record and what is
+// parked.  Nothing of the row is carried across a solve.  Every `if constexpr (D::PLANT)` below is this code, and the policies above compile to what
+// they compiled to without it.
+constexpr int SIM_PLANT_ROW = 46;      // HSDDP_PLANT_ROW: trunk mass | CoM 3 | inertia 6 | link_scale 12 | tau_gain 12 | damping 12
+struct WbsPlantArgs {
+    const double* P;              // [n_plants][SIM_PLANT_ROW]
+    const int* plant_of;          // [B R] the row of a sample, checked against n_plants by the host
+    int n_plants, pad;
+};
+struct WbsPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsPlantArgs* pl; };
+template <int NOISE_> struct WbsMcPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsPlantArgs* pl; };
+struct WbsUniPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsPlantArgs* pl; };
+template <int NOISE_> struct WbsMcUniPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsPlantArgs* pl; };
+struct WbsTerPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsPlantArgs* pl; };
+template <int NOISE_> struct WbsMcTerPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsPlantArgs* pl; };
+template <bool PLANT, bool TER, class S> struct wbs_io_sel { using type = typename wbs_io_of<TER, S>::type; };
+template <bool TER, class S> struct wbs_io_sel<true, TER, S> { using type = WbsPlantIO<S>; };
 // Height of map m at the foot point (px, py), relative to z_ground (sim.terrain_height is the definition).  The cell index is clamped as a double - fmax
 // sends a NaN to 0, fmin an infinity to the last cell - BEFORE it becomes an integer: no address outside the grid can be formed, whatever the state holds.
 HD double wbs_ter_height_lane(const WbsTerArgs& t, int m, double px, double py) {
@@ -512,6 +572,7 @@ inline const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { return p; }
 inline const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { return p; }
 inline const WbsUniArgs* wbs_uni_fresh(const WbsUniArgs* p) { return p; }
 inline const WbsTerArgs* wbs_ter_fresh(const WbsTerArgs* p) { return p; }
+inline const WbsPlantArgs* wbs_plant_fresh(const WbsPlantArgs* p) { return p; }
 inline Q4 wbs_ter_height(const WbsTerArgs& t, int m, const Q4& px, const Q4& py) { return Q4(wbs_ter_height_lane(t, m, px.v[0], py.v[0]), wbs_ter_height_lane(t, m, px.v[1], py.v[1]), wbs_ter_height_lane(t, m, px.v[2], py.v[2]), wbs_ter_height_lane(t, m, px.v[3], py.v[3])); }
 inline bool wbs_any(const Q4& f) { return f.v[0] > 0.5 || f.v[1] > 0.5 || f.v[2] > 0.5 || f.v[3] > 0.5; }      // (host: the quad is the whole wave)
 #else
@@ -523,6 +584,7 @@ HD const WbsGrfArgs* wbs_grf_fresh(const WbsGrfArgs* p) { asm volatile("" : "+s"
 HD const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsUniArgs* wbs_uni_fresh(const WbsUniArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsTerArgs* wbs_ter_fresh(const WbsTerArgs* p) { asm volatile("" : "+s"(p)); return p; }
+HD const WbsPlantArgs* wbs_plant_fresh(const WbsPlantArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD double wbs_ter_height(const WbsTerArgs& t, int m, double px, double py) { return wbs_ter_height_lane(t, m, px, py); }
 // true if the 0 / 1 flag is set in ANY active lane of the wave: a ballot, so the answer is wave-uniform and the branch on it a scalar one
 HD bool wbs_any(double f) { return __builtin_amdgcn_ballot_w64(f > 0.5) != 0ull; }
@@ -707,12 +769,21 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
             _Pragma("nounroll")
             for (;;) {
                 const int mode = (stg == 1 || stg == 3) ? 1 : 0;
-                typename wbs_io_of<D::TER != 0, S>::type io;
+                typename wbs_io_sel<D::PLANT != 0, D::TER != 0, S>::type io;
                 io.cl = stg == 1 ? tl : stg == 3 ? flag(cm_td) : flag(cm_dyn) * (one - fr);
                 if constexpr (D::TER) { if (mode == 0) io.cl = io.cl + (one - flag(cm_dyn)) * er; }      // A = (C \ F) u E
                 S ob[6]; V3<S> ol;
+                if constexpr (D::PLANT) {      // the quad's row: inertias for the solve, gain and friction on the torque it is given
+                    const WbsPlantArgs pa = *wbs_plant_fresh(dist.pl);
+                    io.row = pa.P + (size_t)pa.plant_of[g] * SIM_PLANT_ROW;
+                    S ue[3];
+                    _Pragma("unroll") for (int j = 0; j < 3; j++) ue[j] = Q::ld(io.row, 22 + j, 3) * ul[j] - Q::ld(io.row, 34 + j, 3) * vl[j];
+                    park(true, ul);
+                    wbs_contact_dynamics<Q>(md, 0, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ue, ob, ol, &io);
+                } else {
                 park(true, ul);
                 wbs_contact_dynamics<Q>(md, 0, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol, &io);
+                }
                 park(false, ul);
                 if (mode != 0) {      // positions stay, velocities jump: the scheduled reset map for every live sample, a landing for the quads that have one
                     const typename Q::B on = Q::gt(alive * (stg == 3 ? one : Q::sum(tl)), S(0.5));
@@ -812,7 +883,19 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                 park(true, ul);
                 if constexpr (D::GRF) {
                     V3<S> lam;
+                    if constexpr (D::PLANT) {      // as in the walk with the contact rule; the contact flag is the lane's bit of the wave-uniform mask
+                        const WbsPlantArgs pa = *wbs_plant_fresh(dist.pl);
+                        const int cm = mode == 0 ? cm_dyn : cm_td;
+                        WbsPlantIO<S> io;
+                        io.cl = Q::legc((cm & 1) ? 1.0 : 0.0, (cm & 2) ? 1.0 : 0.0, (cm & 4) ? 1.0 : 0.0, (cm & 8) ? 1.0 : 0.0);
+                        io.row = pa.P + (size_t)pa.plant_of[g] * SIM_PLANT_ROW;
+                        S ue[3];
+                        _Pragma("unroll") for (int j = 0; j < 3; j++) ue[j] = Q::ld(io.row, 22 + j, 3) * ul[j] - Q::ld(io.row, 34 + j, 3) * vl[j];
+                        wbs_contact_dynamics<Q>(md, 0, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ue, ob, ol, &io);
+                        lam = io.lam;
+                    } else {
                     wbs_contact_dynamics<Q>(md, mode == 0 ? cm_dyn : cm_td, mode, mode == 0 ? 1e-12 : 0.0, alpha, qb, vb, ql, vl, ul, ob, ol, &lam);
+                    }
                     park(false, ul);
                     // ---- records: the force of the step on the lane's foot, counted if the foot is a stance foot of the phase (a select on the
                     // wave-uniform contact mask) and the sample had not diverged before the step (`alive` is still the value the step began with).
@@ -894,6 +977,25 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
     _Pragma("unroll") for (int j = 0; j < 3; j++) { Q::st(xfinal, g * 36 + 6 + j, 3, ql[j]); Q::st(xfinal, g * 36 + 24 + j, 3, vl[j]); }
     Q::st0(rows, g * SIM_ROW, wbs_qmax<Q, S>(dq)); Q::st0(rows, g * SIM_ROW + 1, wbs_qmax<Q, S>(dv)); Q::st0(rows, g * SIM_ROW + 2, hmin);
     Q::st0(rows, g * SIM_ROW + 3, wbs_qmax<Q, S>(umax)); Q::st0(rows, g * SIM_ROW + 4, first_bad);
+}
+
+// The pending reset map of an episode (epi_impact of episode.hpp) on the robot's own plant: the same program with the inertias of row plant_of[g].  An
+// impact takes no torque, so gain and friction do not enter.  frozen[g stride] != 0: the robot's episode has ended - its quad computes with the others
+// and stores nothing.
+template <class Q> HD void wbs_plant_impact(PhaseC* ph, const ModelDev& md, int pi, size_t g, const int* frozen, int stride, double* state, double* x0, const WbsPlantArgs* pl) {
+    using S = typename Q::S;
+    PhaseC& P = ph[pi];
+    S qb[6], vb[6], ql[3], vl[3], ul[3], ob[6]; V3<S> ol;
+    _Pragma("unroll") for (int i = 0; i < 6; i++) { qb[i] = Q::ld(state, g * 36 + i, 0); vb[i] = Q::ld(state, g * 36 + 18 + i, 0); }
+    _Pragma("unroll") for (int j = 0; j < 3; j++) { ql[j] = Q::ld(state, g * 36 + 6 + j, 3); vl[j] = Q::ld(state, g * 36 + 24 + j, 3); ul[j] = S(0.0); }
+    WbsPlantIO<S> io;
+    io.cl = Q::legc(P.td[0] ? 1.0 : 0.0, P.td[1] ? 1.0 : 0.0, P.td[2] ? 1.0 : 0.0, P.td[3] ? 1.0 : 0.0);
+    io.row = pl->P + (size_t)pl->plant_of[g] * SIM_PLANT_ROW;
+    wbs_contact_dynamics<Q>(md, 0, 1, 0.0, P.bg_alpha, qb, vb, ql, vl, ul, ob, ol, &io);
+    if (frozen[g * (size_t)stride] != 0) return;
+    const S o3[3] = {ol.x, ol.y, ol.z};
+    _Pragma("unroll") for (int i = 0; i < 6; i++) { Q::st0(state, g * 36 + 18 + i, ob[i]); Q::st0(x0, g * 36 + i, qb[i]); Q::st0(x0, g * 36 + 18 + i, ob[i]); }
+    _Pragma("unroll") for (int j = 0; j < 3; j++) { Q::st(state, g * 36 + 24 + j, 3, o3[j]); Q::st(x0, g * 36 + 6 + j, 3, ql[j]); Q::st(x0, g * 36 + 24 + j, 3, o3[j]); }
 }
 
 #if !defined(HS_HOST_EMU) && !defined(HS_SIM_WALK_ONLY)      // (HS_SIM_WALK_ONLY: hsddp_sub.hip takes the walk and defines kernels of its own)

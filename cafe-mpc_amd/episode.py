@@ -6,6 +6,7 @@ whole-body dynamics, with the simulated state handed to the next solve on the de
     ep.set_substeps(4)                                              # optional: sub-stepped integration (include/hsddp_substep.h)
     ep.set_contact(0.0, 0.0)                                        # optional: unilateral ground contact (include/hsddp_contact.h)
     ep.set_terrain(sim.Terrain(H=heights, cx=0.05, cy=0.05, early=True, w_td=0.05))      # optional, with it: terrain and early touchdown (include/hsddp_terrain.h)
+    ep.set_plant(sim.Plant(rows, plant_of=idx))                     # optional: a plant row per robot, idx int [B] (include/hsddp_plant.h)
     ep.reset(x0)                                                    # [B, 36]; also the solver's initial condition
     solver.solve(opt)
     out = run_mhpc(solver, pd, phases, opt_rt, 50, dist=Disturbance(seed=7, sigma_u=0.2, fall_height=0.12), episode=ep)
@@ -184,6 +185,22 @@ class Episode:
             rc = lib.hsddp_terrain_set(self.lib.hsddp_episode_sim(self.e), 1, C.byref(t), H.ctypes.data, None if mo is None else mo.ctypes.data)
         if rc != 0:
             raise RuntimeError(f"hsddp_terrain_set failed rc={rc}")
+
+    def set_plant(self, plant, on=True):
+        """A plant row per robot for every later tick (include/hsddp_plant.h); `plant`: a sim.Plant whose plant_of, if given, is int [batch] or
+        [batch, 1].  Each robot keeps its plant for the whole episode: the table survives reconfigure and reset, and the reset map that is pending
+        at the end of a tick uses the robot's own inertias.  on = False: the planner's robot again."""
+        lib = _abi.bind_plant(self.lib)
+        if not on:
+            rc = lib.hsddp_plant_set(self.lib.hsddp_episode_sim(self.e), 0, 0, None, None)
+        else:
+            P = plant.table()
+            po = None if plant.plant_of is None else np.ascontiguousarray(plant.plant_of, dtype=np.int32).reshape(-1)
+            if po is not None and po.shape != (self.solver.batch,):
+                raise ValueError(f"Plant.plant_of has {po.size} entries, not {self.solver.batch}")
+            rc = lib.hsddp_plant_set(self.lib.hsddp_episode_sim(self.e), 1, P.shape[0], P.ctypes.data, None if po is None else po.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_plant_set failed rc={rc}")
 
     def terrain_rows(self, b0=0, nb=None):
         """Structured array [nb] of hsddp_terrain_row_t of the last tick, which has to be one with the contact rule and the terrain on."""

@@ -24,6 +24,7 @@
 #include "hsddp_substep.h"
 #include "hsddp_contact.h"
 #include "hsddp_terrain.h"
+#include "hsddp_plant.h"
 #include "hsddp_episode.h"
 
 namespace hsddp {
@@ -81,6 +82,17 @@ public:
     bool set_terrain(bool on, const hsddp_terrain_t* t = nullptr, const double* H = nullptr, const int* map_of = nullptr) { rc_ = s_ ? hsddp_terrain_set(s_, on ? 1 : 0, t, H, map_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // rows of the last run, which has to be one with the contact rule and the terrain on: batch x n_samples
     bool terrain(hsddp_terrain_row_t* rows) { rc_ = s_ ? hsddp_terrain_get(s_, 0, batch_, rows) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // a plant row per sample for every later run (include/hsddp_plant.h): P [n_plants][HSDDP_PLANT_ROW] and plant_of [batch][n_samples] (or null: row 0)
+    // are host arrays, copied by the call; on = false ignores the rest
+    bool set_plant(bool on, int n_plants = 0, const double* P = nullptr, const int* plant_of = nullptr) { rc_ = s_ ? hsddp_plant_set(s_, on ? 1 : 0, n_plants, P, plant_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // the table later runs use: n_plants x HSDDP_PLANT_ROW doubles (empty on a fresh object); on (optional): whether the plant is switched on
+    std::vector<double> plant(bool* on = nullptr) {
+        int o = 0, n = 0; std::vector<double> P;
+        rc_ = s_ ? hsddp_plant_get_params(s_, &o, &n) : HSDDP_EINVAL;
+        if (rc_ == HSDDP_OK && n > 0) { P.resize((size_t)n * HSDDP_PLANT_ROW); rc_ = hsddp_plant_get_table(s_, 0, n, P.data()); }
+        if (on) *on = o != 0;
+        return P;
+    }
     // the records of the last run alone (result() holds them too): rows batch x n_samples, Y batch x n_samples x n_steps x 12 or null
     bool grf(hsddp_grf_row_t* rows, double* Y = nullptr) { rc_ = s_ ? hsddp_grf_get(s_, 0, batch_, rows, Y) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     SimResult result() {
@@ -134,6 +146,8 @@ public:
     bool set_contact(bool on, double fz_rel = 0.0, double z_ground = 0.0) { rc_ = e_ ? hsddp_contact_set(hsddp_episode_sim(e_), on ? 1 : 0, fz_rel, z_ground) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // terrain and early touchdown for every later tick; the swing feet a robot holds are carried from tick to tick (include/hsddp_terrain.h)
     bool set_terrain(bool on, const hsddp_terrain_t* t = nullptr, const double* H = nullptr, const int* map_of = nullptr) { rc_ = e_ ? hsddp_terrain_set(hsddp_episode_sim(e_), on ? 1 : 0, t, H, map_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // a plant row per robot for the whole episode (include/hsddp_plant.h): plant_of [batch] or null
+    bool set_plant(bool on, int n_plants = 0, const double* P = nullptr, const int* plant_of = nullptr) { rc_ = e_ ? hsddp_plant_set(hsddp_episode_sim(e_), on ? 1 : 0, n_plants, P, plant_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     std::vector<hsddp_episode_row_t> rows(std::vector<double>* x_now = nullptr) {
         std::vector<hsddp_episode_row_t> r((size_t)batch_);
         if (x_now) x_now->resize((size_t)batch_ * 36);

@@ -19,6 +19,9 @@
     ter = Terrain(H=heights, x0=-1.0, y0=-1.0, cx=0.05, cy=0.05, early=True, w_td=0.05, map_of=maps)      # include/hsddp_terrain.h: H [n_maps, ny, nx]
     res = solver.simulate(x0, n_steps=50, contact=(0.0, 0.0), terrain=ter)      # res["terrain"]["n_early"], ["max_pen"]
 
+    pl = Plant(np.stack([Plant.nominal().rows[0], with_trunk(Plant.nominal().rows[0], *payload_trunk(1.0, (0.05, 0.0, 0.04)))]), plant_of=idx)
+    res = solver.simulate(x0, n_steps=50, substeps=2, plant=pl)      # include/hsddp_plant.h: a plant row per sample, idx int [batch, R]
+
 Nothing here computes anything: the rollout is the k_sim_quad / k_sim_quad_mc kernel (csrc/wb_sim.hpp).  mc_normals states the generator of the
 disturbed runs in numpy, grf_rows the contact-force records and grf_rows_sub those of a sub-stepped run, terrain_height the height lookup of a terrain: the definitions the kernel mirrors."""
 import ctypes as C
@@ -81,6 +84,72 @@ def terrain_height(terrain, p_xy, m=0):
         ix = np.fmin(np.fmax(np.floor((p[..., 0] - terrain.x0) / terrain.cx), 0.0), H.shape[2] - 1.0).astype(np.int64)
         iy = np.fmin(np.fmax(np.floor((p[..., 1] - terrain.y0) / terrain.cy), 0.0), H.shape[1] - 1.0).astype(np.int64)
     return H[np.asarray(m, dtype=np.int64), iy, ix]
+
+
+@dataclasses.dataclass
+class Plant:
+    """The plant table of include/hsddp_plant.h: rows [n_plants, 46] (a [46] array is one row) and plant_of, None (row 0 for every sample) or int
+    [batch, n_samples].  A row: trunk mass | trunk CoM | trunk inertia about its CoM (xx, xy, xz, yy, yz, zz) | link_scale 12 | tau_gain 12 | damping 12,
+    joints leg-major (_abi.PLANT_SLICES)."""
+    rows: np.ndarray
+    plant_of: np.ndarray = None
+
+    def table(self):
+        P = np.ascontiguousarray(self.rows, dtype=np.float64)
+        P = P[None] if P.ndim == 1 else P
+        if P.ndim != 2 or P.shape[1] != _abi.PLANT_ROW:
+            raise ValueError(f"Plant: rows have shape {P.shape}")
+        return P
+
+    @staticmethod
+    def nominal(n=1):
+        """n copies of the row the planner believes in."""
+        return Plant(np.tile(np.array(_abi.PLANT_NOMINAL), (int(n), 1)))
+
+
+def payload_trunk(mass, pos, inertia=None):
+    """(mass, CoM [3], inertia about the CoM [6: xx, xy, xz, yy, yz, zz]) of the nominal trunk with a payload of `mass` at `pos` (trunk axes) whose
+    own inertia about its centre is `inertia` (same six entries; None: a point mass): the parallel-axis composition, which is the definition."""
+    nom = np.array(_abi.PLANT_NOMINAL)
+    m0, c0 = nom[0], nom[1:4]
+    sym = lambda v: np.array([[v[0], v[1], v[2]], [v[1], v[3], v[4]], [v[2], v[4], v[5]]], dtype=np.float64)
+    about = lambda m, d: m * (float(d @ d) * np.eye(3) - np.outer(d, d))      # a point mass m at d, about the origin
+    p = np.asarray(pos, dtype=np.float64)
+    m = m0 + float(mass)
+    c = (m0 * c0 + float(mass) * p) / m
+    Ic = sym(nom[4:10]) + about(m0, c0 - c) + (sym(np.asarray(inertia, dtype=np.float64)) if inertia is not None else 0.0) + about(float(mass), p - c)
+    return m, c, np.array([Ic[0, 0], Ic[0, 1], Ic[0, 2], Ic[1, 1], Ic[1, 2], Ic[2, 2]])
+
+
+def with_trunk(row, mass, com, inertia):
+    """A copy of the plant row with the trunk's ten entries replaced (what payload_trunk returns)."""
+    out = np.array(row, dtype=np.float64)
+    out[0] = mass; out[1:4] = com; out[4:10] = inertia
+    return out
+
+
+def _with_joints(row, name, v):
+    out = np.array(row, dtype=np.float64)
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    if v.size not in (1, 3, 12):
+        raise ValueError(f"{name}: {v.size} values, not 1, 3 or 12")
+    out[_abi.PLANT_SLICES[name]] = np.tile(v, 12 // v.size)
+    return out
+
+
+def with_link_scale(row, scale):
+    """A copy of the row with link_scale set: a scalar, three values (abad, hip, knee of every leg) or twelve (leg-major)."""
+    return _with_joints(row, "link_scale", scale)
+
+
+def with_gain(row, gain):
+    """A copy of the row with tau_gain set (scalar, three or twelve values)."""
+    return _with_joints(row, "tau_gain", gain)
+
+
+def with_damping(row, b):
+    """A copy of the row with the viscous friction set, N m s / rad (scalar, three or twelve values).  The friction is explicit: see the header."""
+    return _with_joints(row, "damping", b)
 
 
 def mc_normals(seed, problem, r, s):
@@ -157,6 +226,7 @@ class Simulation:
         self.grf_on = False
         self.contact_on = False
         self.terrain_on = False
+        self.plant_on = False
         self.solver, self.R, self.n_steps, self.keep_traj = solver, int(n_samples), int(n_steps), bool(keep_traj)
         self.s = C.c_void_p()
         rc = self.lib.hsddp_sim_create(solver.h, self.R, self.n_steps, 1 if keep_traj else 0, C.byref(self.s))
@@ -301,6 +371,39 @@ class Simulation:
             raise RuntimeError(f"hsddp_terrain_get failed rc={rc}")
         return rows
 
+    def set_plant(self, plant):
+        """A plant row per sample for every later run (include/hsddp_plant.h); `plant`: a Plant.  The table and the index are copied."""
+        P = plant.table()
+        po = None if plant.plant_of is None else np.ascontiguousarray(plant.plant_of, dtype=np.int32)
+        if po is not None and po.shape != (self.solver.batch, self.R):
+            raise ValueError(f"Plant.plant_of has shape {po.shape}, not {(self.solver.batch, self.R)}")
+        rc = _abi.bind_plant(self.lib).hsddp_plant_set(self.s, 1, P.shape[0], P.ctypes.data, None if po is None else po.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_plant_set failed rc={rc}")
+        self.plant_on = True
+
+    def clear_plant(self):
+        """Later runs simulate the planner's robot again (the kernels without the plant)."""
+        rc = _abi.bind_plant(self.lib).hsddp_plant_set(self.s, 0, 0, None, None)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_plant_set failed rc={rc}")
+        self.plant_on = False
+
+    @property
+    def plant(self):
+        """(on, rows [n_plants, 46]) as later runs use them (hsddp_plant_get_params, hsddp_plant_get_table); no rows on a fresh object."""
+        lib = _abi.bind_plant(self.lib)
+        on = C.c_int(); n = C.c_int()
+        rc = lib.hsddp_plant_get_params(self.s, C.byref(on), C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_plant_get_params failed rc={rc}")
+        P = np.zeros((n.value, _abi.PLANT_ROW))
+        if n.value > 0:
+            rc = lib.hsddp_plant_get_table(self.s, 0, n.value, P.ctypes.data)
+            if rc != 0:
+                raise RuntimeError(f"hsddp_plant_get_table failed rc={rc}")
+        return bool(on.value), P
+
     @property
     def substeps(self):
         """What later runs use, as the library reports it (hsddp_substep_get)."""
@@ -351,12 +454,12 @@ class Simulation:
         return float(ms.value)
 
 
-def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None):
+def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None, plant=None):
     """One-off simulation on `solver`: dict with rows, x_final and, with keep_traj, X and U (see Simulation); a disturbed run (dist / kick given)
     returns extra too; grf = (mu, fz_min) adds the contact-force records grf and, with keep_traj, Y; substeps = S > 1 integrates every control
     knot in S steps (include/hsddp_substep.h); contact = (fz_rel, z_ground) switches unilateral ground contact on (include/hsddp_contact.h) and
     adds the rows contact; terrain = Terrain(...) beside it switches height maps and early touchdown on (include/hsddp_terrain.h) and adds the rows
-    terrain."""
+    terrain; plant = Plant(...) gives every sample a plant row (include/hsddp_plant.h)."""
     sim = Simulation(solver, x0.shape[1], n_steps, keep_traj)
     try:
         if substeps != 1:
@@ -367,6 +470,8 @@ def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=Non
             sim.set_contact(*contact)
         if terrain is not None:
             sim.set_terrain(terrain)
+        if plant is not None:
+            sim.set_plant(plant)
         sim.run(x0, dist=dist, kick=kick)
         rows, xf = sim.rows()
         out = dict(rows=rows, x_final=xf)
