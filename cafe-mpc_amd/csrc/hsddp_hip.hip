@@ -182,6 +182,23 @@ __global__ void __launch_bounds__(64) ROLL_HKD_ATTR k_rollout_hkd(ROLL_ARGS) { _
 #ifndef HS_QUAD_SEPARATE
 #include "hsddp_quad.hip"
 #endif
+// The simulation walks beyond the six of wb_sim.hpp - sub-stepped (hsddp_substep.h), with unilateral ground contact (hsddp_contact.h), with terrain
+// (hsddp_terrain.h), with a per-sample plant (hsddp_plant.h) - and their launchers.  The Makefile compiles each file as a translation unit of its own
+// (-DHS_SUB_SEPARATE, -DHS_UNI_SEPARATE, -DHS_TER_SEPARATE, -DHS_PLANT_SEPARATE here) so that this file's code object stays what it was without them
+// (hsddp_sub.hip); any other build takes them in HERE, where both the host pass and the device pass see the kernels.  The launchers' prototypes are in
+// wb_sim.hpp either way.
+#ifndef HS_SUB_SEPARATE
+#include "hsddp_sub.hip"
+#endif
+#ifndef HS_UNI_SEPARATE
+#include "hsddp_uni.hip"
+#endif
+#ifndef HS_TER_SEPARATE
+#include "hsddp_ter.hip"
+#endif
+#ifndef HS_PLANT_SEPARATE
+#include "hsddp_plant.hip"
+#endif
 
 // Batched line search, decision step (MultiPhaseDDP::line_search, MultiPhaseDDP.cpp:108-131, for the candidates of one probe launch): per
 // problem the candidates are examined IN ORDER - reduction of the slice's partials, merit, Armijo test - exactly as if they had been
@@ -1663,672 +1680,8 @@ int hsddp_get_references(hsddp_handle_t* h, int phase, int b0, int nb, double* x
     return HSDDP_OK;
 }
 
-
-// ------------------------------------------------------------------------------------------------ closed-loop policy simulation (hsddp_sim.h)
 }  // extern "C"
-// The sub-stepped kernels and their launcher (hsddp_substep.h): hsddp_sub.hip, which the Makefile compiles as a translation unit of its own
-// (-DHS_SUB_SEPARATE here) so that this file's code object stays what it was; any other build takes it in here.
-#ifdef HS_SUB_SEPARATE
-namespace hs {
-void wbs_sub_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
-                    double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb);
-}
-#else
-#include "hsddp_sub.hip"
-#endif
-// The kernels with unilateral ground contact and their launcher (hsddp_contact.h): hsddp_uni.hip, a translation unit of its own for the same reason
-// (-DHS_UNI_SEPARATE here).
-#ifdef HS_UNI_SEPARATE
-namespace hs {
-void wbs_uni_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
-                    double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un);
-}
-#else
-#include "hsddp_uni.hip"
-#endif
-// The kernels with terrain and early swing-foot touchdown and their launcher (hsddp_terrain.h): hsddp_ter.hip, likewise (-DHS_TER_SEPARATE here).
-#ifdef HS_TER_SEPARATE
-namespace hs {
-void wbs_ter_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
-                    double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un,
-                    const WbsTerArgs* te);
-}
-#else
-#include "hsddp_ter.hip"
-#endif
-// The kernels with a per-sample plant and their launchers (hsddp_plant.h): hsddp_plant.hip, likewise (-DHS_PLANT_SEPARATE here).
-#include "plant_host.hpp"
-#ifdef HS_PLANT_SEPARATE
-namespace hs {
-void wbs_plant_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
-                      double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un,
-                      const WbsTerArgs* te, const WbsPlantArgs* pl);
-void wbs_plant_impact_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, int pi, int total, const int* frozen, int stride, double* state, double* x0,
-                             const WbsPlantArgs* pl);
-}
-#else
-#include "hsddp_plant.hip"
-#endif
-struct hsddp_sim {
-    hsddp_handle* h = nullptr;
-    int R = 0, n_steps = 0, keep = 0, gen = 0;
-    int* d_map = nullptr;                                  // [3][n_steps] step -> phase, knot, reset map behind the step (wb_sim.hpp)
-    double *d_x0 = nullptr, *d_final = nullptr, *d_rows = nullptr, *d_X = nullptr, *d_U = nullptr;      // [B R] x 36 / 36 / SIM_ROW / (n_steps+1) 36 / n_steps 12
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
-    // disturbed runs (hsddp_mc.h): allocated at the first one.  last_mc: 0 the last run was plain, 1 disturbed, 2 hsddp_mc_run with every switch off
-    double *d_extra = nullptr, *d_kick = nullptr; WbsMcArgs* d_mc = nullptr;      // [B R][2] first_fall | n_sat ; staging of a host kick ; the switches
-    int last_mc = 0;
-    // contact-force records (hsddp_grf.h): allocated by the first hsddp_grf_set that switches them on.  grf_on: what later runs do; last_grf: what the last run did
-    double *d_grf_rows = nullptr, *d_Y = nullptr; WbsGrfArgs* d_grf = nullptr;      // [B R][SIM_GRF_ROW] ; [B R][n_steps][12] (keep) ; thresholds and destinations
-    bool grf_on = false, last_grf = false;
-    // sub-stepped integration (hsddp_substep.h): what later runs use; the trip count on the device, allocated by the first hsddp_substep_set above 1
-    int substeps = 1; WbsSubArgs* d_sub = nullptr;
-    // unilateral ground contact (hsddp_contact.h): everything below is allocated by the first hsddp_contact_set that switches the rule on.
-    // uni_on: what later runs do; last_uni: what the last run did.  d_uni_grf / d_uni_grows: thresholds and rows of the records the walk always keeps,
-    // used while hsddp_grf_set has them off.  d_uni_F: the free flags an episode carries from tick to tick (uni_keep, set by hsddp_episode_create;
-    // uni_hold: the end_reason of the episode's rows, stride in ints)
-    bool uni_on = false, last_uni = false, uni_keep = false;
-    double uni_fz_rel = 0.0, uni_z_ground = 0.0;
-    WbsUniArgs* d_uni = nullptr; double *d_uni_rows = nullptr, *d_uni_F = nullptr, *d_uni_grows = nullptr; WbsGrfArgs* d_uni_grf = nullptr;
-    const int* uni_hold = nullptr; int uni_hold_stride = 0;
-    // terrain and early touchdown (hsddp_terrain.h): allocated by hsddp_terrain_set calls that switch it on (the grid again when it grows: ter_cap
-    // doubles).  ter_on: what later runs ask for - it acts while uni_on is set too; last_ter: the last run launched the _ter kernels.  d_ter_E: the early
-    // flags an episode carries from tick to tick (uni_keep), under the hold of d_uni_F
-    bool ter_on = false, last_ter = false;
-    hsddp_terrain_t ter = {};
-    WbsTerArgs* d_ter = nullptr; double *d_ter_H = nullptr, *d_ter_rows = nullptr, *d_ter_E = nullptr; int* d_ter_map = nullptr; size_t ter_cap = 0;
-    // per-sample plant (hsddp_plant.h): allocated by hsddp_plant_set calls that switch it on (the table again when it grows: plant_cap rows).  plant_on:
-    // what later runs do.  plant_rows: the host's copy of the table, for hsddp_plant_get_table.  The _plant walks always keep the force records and read
-    // the trip count from the device: while hsddp_grf_set has the records off they go to d_uni_grows through d_uni_grf (the buffer the walks with the
-    // contact rule use for the same purpose), and d_sub is made current by the set call as hsddp_contact_set does
-    bool plant_on = false; int n_plants = 0;
-    WbsPlantArgs* d_plant = nullptr; double* d_plant_P = nullptr; int* d_plant_of = nullptr; size_t plant_cap = 0;
-    std::vector<double> plant_rows;
-};
-static void sim_free(hsddp_sim* s) {
-    if (!s) return;
-    hipSetDevice(s->h->device);
-    if (s->h->stream) hipStreamSynchronize(s->h->stream);
-    void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf, s->d_sub, s->d_uni, s->d_uni_rows, s->d_uni_F, s->d_uni_grows, s->d_uni_grf,
-                 s->d_ter, s->d_ter_H, s->d_ter_rows, s->d_ter_E, s->d_ter_map, s->d_plant, s->d_plant_P, s->d_plant_of};
-    for (void* q : p) if (q) hipFree(q);
-    if (s->ev0) hipEventDestroy(s->ev0);
-    if (s->ev1) hipEventDestroy(s->ev1);
-    delete s;
-}
-static bool sim_range_ok(const hsddp_sim* s, int b0, int nb) { return s && nb > 0 && b0 >= 0 && b0 <= s->h->batch - nb; }
-// step -> (phase, knot) over the leading whole-body control knots of the handle's CURRENT window, as hsddp_export_mpc_command walks them; the reset
-// map of a phase is applied behind its last knot when the window goes on.  map: 3 n_steps ints.  False if the window holds fewer such knots.
-// pending (optional): the phase whose reset map lies behind the LAST step - the one no run applies (hsddp_episode.h) - or -1.
-static bool sim_step_map(const hsddp_handle* h, int n_steps, int* map, int* pending = nullptr) {
-    int n = 0, pend = -1;
-    for (int i = 0; i < h->nph && n < n_steps; i++) {
-        if (h->ph[i].model != HSDDP_MODEL_WB) break;
-        for (int k = 0; k < h->ph[i].h && n < n_steps; k++, n++) {
-            map[n] = i; map[n_steps + n] = k;
-            const bool td = k == h->ph[i].h - 1 && h->ph[i].has_impact;
-            map[2 * (size_t)n_steps + n] = (td && n + 1 < n_steps) ? 1 : 0;
-            if (td && n + 1 == n_steps) pend = i;
-        }
-    }
-    if (pending) *pending = pend;
-    return n == n_steps;
-}
-// the switches hsddp_mc_run accepts on object s
-static bool mc_dist_ok(const hsddp_sim* s, const hsddp_mc_dist_t* d, const double* kick) {
-    auto sigma_ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
-    if (!sigma_ok(d->sigma_u) || !sigma_ok(d->sigma_q) || !sigma_ok(d->sigma_v) || !std::isfinite(d->u_max) || !std::isfinite(d->fall_height) || d->first_problem < 0) return false;
-    if (kick && (d->kick_step < 0 || d->kick_step >= s->n_steps)) return false;
-    return s->n_steps <= 65536 && s->R <= 65536;      // the generator numbers samples and steps in 16 bits each
-}
 
-extern "C" {
-
-int hsddp_sim_create(hsddp_handle_t* h, int n_samples, int n_steps, int keep_traj, hsddp_sim_t** out) {
-    if (!h || !out || n_samples <= 0 || n_steps <= 0) return HSDDP_EINVAL;
-    std::vector<int> map(3 * (size_t)n_steps, 0);
-    if (!sim_step_map(h, n_steps, map.data())) return HSDDP_EINVAL;
-    const size_t total = (size_t)h->batch * n_samples;
-    if (total >= ((size_t)1 << 31)) return HSDDP_ENOTSUP;      // quads are indexed in 32 bits
-    HIPCK(hipSetDevice(h->device));
-    hsddp_sim* s = new hsddp_sim();
-    s->h = h; s->R = n_samples; s->n_steps = n_steps; s->keep = keep_traj ? 1 : 0; s->gen = h->window_gen;
-#define SIM_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); sim_free(s); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
-    SIM_CK(hipMalloc((void**)&s->d_map, map.size() * sizeof(int)));
-    SIM_CK(hipMalloc((void**)&s->d_x0, total * 36 * 8));
-    SIM_CK(hipMalloc((void**)&s->d_final, total * 36 * 8));
-    SIM_CK(hipMalloc((void**)&s->d_rows, total * SIM_ROW * 8));
-    if (s->keep) { SIM_CK(hipMalloc((void**)&s->d_X, total * (n_steps + 1) * 36 * 8)); SIM_CK(hipMalloc((void**)&s->d_U, total * n_steps * 12 * 8)); }
-    SIM_CK(hipEventCreate(&s->ev0)); SIM_CK(hipEventCreate(&s->ev1));
-    SIM_CK(hipMemcpy(s->d_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-    SIM_CK(hipMemset(s->d_final, 0, total * 36 * 8)); SIM_CK(hipMemset(s->d_rows, 0, total * SIM_ROW * 8));
-#undef SIM_CK
-    *out = s; return HSDDP_OK;
-}
-
-void hsddp_sim_destroy(hsddp_sim_t* s) { sim_free(s); }
-
-// the one launch path of a run: the plain kernel, or (mc) the disturbed one with the switches that are already on the device at s->d_mc; with the
-// contact-force records on (hsddp_grf_set), the twin of that kernel that keeps them; with more than one substep (hsddp_substep_set), the sub-stepped
-// twin of whichever of the six that is
-static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, bool noise = false) {
-    hsddp_handle* h = s->h;
-    const size_t total = (size_t)h->batch * s->R;
-    if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCK(hipEventRecord(s->ev0, h->stream));
-    const bool ter = s->uni_on && s->ter_on;      // (hsddp_terrain.h: dormant while the contact rule is off)
-    if (s->plant_on) {      // (hsddp_plant.h) the _plant twin of the family the other switches select; records and trip count always
-        wbs_plant_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
-                         s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : (const WbsGrfArgs*)s->d_uni_grf,
-                         s->d_sub, s->uni_on ? (const WbsUniArgs*)s->d_uni : nullptr, ter ? (const WbsTerArgs*)s->d_ter : nullptr, s->d_plant);
-    } else if (ter) {
-        wbs_ter_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
-                       s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : (const WbsGrfArgs*)s->d_uni_grf,
-                       s->d_sub, s->d_uni, s->d_ter);
-    } else if (s->uni_on) {      // (for every S: the walk with the rule carries the sub-step loop and the records)
-        wbs_uni_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
-                       s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : (const WbsGrfArgs*)s->d_uni_grf,
-                       s->d_sub, s->d_uni);
-    } else if (s->substeps > 1) {
-        // (the launcher leaves the runtime's error state alone: a failed launch is caught by the hipGetLastError below, as for the other kernels)
-        wbs_sub_launch(h->stream, (unsigned)((total + 15) / 16), h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total, src_device ? x0 : s->d_x0, s->d_final,
-                       s->d_rows, s->d_X, s->d_U, mc ? (const WbsMcArgs*)s->d_mc : nullptr, noise, s->grf_on ? (const WbsGrfArgs*)s->d_grf : nullptr, s->d_sub);
-    } else if (!s->grf_on) {
-        if (!mc)
-            hipLaunchKernelGGL(k_sim_quad, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
-                               src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U);
-        else
-            hipLaunchKernelGGL(noise ? k_sim_quad_mc : k_sim_quad_mc0, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
-                               src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, (const WbsMcArgs*)s->d_mc);
-    } else {
-        if (!mc)
-            hipLaunchKernelGGL(k_sim_quad_grf, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
-                               src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, (const WbsGrfArgs*)s->d_grf);
-        else
-            hipLaunchKernelGGL(noise ? k_sim_quad_mc_grf : k_sim_quad_mc0_grf, dim3((unsigned)((total + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, s->d_map, s->n_steps, s->R, (int)total,
-                               src_device ? x0 : s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, (const WbsMcArgs*)s->d_mc, (const WbsGrfArgs*)s->d_grf);
-    }
-    HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(s->ev1, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));
-    s->timed = true; s->last_grf = s->grf_on; s->last_uni = s->uni_on; s->last_ter = ter;
-    return HSDDP_OK;
-}
-
-int hsddp_sim_run(hsddp_sim_t* s, const double* x0, int src_device) {
-    if (!s || !x0) return HSDDP_EINVAL;
-    hsddp_handle* h = s->h;
-    if (s->gen != h->window_gen) return HSDDP_EINVAL;      // hsddp_reconfigure moved the window: the step map is that of the old one
-    HIPCK(hipSetDevice(h->device));
-    const int rc = sim_launch(s, x0, src_device, false);
-    if (rc == HSDDP_OK) s->last_mc = 0;
-    return rc;
-}
-
-int hsddp_mc_run(hsddp_sim_t* s, const double* x0, int x0_device, const hsddp_mc_dist_t* d, const double* kick, int kick_device) {
-    if (!s || !x0 || !d) return HSDDP_EINVAL;
-    hsddp_handle* h = s->h;
-    if (s->gen != h->window_gen) return HSDDP_EINVAL;
-    if (!mc_dist_ok(s, d, kick)) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(h->device));
-    if (!kick && d->sigma_u == 0.0 && d->sigma_q == 0.0 && d->sigma_v == 0.0 && d->u_max <= 0.0 && d->fall_height <= 0.0) {      // nothing switched on: the plain kernel
-        const int rc = sim_launch(s, x0, x0_device, false);
-        if (rc == HSDDP_OK) s->last_mc = 2;
-        return rc;
-    }
-    const size_t total = (size_t)h->batch * s->R;
-#define MC_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
-    if (!s->d_extra) MC_CK(hipMalloc((void**)&s->d_extra, total * 2 * 8));
-    if (!s->d_mc) MC_CK(hipMalloc((void**)&s->d_mc, sizeof(WbsMcArgs)));
-    if (kick && !kick_device && !s->d_kick) MC_CK(hipMalloc((void**)&s->d_kick, total * 36 * 8));
-#undef MC_CK
-    if (kick && !kick_device) HIPCK(hipMemcpyAsync(s->d_kick, kick, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
-    WbsMcArgs a;
-    a.seed = d->seed; a.first_problem = (unsigned long long)d->first_problem;
-    a.su = d->sigma_u; a.sq = d->sigma_q; a.sv = d->sigma_v; a.umax = d->u_max; a.fall = d->fall_height;
-    a.kick_step = kick ? d->kick_step : -1; a.R = s->R;
-    a.kick = kick ? (kick_device ? kick : s->d_kick) : nullptr; a.extra = s->d_extra;
-    HIPCK(hipMemcpyAsync(s->d_mc, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));      // (pageable source: staged before the call returns)
-    const int rc = sim_launch(s, x0, x0_device, true, d->sigma_u > 0.0 || d->sigma_q > 0.0 || d->sigma_v > 0.0);      // (without noise: the walk compiled without the generator)
-    if (rc == HSDDP_OK) s->last_mc = 1;
-    return rc;
-}
-
-int hsddp_mc_get_extra(hsddp_sim_t* s, int b0, int nb, hsddp_mc_extra_t* out) {
-    if (!sim_range_ok(s, b0, nb) || !out || s->last_mc == 0) return HSDDP_EINVAL;
-    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R;
-    if (s->last_mc == 2) { for (size_t i = 0; i < cnt; i++) { out[i].first_fall = -1; out[i].n_sat = 0; } return HSDDP_OK; }
-    HIPCK(hipSetDevice(s->h->device));
-    std::vector<double> r(cnt * 2);
-    HIPCK(hipMemcpy(r.data(), s->d_extra + off * 2, r.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < cnt; i++) { out[i].first_fall = (int)r[2 * i]; out[i].n_sat = (int)r[2 * i + 1]; }
-    return HSDDP_OK;
-}
-
-int hsddp_sim_get_rows(hsddp_sim_t* s, int b0, int nb, hsddp_sim_row_t* rows, double* x_final) {
-    if (!sim_range_ok(s, b0, nb) || !rows) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(s->h->device));
-    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R;
-    std::vector<double> r(cnt * SIM_ROW);
-    HIPCK(hipMemcpy(r.data(), s->d_rows + off * SIM_ROW, r.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < cnt; i++) {
-        const double* q = &r[i * SIM_ROW];
-        rows[i].dev_q = q[0]; rows[i].dev_v = q[1]; rows[i].min_height = q[2]; rows[i].max_torque = q[3]; rows[i].first_bad = (int)q[4]; rows[i].pad = 0;
-    }
-    if (x_final) HIPCK(hipMemcpy(x_final, s->d_final + off * 36, cnt * 36 * 8, hipMemcpyDeviceToHost));
-    return HSDDP_OK;
-}
-
-int hsddp_sim_get_traj(hsddp_sim_t* s, int b0, int nb, double* X, double* U) {
-    if (!sim_range_ok(s, b0, nb) || !s->keep) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(s->h->device));
-    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R, sx = (size_t)(s->n_steps + 1) * 36, su = (size_t)s->n_steps * 12;
-    if (X) HIPCK(hipMemcpy(X, s->d_X + off * sx, cnt * sx * 8, hipMemcpyDeviceToHost));
-    if (U) HIPCK(hipMemcpy(U, s->d_U + off * su, cnt * su * 8, hipMemcpyDeviceToHost));
-    return HSDDP_OK;
-}
-
-int hsddp_grf_set(hsddp_sim_t* s, double mu, double fz_min) {
-    if (!s || !std::isfinite(mu) || !std::isfinite(fz_min) || mu < 0.0 || fz_min < 0.0) return HSDDP_EINVAL;
-    if (mu == 0.0) { s->grf_on = false; return HSDDP_OK; }      // later runs launch the kernels without records; the buffers are kept
-    hsddp_handle* h = s->h;
-    HIPCK(hipSetDevice(h->device));
-    const size_t total = (size_t)h->batch * s->R;
-    // (as MC_CK of hsddp_mc_run: an allocation that fails returns its code at once; the buffers made before it are kept for the next call and freed
-    // with the object, and the records stay off - "nothing changed" holds for what a run does, not for those allocations)
-#define GRF_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
-    if (!s->d_grf_rows) GRF_CK(hipMalloc((void**)&s->d_grf_rows, total * SIM_GRF_ROW * 8));
-    if (s->keep && !s->d_Y) GRF_CK(hipMalloc((void**)&s->d_Y, total * (size_t)s->n_steps * 12 * 8));
-    if (!s->d_grf) GRF_CK(hipMalloc((void**)&s->d_grf, sizeof(WbsGrfArgs)));
-#undef GRF_CK
-    WbsGrfArgs a;
-    a.mu = mu; a.fz_min = fz_min; a.rows = s->d_grf_rows; a.Y = s->keep ? s->d_Y : nullptr;
-    HIPCK(hipMemcpyAsync(s->d_grf, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));      // (pageable source: staged before the call returns; the runs are on this stream)
-    s->grf_on = true;
-    return HSDDP_OK;
-}
-
-int hsddp_grf_get(hsddp_sim_t* s, int b0, int nb, hsddp_grf_row_t* rows, double* Y) {
-    if (!sim_range_ok(s, b0, nb) || !rows || !s->last_grf || (Y && !s->keep)) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(s->h->device));
-    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R, sy = (size_t)s->n_steps * 12;
-    std::vector<double> r(cnt * SIM_GRF_ROW);
-    HIPCK(hipMemcpy(r.data(), s->d_grf_rows + off * SIM_GRF_ROW, r.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < cnt; i++) {
-        const double* q = &r[i * SIM_GRF_ROW];
-        rows[i].min_fz = q[0]; rows[i].min_cone = q[1]; rows[i].max_fz = q[2]; rows[i].first_slip = (int)q[3]; rows[i].n_slip = (int)q[4];
-    }
-    if (Y) HIPCK(hipMemcpy(Y, s->d_Y + off * sy, cnt * sy * 8, hipMemcpyDeviceToHost));
-    return HSDDP_OK;
-}
-
-int hsddp_substep_set(hsddp_sim_t* s, int substeps) {
-    if (!s || substeps < 1 || substeps > HSDDP_SUBSTEP_MAX) return HSDDP_EINVAL;
-    hsddp_handle* h = s->h;
-    if (substeps > 1 || s->d_sub) {      // (an object that never asks for more than one holds what it held before)
-        HIPCK(hipSetDevice(h->device));
-        if (!s->d_sub) {
-            hipError_t e_ = hipMalloc((void**)&s->d_sub, sizeof(WbsSubArgs));
-            if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] hipMalloc of the substep block failed: %s\n", hipGetErrorString(e_)); s->d_sub = nullptr; return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; }
-        }
-        WbsSubArgs a;
-        a.substeps = substeps; a.pad = 0;
-        HIPCK(hipMemcpyAsync(s->d_sub, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));      // (pageable source: staged before the call returns; the runs are on this stream)
-    }
-    s->substeps = substeps;
-    return HSDDP_OK;
-}
-
-int hsddp_substep_get(hsddp_sim_t* s, int* substeps) {
-    if (!s || !substeps) return HSDDP_EINVAL;
-    *substeps = s->substeps;
-    return HSDDP_OK;
-}
-
-int hsddp_contact_set(hsddp_sim_t* s, int on, double fz_rel, double z_ground) {
-    if (!s || !std::isfinite(fz_rel) || !std::isfinite(z_ground)) return HSDDP_EINVAL;
-    if (!on) { s->uni_on = false; return HSDDP_OK; }      // later runs launch the kernels without the rule; the buffers and the thresholds are kept
-    hsddp_handle* h = s->h;
-    if (h->f32) return HSDDP_ENOTSUP;
-    HIPCK(hipSetDevice(h->device));
-    const size_t total = (size_t)h->batch * s->R;
-    // (as GRF_CK of hsddp_grf_set: an allocation that fails returns its code at once, what was made before it is kept, and the rule stays off)
-#define UNI_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
-    if (!s->d_uni) UNI_CK(hipMalloc((void**)&s->d_uni, sizeof(WbsUniArgs)));
-    if (!s->d_uni_rows) UNI_CK(hipMalloc((void**)&s->d_uni_rows, total * SIM_UNI_ROW * 8));
-    if (!s->d_uni_grows) UNI_CK(hipMalloc((void**)&s->d_uni_grows, total * SIM_GRF_ROW * 8));
-    if (!s->d_uni_grf) {
-        UNI_CK(hipMalloc((void**)&s->d_uni_grf, sizeof(WbsGrfArgs)));
-        WbsGrfArgs g;
-        g.mu = 1.0; g.fz_min = 0.0; g.rows = s->d_uni_grows; g.Y = nullptr;      // (nobody reads these records: hsddp_grf_get refuses while the records are off)
-        HIPCK(hipMemcpyAsync(s->d_uni_grf, &g, sizeof(g), hipMemcpyHostToDevice, h->stream));
-    }
-    if (s->uni_keep && !s->d_uni_F) { UNI_CK(hipMalloc((void**)&s->d_uni_F, total * 4 * 8)); HIPCK(hipMemsetAsync(s->d_uni_F, 0, total * 4 * 8, h->stream)); }
-    if (!s->d_sub) {      // the walk reads its trip count from here for S = 1 too; from now on hsddp_substep_set keeps it current
-        UNI_CK(hipMalloc((void**)&s->d_sub, sizeof(WbsSubArgs)));
-        WbsSubArgs b;
-        b.substeps = s->substeps; b.pad = 0;
-        HIPCK(hipMemcpyAsync(s->d_sub, &b, sizeof(b), hipMemcpyHostToDevice, h->stream));
-    }
-#undef UNI_CK
-    WbsUniArgs a;
-    a.fz_rel = fz_rel; a.z_ground = z_ground; a.rows = s->d_uni_rows; a.F = s->d_uni_F; a.hold = s->uni_hold; a.hold_stride = s->uni_hold_stride; a.pad = 0;
-    HIPCK(hipMemcpyAsync(s->d_uni, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));      // (pageable sources: staged before the calls return; the runs are on this stream)
-    s->uni_on = true; s->uni_fz_rel = fz_rel; s->uni_z_ground = z_ground;
-    return HSDDP_OK;
-}
-
-int hsddp_contact_get_params(hsddp_sim_t* s, int* on, double* fz_rel, double* z_ground) {
-    if (!s || !on || !fz_rel || !z_ground) return HSDDP_EINVAL;
-    *on = s->uni_on ? 1 : 0; *fz_rel = s->uni_fz_rel; *z_ground = s->uni_z_ground;
-    return HSDDP_OK;
-}
-
-int hsddp_contact_get(hsddp_sim_t* s, int b0, int nb, hsddp_contact_row_t* rows) {
-    if (!sim_range_ok(s, b0, nb) || !rows || !s->last_uni) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(s->h->device));
-    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R;
-    std::vector<double> r(cnt * SIM_UNI_ROW);
-    HIPCK(hipMemcpy(r.data(), s->d_uni_rows + off * SIM_UNI_ROW, r.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < cnt; i++) {
-        const double* q = &r[i * SIM_UNI_ROW];
-        rows[i].first_release = (int)q[0]; rows[i].n_release = (int)q[1]; rows[i].n_land = (int)q[2]; rows[i].n_free = (int)q[3]; rows[i].free_final = (int)q[4]; rows[i].pad = 0;
-        rows[i].max_lift = q[5];
-    }
-    return HSDDP_OK;
-}
-
-int hsddp_terrain_set(hsddp_sim_t* s, int on, const hsddp_terrain_t* t, const double* H, const int* map_of) {
-    if (!s) return HSDDP_EINVAL;
-    if (!on) { s->ter_on = false; return HSDDP_OK; }      // later runs launch the kernels without the terrain; the buffers and the parameters are kept
-    if (!t || !H) return HSDDP_EINVAL;
-    if (!std::isfinite(t->x0) || !std::isfinite(t->y0) || !std::isfinite(t->cx) || !std::isfinite(t->cy) || !std::isfinite(t->w_td)) return HSDDP_EINVAL;
-    if (!(t->cx > 0.0) || !(t->cy > 0.0) || t->w_td < 0.0) return HSDDP_EINVAL;
-    if (t->nx < 1 || t->nx > 1024 || t->ny < 1 || t->ny > 1024 || t->n_maps < 1 || t->n_maps > 4096) return HSDDP_EINVAL;
-    const size_t cells = (size_t)t->n_maps * (size_t)t->nx * (size_t)t->ny;
-    if (cells > ((size_t)1 << 22)) return HSDDP_EINVAL;
-    for (size_t i = 0; i < cells; i++) if (!std::isfinite(H[i])) return HSDDP_EINVAL;
-    hsddp_handle* h = s->h;
-    const size_t total = (size_t)h->batch * s->R;
-    if (map_of) for (size_t i = 0; i < total; i++) if (map_of[i] < 0 || map_of[i] >= t->n_maps) return HSDDP_EINVAL;
-    if (h->f32) return HSDDP_ENOTSUP;
-    HIPCK(hipSetDevice(h->device));
-    // (as UNI_CK of hsddp_contact_set: an allocation that fails returns its code at once, what was made before it is kept, and the terrain stays as it was)
-#define TER_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
-    if (!s->d_ter) TER_CK(hipMalloc((void**)&s->d_ter, sizeof(WbsTerArgs)));
-    if (!s->d_ter_rows) TER_CK(hipMalloc((void**)&s->d_ter_rows, total * SIM_TER_ROW * 8));
-    if (!s->d_ter_map) TER_CK(hipMalloc((void**)&s->d_ter_map, total * sizeof(int)));
-    if (s->uni_keep && !s->d_ter_E) { TER_CK(hipMalloc((void**)&s->d_ter_E, total * 4 * 8)); HIPCK(hipMemsetAsync(s->d_ter_E, 0, total * 4 * 8, h->stream)); }
-    if (cells > s->ter_cap) {      // the grid grows: the new block first, so that a failure leaves the old one in place
-        double* nb = nullptr;
-        TER_CK(hipMalloc((void**)&nb, cells * 8));
-        HIPCK(hipStreamSynchronize(h->stream));
-        if (s->d_ter_H) hipFree(s->d_ter_H);
-        s->d_ter_H = nb; s->ter_cap = cells;
-    }
-#undef TER_CK
-    HIPCK(hipMemcpyAsync(s->d_ter_H, H, cells * 8, hipMemcpyHostToDevice, h->stream));
-    if (map_of) HIPCK(hipMemcpyAsync(s->d_ter_map, map_of, total * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    else HIPCK(hipMemsetAsync(s->d_ter_map, 0, total * sizeof(int), h->stream));
-    WbsTerArgs a;
-    a.H = s->d_ter_H; a.map_of = s->d_ter_map; a.nx = t->nx; a.ny = t->ny; a.n_maps = t->n_maps; a.early = t->early ? 1 : 0;
-    a.x0 = t->x0; a.y0 = t->y0; a.cx = t->cx; a.cy = t->cy; a.w_td = t->w_td; a.rows = s->d_ter_rows; a.E = s->d_ter_E;
-    HIPCK(hipMemcpyAsync(s->d_ter, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));      // H and map_of are the caller's: they may go once the call returns
-    s->ter_on = true; s->ter = *t; s->ter.early = a.early;
-    return HSDDP_OK;
-}
-
-int hsddp_terrain_get_params(hsddp_sim_t* s, int* on, hsddp_terrain_t* t) {
-    if (!s || !on || !t) return HSDDP_EINVAL;
-    *on = s->ter_on ? 1 : 0; *t = s->ter;
-    return HSDDP_OK;
-}
-
-int hsddp_terrain_get(hsddp_sim_t* s, int b0, int nb, hsddp_terrain_row_t* rows) {
-    if (!sim_range_ok(s, b0, nb) || !rows || !s->last_ter) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(s->h->device));
-    const size_t cnt = (size_t)nb * s->R, off = (size_t)b0 * s->R;
-    std::vector<double> r(cnt * SIM_TER_ROW);
-    HIPCK(hipMemcpy(r.data(), s->d_ter_rows + off * SIM_TER_ROW, r.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < cnt; i++) {
-        const double* q = &r[i * SIM_TER_ROW];
-        rows[i].first_early = (int)q[0]; rows[i].n_early = (int)q[1]; rows[i].n_early_release = (int)q[2]; rows[i].n_held = (int)q[3]; rows[i].early_final = (int)q[4]; rows[i].pad = 0;
-        rows[i].max_pen = q[5];
-    }
-    return HSDDP_OK;
-}
-
-int hsddp_plant_set(hsddp_sim_t* s, int on, int n_plants, const double* P, const int* plant_of) {
-    if (!s) return HSDDP_EINVAL;
-    if (!on) { s->plant_on = false; return HSDDP_OK; }      // later runs launch the kernels without the plant; the buffers and the table are kept
-    hsddp_handle* h = s->h;
-    const size_t total = (size_t)h->batch * s->R;
-    if (!plant_table_ok(n_plants, P, plant_of, total)) return HSDDP_EINVAL;
-    if (h->f32) return HSDDP_ENOTSUP;
-    HIPCK(hipSetDevice(h->device));
-    std::vector<double> rows; std::vector<int> idx;
-    plant_table_pack(n_plants, P, plant_of, total, rows, idx);
-    // (as TER_CK of hsddp_terrain_set: an allocation that fails returns its code at once, what was made before it is kept, and the plant stays as it was)
-#define PLANT_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
-    if (!s->d_plant) PLANT_CK(hipMalloc((void**)&s->d_plant, sizeof(WbsPlantArgs)));
-    if (!s->d_plant_of) PLANT_CK(hipMalloc((void**)&s->d_plant_of, total * sizeof(int)));
-    if (!s->d_uni_grows) PLANT_CK(hipMalloc((void**)&s->d_uni_grows, total * SIM_GRF_ROW * 8));
-    if (!s->d_uni_grf) {
-        PLANT_CK(hipMalloc((void**)&s->d_uni_grf, sizeof(WbsGrfArgs)));
-        WbsGrfArgs g;
-        g.mu = 1.0; g.fz_min = 0.0; g.rows = s->d_uni_grows; g.Y = nullptr;      // (nobody reads these records: hsddp_grf_get refuses while the records are off)
-        HIPCK(hipMemcpyAsync(s->d_uni_grf, &g, sizeof(g), hipMemcpyHostToDevice, h->stream));
-    }
-    if (!s->d_sub) {      // the walk reads its trip count from here for S = 1 too; from now on hsddp_substep_set keeps it current
-        PLANT_CK(hipMalloc((void**)&s->d_sub, sizeof(WbsSubArgs)));
-        WbsSubArgs b;
-        b.substeps = s->substeps; b.pad = 0;
-        HIPCK(hipMemcpyAsync(s->d_sub, &b, sizeof(b), hipMemcpyHostToDevice, h->stream));
-    }
-    if ((size_t)n_plants > s->plant_cap) {      // the table grows: the new block first, so that a failure leaves the old one in place
-        double* nb = nullptr;
-        PLANT_CK(hipMalloc((void**)&nb, (size_t)n_plants * SIM_PLANT_ROW * 8));
-        HIPCK(hipStreamSynchronize(h->stream));
-        if (s->d_plant_P) hipFree(s->d_plant_P);
-        s->d_plant_P = nb; s->plant_cap = (size_t)n_plants;
-    }
-#undef PLANT_CK
-    HIPCK(hipMemcpyAsync(s->d_plant_P, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCK(hipMemcpyAsync(s->d_plant_of, idx.data(), total * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    WbsPlantArgs a;
-    a.P = s->d_plant_P; a.plant_of = s->d_plant_of; a.n_plants = n_plants; a.pad = 0;
-    HIPCK(hipMemcpyAsync(s->d_plant, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));      // the sources are locals and the caller's: they may go once the call returns
-    s->plant_on = true; s->n_plants = n_plants; s->plant_rows.swap(rows);
-    return HSDDP_OK;
-}
-
-int hsddp_plant_get_params(hsddp_sim_t* s, int* on, int* n_plants) {
-    if (!s || !on || !n_plants) return HSDDP_EINVAL;
-    *on = s->plant_on ? 1 : 0; *n_plants = s->n_plants;
-    return HSDDP_OK;
-}
-
-int hsddp_plant_get_table(hsddp_sim_t* s, int p0, int np, double* P) {
-    if (!s || !P || np <= 0 || p0 < 0 || p0 > s->n_plants - np) return HSDDP_EINVAL;
-    memcpy(P, s->plant_rows.data() + (size_t)p0 * SIM_PLANT_ROW, (size_t)np * SIM_PLANT_ROW * 8);
-    return HSDDP_OK;
-}
-
-const double* hsddp_sim_device_final(hsddp_sim_t* s) { return s ? s->d_final : nullptr; }
-
-int hsddp_sim_get_kernel_time_ms(hsddp_sim_t* s, float* ms) {
-    if (!s || !ms || !s->timed) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(s->h->device));
-    HIPCK(hipEventElapsedTime(ms, s->ev0, s->ev1));
-    return HSDDP_OK;
-}
-
-
-// ------------------------------------------------------------------------------------------------ MPC episodes (hsddp_episode.h)
-}  // extern "C"
-static_assert(sizeof(hsddp_episode_row_t) == sizeof(EpiRow), "the device row is hsddp_episode_row_t");
-struct hsddp_episode {
-    hsddp_handle* h = nullptr;
-    hsddp_sim* sim = nullptr;                               // one sample per problem, n_exec steps, trajectories kept
-    int n_exec = 0, max_ticks = 0, keep = 0, tick = 0, n_impacts = 0;
-    bool started = false;                                   // hsddp_episode_reset has given the states
-    int pending = -1;                                       // phase of the bound window whose reset map lies behind the tick's last step, else -1
-    std::vector<int> map, map_new;                          // host copies of the step map: the bound one (source of the upload) / scratch of a rebind
-    std::vector<EpiRow> row0;                               // [B] rows of a reset (source of the upload)
-    double* d_state = nullptr; EpiRow* d_rows = nullptr;    // [B][36] ; [B]
-    double *d_X = nullptr, *d_U = nullptr, *d_Y = nullptr;  // the log (keep): [B][max_ticks n_exec + 1][36], [B][max_ticks n_exec][12] twice
-};
-static void episode_free(hsddp_episode* e) {
-    if (!e) return;
-    hipSetDevice(e->h->device);
-    if (e->h->stream) hipStreamSynchronize(e->h->stream);
-    if (e->sim) sim_free(e->sim);
-    void* p[] = {e->d_state, e->d_rows, e->d_X, e->d_U, e->d_Y};
-    for (void* q : p) if (q) hipFree(q);
-    delete e;
-}
-static bool episode_range_ok(const hsddp_episode* e, int b0, int nb) { return e && nb > 0 && b0 >= 0 && b0 <= e->h->batch - nb; }
-// seed of tick t (hsddp_episode.h): the seed itself, then the raw outputs of SplitMix64(seed)
-static unsigned long long episode_tick_seed(unsigned long long seed, int t) {
-    if (t == 0) return seed;
-    unsigned long long z = seed + (unsigned long long)t * WBS_MC_G;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-extern "C" {
-
-int hsddp_episode_create(hsddp_handle_t* h, int n_exec, int max_ticks, int keep_log, hsddp_episode_t** out) {
-    if (!h || !out || n_exec <= 0 || max_ticks <= 0 || h->f32) return HSDDP_EINVAL;
-    const size_t B = h->batch, steps = (size_t)max_ticks * n_exec;
-    if (steps >= ((size_t)1 << 31)) return HSDDP_ENOTSUP;      // global step indices are ints
-    hsddp_sim* s = nullptr;
-    int rc = hsddp_sim_create(h, 1, n_exec, 1, &s);
-    if (rc != HSDDP_OK) return rc;
-    hsddp_episode* e = new hsddp_episode();
-    e->h = h; e->sim = s; e->n_exec = n_exec; e->max_ticks = max_ticks; e->keep = keep_log ? 1 : 0;
-    e->map.assign(3 * (size_t)n_exec, 0); e->map_new.assign(3 * (size_t)n_exec, 0);
-    sim_step_map(h, n_exec, e->map.data(), &e->pending);
-    EpiRow r0{};
-    r0.min_height = HUGE_VAL; r0.min_fz = HUGE_VAL; r0.min_cone = HUGE_VAL; r0.max_fz = -HUGE_VAL; r0.first_slip = -1; r0.end_step = -1;
-    e->row0.assign(B, r0);
-#define EPI_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[hsddp_hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); episode_free(e); return e_ == hipErrorOutOfMemory ? HSDDP_ENOMEM : HSDDP_ENODEV; } } while (0)
-    EPI_CK(hipMalloc((void**)&e->d_state, B * 36 * 8));
-    EPI_CK(hipMalloc((void**)&e->d_rows, B * sizeof(EpiRow)));
-    if (e->keep) {
-        EPI_CK(hipMalloc((void**)&e->d_X, B * (steps + 1) * 36 * 8)); EPI_CK(hipMalloc((void**)&e->d_U, B * steps * 12 * 8)); EPI_CK(hipMalloc((void**)&e->d_Y, B * steps * 12 * 8));
-        EPI_CK(hipMemset(e->d_X, 0, B * (steps + 1) * 36 * 8)); EPI_CK(hipMemset(e->d_U, 0, B * steps * 12 * 8)); EPI_CK(hipMemset(e->d_Y, 0, B * steps * 12 * 8));
-    }
-    EPI_CK(hipMemset(e->d_state, 0, B * 36 * 8));
-    s->uni_keep = true; s->uni_hold = &e->d_rows[0].end_reason; s->uni_hold_stride = (int)(sizeof(EpiRow) / sizeof(int));      // (hsddp_contact.h: F lives across ticks, a frozen robot keeps its own)
-    EPI_CK(hipMemcpy(e->d_rows, e->row0.data(), B * sizeof(EpiRow), hipMemcpyHostToDevice));
-#undef EPI_CK
-    *out = e; return HSDDP_OK;
-}
-
-void hsddp_episode_destroy(hsddp_episode_t* e) { episode_free(e); }
-
-int hsddp_episode_reset(hsddp_episode_t* e, const double* x0, int src_device) {
-    if (!e || !x0) return HSDDP_EINVAL;
-    hsddp_handle* h = e->h;
-    const size_t B = h->batch, steps = (size_t)e->max_ticks * e->n_exec;
-    HIPCK(hipSetDevice(h->device));
-    HIPCK(hipMemcpyAsync(e->d_state, x0, B * 36 * 8, src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    HIPCK(hipMemcpyAsync(h->d_x0, e->d_state, B * 36 * 8, hipMemcpyDeviceToDevice, h->stream));      // what hsddp_set_initial_condition leaves
-    HIPCK(hipMemcpyAsync(e->d_rows, e->row0.data(), B * sizeof(EpiRow), hipMemcpyHostToDevice, h->stream));
-    if (e->keep) {
-        HIPCK(hipMemsetAsync(e->d_X, 0, B * (steps + 1) * 36 * 8, h->stream)); HIPCK(hipMemsetAsync(e->d_U, 0, B * steps * 12 * 8, h->stream));
-        HIPCK(hipMemsetAsync(e->d_Y, 0, B * steps * 12 * 8, h->stream));
-    }
-    if (e->sim->d_uni_F) HIPCK(hipMemsetAsync(e->sim->d_uni_F, 0, B * 4 * 8, h->stream));      // (hsddp_contact.h) every foot attached again
-    if (e->sim->d_ter_E) HIPCK(hipMemsetAsync(e->sim->d_ter_E, 0, B * 4 * 8, h->stream));      // (hsddp_terrain.h) no swing foot held
-    HIPCK(hipStreamSynchronize(h->stream));
-    e->tick = 0; e->n_impacts = 0; e->started = true;
-    return HSDDP_OK;
-}
-
-int hsddp_episode_advance(hsddp_episode_t* e, const hsddp_mc_dist_t* dist, const double* kick, int kick_device) {
-    if (!e || !e->started || e->tick >= e->max_ticks) return HSDDP_EINVAL;
-    hsddp_handle* h = e->h; hsddp_sim* s = e->sim;
-    if (kick && !dist) return HSDDP_EINVAL;                       // (the step of the push is the disturbance's)
-    if (dist && !mc_dist_ok(s, dist, kick)) return HSDDP_EINVAL;
-    const bool moved = s->gen != h->window_gen;
-    int pend = e->pending;
-    if (moved && !sim_step_map(h, e->n_exec, e->map_new.data(), &pend)) return HSDDP_EINVAL;      // the window no longer leads with n_exec whole-body knots
-    HIPCK(hipSetDevice(h->device));
-    // rebind: the step map of the new window into the simulation object's buffer (the walk below synchronises the stream).  It stays in place if the
-    // walk then fails with a device error - the map is that of the handle's current window either way; "nothing changed" is promised for HSDDP_EINVAL
-    if (moved) {
-        e->map.swap(e->map_new); e->pending = pend;
-        HIPCK(hipMemcpyAsync(s->d_map, e->map.data(), e->map.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        s->gen = h->window_gen;
-    }
-    int rc;
-    if (!dist) rc = hsddp_sim_run(s, e->d_state, 1);
-    else {
-        hsddp_mc_dist_t d = *dist; d.seed = episode_tick_seed(dist->seed, e->tick);
-        rc = hsddp_mc_run(s, e->d_state, 1, &d, kick, kick_device);
-    }
-    if (rc != HSDDP_OK) return rc;
-    EpiCommitArgs a;
-    a.n_exec = e->n_exec; a.tick = e->tick; a.max_ticks = e->max_ticks; a.handoff = e->pending < 0 ? 1 : 0;
-    a.map = s->d_map; a.simX = s->d_X; a.simU = s->d_U; a.simY = s->last_grf ? s->d_Y : nullptr;
-    a.fin = s->d_final; a.sim_rows = s->d_rows; a.extra = s->last_mc == 1 ? s->d_extra : nullptr; a.grf_rows = s->last_grf ? s->d_grf_rows : nullptr;
-    a.st = h->d_st; a.rows = e->d_rows; a.state = e->d_state; a.x0 = h->d_x0;
-    a.logX = e->d_X; a.logU = e->d_U; a.logY = e->d_Y;
-    // (both kernels are timed into the handle's kernel table, hsddp_get_kernel_times, like the solver's; the walk's time is the simulation object's)
-    { Timed t(h, "k_episode_commit"); hipLaunchKernelGGL(k_episode_commit, dim3((unsigned)h->batch), dim3(64), 0, h->stream, h->d_ph, a); }
-    if (e->pending >= 0) {      // the tick ended on a touchdown: the reset map the moved window no longer holds
-        Timed t(h, s->plant_on ? "k_episode_impact_plant" : "k_episode_impact");
-        if (s->plant_on)      // (hsddp_plant.h) the same map with each robot's own inertias
-            wbs_plant_impact_launch(h->stream, (unsigned)((h->batch + 15) / 16), h->d_ph, h->md, e->pending, h->batch, &e->d_rows[0].end_reason, (int)(sizeof(EpiRow) / sizeof(int)), e->d_state, h->d_x0, s->d_plant);
-        else
-        hipLaunchKernelGGL(k_episode_impact, dim3((unsigned)((h->batch + 15) / 16)), dim3(64), 0, h->stream, h->d_ph, h->md, e->pending, h->batch, (const EpiRow*)e->d_rows, e->d_state, h->d_x0);
-        e->n_impacts++;
-    }
-    HIPCK(hipGetLastError());
-    HIPCK(hipStreamSynchronize(h->stream));
-    drain_events(h);
-    e->tick++;
-    return HSDDP_OK;
-}
-
-int hsddp_episode_get_rows(hsddp_episode_t* e, int b0, int nb, hsddp_episode_row_t* rows, double* x_now) {
-    if (!episode_range_ok(e, b0, nb) || !rows) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(e->h->device));
-    HIPCK(hipMemcpy(rows, e->d_rows + b0, (size_t)nb * sizeof(EpiRow), hipMemcpyDeviceToHost));
-    if (x_now) HIPCK(hipMemcpy(x_now, e->d_state + (size_t)b0 * 36, (size_t)nb * 36 * 8, hipMemcpyDeviceToHost));
-    return HSDDP_OK;
-}
-
-int hsddp_episode_get_log(hsddp_episode_t* e, int b0, int nb, double* X, double* U, double* Y) {
-    if (!episode_range_ok(e, b0, nb) || !e->keep) return HSDDP_EINVAL;
-    HIPCK(hipSetDevice(e->h->device));
-    const size_t steps = (size_t)e->max_ticks * e->n_exec, sx = (steps + 1) * 36, su = steps * 12;
-    if (X) HIPCK(hipMemcpy(X, e->d_X + (size_t)b0 * sx, (size_t)nb * sx * 8, hipMemcpyDeviceToHost));
-    if (U) HIPCK(hipMemcpy(U, e->d_U + (size_t)b0 * su, (size_t)nb * su * 8, hipMemcpyDeviceToHost));
-    if (Y) HIPCK(hipMemcpy(Y, e->d_Y + (size_t)b0 * su, (size_t)nb * su * 8, hipMemcpyDeviceToHost));
-    return HSDDP_OK;
-}
-
-const double* hsddp_episode_device_state(hsddp_episode_t* e) { return e ? e->d_state : nullptr; }
-hsddp_sim_t* hsddp_episode_sim(hsddp_episode_t* e) { return e ? e->sim : nullptr; }
-
-int hsddp_episode_status(hsddp_episode_t* e, int* tick, int* n_alive, int* n_impacts) {
-    if (!e) return HSDDP_EINVAL;
-    if (n_alive) {
-        HIPCK(hipSetDevice(e->h->device));
-        std::vector<EpiRow> r((size_t)e->h->batch);
-        HIPCK(hipMemcpy(r.data(), e->d_rows, r.size() * sizeof(EpiRow), hipMemcpyDeviceToHost));
-        int n = 0; for (const EpiRow& q : r) n += q.end_reason == 0 ? 1 : 0;
-        *n_alive = n;
-    }
-    if (tick) *tick = e->tick;
-    if (n_impacts) *n_impacts = e->n_impacts;
-    return HSDDP_OK;
-}
-
-}  // extern "C"
+// ------------------------------------------------------------------------------------------------ closed-loop policy simulation (hsddp_sim.h) and MPC episodes (hsddp_episode.h)
+#include "sim_host.hpp"
 #endif

@@ -11,39 +11,23 @@
 
 namespace hs {
 
-#ifndef SIM_WPE
-#define SIM_WPE 1
-#endif
-// The launch shape of the other walks: 64 lanes, sixteen quads per wave, one wave per SIMD.  Nothing of the row is parked, so the parked column is that
-// of the twin WITH records and sub-step loop: 32 / 34 doubles per lane for the bilateral walks, 39 / 41 with the contact rule, 45 / 47 with the terrain
-// (at most 24 064 B per wave).
-#define WBS_PLANT_KERNEL(NAME, POLICY, PARK, PARAMS, ...)                                                                                                                      \
-    __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))                                                                               \
-    NAME(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU, \
-         PARAMS const WbsPlantArgs* pl) {                                                                                                                                      \
-        __shared__ double stash[(PARK) * 64];                                                                                                                                  \
-        const int g = blockIdx.x * 16 + (threadIdx.x >> 2);                                                                                                                    \
-        if (g >= total) return;                                                                                                                                                \
-        wbs_walk<QS, POLICY>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, POLICY{__VA_ARGS__});                            \
-    }
-#define WBS_P(...) __VA_ARGS__,
+// Nothing of the row is parked, so the parked column is that of the twin WITH records and sub-step loop: 32 / 34 doubles per lane for the bilateral
+// walks, 39 / 41 with the contact rule, 45 / 47 with the terrain (at most 24 064 B per wave).
 #define PARK_B (SIM_GRF_PARK + SIM_SUB_PARK)
 #define PARK_U (PARK_B + SIM_UNI_PARK)
 #define PARK_T (PARK_U + SIM_TER_PARK)
-WBS_PLANT_KERNEL(k_sim_quad_plant, WbsPlant, SIM_PARK + PARK_B, WBS_P(const WbsGrfArgs* gr, const WbsSubArgs* sb), gr, sb, pl)
-WBS_PLANT_KERNEL(k_sim_quad_mc_plant, WbsMcPlant<1>, SIM_PARK_MC + PARK_B, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb), mc, gr, sb, pl)
-WBS_PLANT_KERNEL(k_sim_quad_mc0_plant, WbsMcPlant<0>, SIM_PARK_MC + PARK_B, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb), mc, gr, sb, pl)
-WBS_PLANT_KERNEL(k_sim_quad_uni_plant, WbsUniPlant, SIM_PARK + PARK_U, WBS_P(const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un), gr, sb, un, pl)
-WBS_PLANT_KERNEL(k_sim_quad_mc_uni_plant, WbsMcUniPlant<1>, SIM_PARK_MC + PARK_U, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un), mc, gr, sb, un, pl)
-WBS_PLANT_KERNEL(k_sim_quad_mc0_uni_plant, WbsMcUniPlant<0>, SIM_PARK_MC + PARK_U, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un), mc, gr, sb, un, pl)
-WBS_PLANT_KERNEL(k_sim_quad_ter_plant, WbsTerPlant, SIM_PARK + PARK_T, WBS_P(const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsTerArgs* te), gr, sb, un, te, pl)
-WBS_PLANT_KERNEL(k_sim_quad_mc_ter_plant, WbsMcTerPlant<1>, SIM_PARK_MC + PARK_T, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsTerArgs* te), mc, gr, sb, un, te, pl)
-WBS_PLANT_KERNEL(k_sim_quad_mc0_ter_plant, WbsMcTerPlant<0>, SIM_PARK_MC + PARK_T, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsTerArgs* te), mc, gr, sb, un, te, pl)
+WBS_KERNEL(k_sim_quad_plant, WbsPlant, SIM_PARK + PARK_B, WBS_P(const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsPlantArgs* pl), gr, sb, pl)
+WBS_KERNEL(k_sim_quad_mc_plant, WbsMcPlant<1>, SIM_PARK_MC + PARK_B, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsPlantArgs* pl), mc, gr, sb, pl)
+WBS_KERNEL(k_sim_quad_mc0_plant, WbsMcPlant<0>, SIM_PARK_MC + PARK_B, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsPlantArgs* pl), mc, gr, sb, pl)
+WBS_KERNEL(k_sim_quad_uni_plant, WbsUniPlant, SIM_PARK + PARK_U, WBS_P(const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsPlantArgs* pl), gr, sb, un, pl)
+WBS_KERNEL(k_sim_quad_mc_uni_plant, WbsMcUniPlant<1>, SIM_PARK_MC + PARK_U, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsPlantArgs* pl), mc, gr, sb, un, pl)
+WBS_KERNEL(k_sim_quad_mc0_uni_plant, WbsMcUniPlant<0>, SIM_PARK_MC + PARK_U, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsPlantArgs* pl), mc, gr, sb, un, pl)
+WBS_KERNEL(k_sim_quad_ter_plant, WbsTerPlant, SIM_PARK + PARK_T, WBS_P(const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsTerArgs* te, const WbsPlantArgs* pl), gr, sb, un, te, pl)
+WBS_KERNEL(k_sim_quad_mc_ter_plant, WbsMcTerPlant<1>, SIM_PARK_MC + PARK_T, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsTerArgs* te, const WbsPlantArgs* pl), mc, gr, sb, un, te, pl)
+WBS_KERNEL(k_sim_quad_mc0_ter_plant, WbsMcTerPlant<0>, SIM_PARK_MC + PARK_T, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un, const WbsTerArgs* te, const WbsPlantArgs* pl), mc, gr, sb, un, te, pl)
 #undef PARK_T
 #undef PARK_U
 #undef PARK_B
-#undef WBS_P
-#undef WBS_PLANT_KERNEL
 
 // The pending reset map of an episode on each robot's own plant (k_episode_impact of episode.hpp is its twin): grid = ceil(B / 16) waves of sixteen quads.
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))
@@ -53,26 +37,19 @@ k_episode_impact_plant(const PhaseDev* ph_, ModelDev md, int pi, int total, cons
     wbs_plant_impact<QS>((PhaseC*)ph_, md, pi, (size_t)g, frozen, stride, state, x0, pl);
 }
 
-// The one launch of a run with the plant on.  un null: the bilateral walk; te null: the walk with the contact rule; else the one with the terrain.  mc
-// null - the plain walk, else the disturbed one (noise: with the generator).  As wbs_ter_launch it leaves the runtime's error state to the caller.
-void wbs_plant_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
-                      double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un,
-                      const WbsTerArgs* te, const WbsPlantArgs* pl) {
-#define PLANT_LAUNCH(K, ...) hipLaunchKernelGGL(K, dim3(grid), dim3(64), 0, stream, ph, md, map, n_steps, n_samples, total, x0, xfinal, rows, trajX, trajU, __VA_ARGS__)
-    if (!un) {
-        if (!mc) PLANT_LAUNCH(k_sim_quad_plant, gr, sb, pl);
-        else if (noise) PLANT_LAUNCH(k_sim_quad_mc_plant, mc, gr, sb, pl);
-        else PLANT_LAUNCH(k_sim_quad_mc0_plant, mc, gr, sb, pl);
-    } else if (!te) {
-        if (!mc) PLANT_LAUNCH(k_sim_quad_uni_plant, gr, sb, un, pl);
-        else if (noise) PLANT_LAUNCH(k_sim_quad_mc_uni_plant, mc, gr, sb, un, pl);
-        else PLANT_LAUNCH(k_sim_quad_mc0_uni_plant, mc, gr, sb, un, pl);
+// the _plant twin of the family the pick's contact model names
+void wbs_plant_launch(const WbsLaunch& L) {
+    const bool plain = L.pick.variant == SIM_VAR_PLAIN, noise = L.pick.variant == SIM_VAR_MC;
+    if (L.pick.contact == SIM_BILATERAL) {
+        if (plain) wbs_launch(L, k_sim_quad_plant, L.gr, L.sb, L.pl);
+        else wbs_launch(L, noise ? k_sim_quad_mc_plant : k_sim_quad_mc0_plant, L.mc, L.gr, L.sb, L.pl);
+    } else if (L.pick.contact == SIM_CONTACT_RULE) {
+        if (plain) wbs_launch(L, k_sim_quad_uni_plant, L.gr, L.sb, L.un, L.pl);
+        else wbs_launch(L, noise ? k_sim_quad_mc_uni_plant : k_sim_quad_mc0_uni_plant, L.mc, L.gr, L.sb, L.un, L.pl);
     } else {
-        if (!mc) PLANT_LAUNCH(k_sim_quad_ter_plant, gr, sb, un, te, pl);
-        else if (noise) PLANT_LAUNCH(k_sim_quad_mc_ter_plant, mc, gr, sb, un, te, pl);
-        else PLANT_LAUNCH(k_sim_quad_mc0_ter_plant, mc, gr, sb, un, te, pl);
+        if (plain) wbs_launch(L, k_sim_quad_ter_plant, L.gr, L.sb, L.un, L.te, L.pl);
+        else wbs_launch(L, noise ? k_sim_quad_mc_ter_plant : k_sim_quad_mc0_ter_plant, L.mc, L.gr, L.sb, L.un, L.te, L.pl);
     }
-#undef PLANT_LAUNCH
 }
 
 void wbs_plant_impact_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, int pi, int total, const int* frozen, int stride, double* state, double* x0,

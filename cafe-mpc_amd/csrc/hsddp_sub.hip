@@ -15,46 +15,24 @@
 
 namespace hs {
 
-#ifndef SIM_WPE
-#define SIM_WPE 1
-#endif
-// The same launch shape as the kernels of wb_sim.hpp: 64 lanes, sixteen quads per wave, one wave per SIMD; three more doubles per lane in the parked
-// column (27 / 29 doubles without records, 32 / 34 with them: at most 17 408 B per wave); sb points at the trip count in device memory.
-#define WBS_SUB_KERNEL(NAME, POLICY, PARK, PARAMS, ...)                                                                                                                        \
-    __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))                                                                               \
-    NAME(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU, \
-         PARAMS const WbsSubArgs* sb) {                                                                                                                                        \
-        __shared__ double stash[((PARK) + SIM_SUB_PARK) * 64];                                                                                                                 \
-        const int g = blockIdx.x * 16 + (threadIdx.x >> 2);                                                                                                                    \
-        if (g >= total) return;                                                                                                                                                \
-        wbs_walk<QS, POLICY>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, POLICY{__VA_ARGS__});                            \
-    }
-#define WBS_P(...) __VA_ARGS__,
-WBS_SUB_KERNEL(k_sim_quad_sub, WbsSub, SIM_PARK, , sb)
-WBS_SUB_KERNEL(k_sim_quad_mc_sub, WbsMcSub<1>, SIM_PARK_MC, WBS_P(const WbsMcArgs* mc), mc, sb)
-WBS_SUB_KERNEL(k_sim_quad_mc0_sub, WbsMcSub<0>, SIM_PARK_MC, WBS_P(const WbsMcArgs* mc), mc, sb)
-WBS_SUB_KERNEL(k_sim_quad_grf_sub, WbsGrfSub, SIM_PARK + SIM_GRF_PARK, WBS_P(const WbsGrfArgs* gr), gr, sb)
-WBS_SUB_KERNEL(k_sim_quad_mc_grf_sub, WbsMcGrfSub<1>, SIM_PARK_MC + SIM_GRF_PARK, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr), mc, gr, sb)
-WBS_SUB_KERNEL(k_sim_quad_mc0_grf_sub, WbsMcGrfSub<0>, SIM_PARK_MC + SIM_GRF_PARK, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr), mc, gr, sb)
-#undef WBS_P
-#undef WBS_SUB_KERNEL
+// Three more doubles per lane in the parked column (27 / 29 doubles without records, 32 / 34 with them: at most 17 408 B per wave); sb points at the
+// trip count in device memory.
+WBS_KERNEL(k_sim_quad_sub, WbsSub, SIM_PARK + SIM_SUB_PARK, WBS_P(const WbsSubArgs* sb), sb)
+WBS_KERNEL(k_sim_quad_mc_sub, WbsMcSub<1>, SIM_PARK_MC + SIM_SUB_PARK, WBS_P(const WbsMcArgs* mc, const WbsSubArgs* sb), mc, sb)
+WBS_KERNEL(k_sim_quad_mc0_sub, WbsMcSub<0>, SIM_PARK_MC + SIM_SUB_PARK, WBS_P(const WbsMcArgs* mc, const WbsSubArgs* sb), mc, sb)
+WBS_KERNEL(k_sim_quad_grf_sub, WbsGrfSub, SIM_PARK + SIM_GRF_PARK + SIM_SUB_PARK, WBS_P(const WbsGrfArgs* gr, const WbsSubArgs* sb), gr, sb)
+WBS_KERNEL(k_sim_quad_mc_grf_sub, WbsMcGrfSub<1>, SIM_PARK_MC + SIM_GRF_PARK + SIM_SUB_PARK, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb), mc, gr, sb)
+WBS_KERNEL(k_sim_quad_mc0_grf_sub, WbsMcGrfSub<0>, SIM_PARK_MC + SIM_GRF_PARK + SIM_SUB_PARK, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb), mc, gr, sb)
 
-// The one launch of a sub-stepped run: mc null - the plain walk, else the disturbed one (noise: with the generator); gr null - without records.
-// It does not look at the runtime's error state: a launch that fails is reported by the caller's hipGetLastError, as for the kernels of wb_sim.hpp
-// (reading the error here would reset it and hide the failure from that check).
-void wbs_sub_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
-                    double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb) {
-#define SUB_LAUNCH(K, ...) hipLaunchKernelGGL(K, dim3(grid), dim3(64), 0, stream, ph, md, map, n_steps, n_samples, total, x0, xfinal, rows, trajX, trajU, __VA_ARGS__)
-    if (!gr) {
-        if (!mc) SUB_LAUNCH(k_sim_quad_sub, sb);
-        else if (noise) SUB_LAUNCH(k_sim_quad_mc_sub, mc, sb);
-        else SUB_LAUNCH(k_sim_quad_mc0_sub, mc, sb);
+void wbs_sub_launch(const WbsLaunch& L) {
+    const bool noise = L.pick.variant == SIM_VAR_MC;
+    if (!L.pick.records) {
+        if (L.pick.variant == SIM_VAR_PLAIN) wbs_launch(L, k_sim_quad_sub, L.sb);
+        else wbs_launch(L, noise ? k_sim_quad_mc_sub : k_sim_quad_mc0_sub, L.mc, L.sb);
     } else {
-        if (!mc) SUB_LAUNCH(k_sim_quad_grf_sub, gr, sb);
-        else if (noise) SUB_LAUNCH(k_sim_quad_mc_grf_sub, mc, gr, sb);
-        else SUB_LAUNCH(k_sim_quad_mc0_grf_sub, mc, gr, sb);
+        if (L.pick.variant == SIM_VAR_PLAIN) wbs_launch(L, k_sim_quad_grf_sub, L.gr, L.sb);
+        else wbs_launch(L, noise ? k_sim_quad_mc_grf_sub : k_sim_quad_mc0_grf_sub, L.mc, L.gr, L.sb);
     }
-#undef SUB_LAUNCH
 }
 
 }  // namespace hs

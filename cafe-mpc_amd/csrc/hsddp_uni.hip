@@ -11,36 +11,15 @@
 
 namespace hs {
 
-#ifndef SIM_WPE
-#define SIM_WPE 1
-#endif
-// The launch shape of the other walks: 64 lanes, sixteen quads per wave, one wave per SIMD.  Records and the sub-step loop are always compiled in, so
-// the parked column is that of the _grf_sub twins plus SIM_UNI_PARK doubles per lane (39 / 41: at most 20 992 B per wave).
-#define WBS_UNI_KERNEL(NAME, POLICY, PARK, PARAMS, ...)                                                                                                                        \
-    __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))                                                                               \
-    NAME(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU, \
-         PARAMS const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un) {                                                                                            \
-        __shared__ double stash[((PARK) + SIM_GRF_PARK + SIM_SUB_PARK + SIM_UNI_PARK) * 64];                                                                                   \
-        const int g = blockIdx.x * 16 + (threadIdx.x >> 2);                                                                                                                    \
-        if (g >= total) return;                                                                                                                                                \
-        wbs_walk<QS, POLICY>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, POLICY{__VA_ARGS__});                            \
-    }
-#define WBS_P(...) __VA_ARGS__,
-WBS_UNI_KERNEL(k_sim_quad_uni, WbsUni, SIM_PARK, , gr, sb, un)
-WBS_UNI_KERNEL(k_sim_quad_mc_uni, WbsMcUni<1>, SIM_PARK_MC, WBS_P(const WbsMcArgs* mc), mc, gr, sb, un)
-WBS_UNI_KERNEL(k_sim_quad_mc0_uni, WbsMcUni<0>, SIM_PARK_MC, WBS_P(const WbsMcArgs* mc), mc, gr, sb, un)
-#undef WBS_P
-#undef WBS_UNI_KERNEL
+// Records and the sub-step loop are always compiled in, so the parked column is that of the _grf_sub twins plus SIM_UNI_PARK doubles per lane (39 / 41:
+// at most 20 992 B per wave).
+WBS_KERNEL(k_sim_quad_uni, WbsUni, SIM_PARK + SIM_GRF_PARK + SIM_SUB_PARK + SIM_UNI_PARK, WBS_P(const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un), gr, sb, un)
+WBS_KERNEL(k_sim_quad_mc_uni, WbsMcUni<1>, SIM_PARK_MC + SIM_GRF_PARK + SIM_SUB_PARK + SIM_UNI_PARK, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un), mc, gr, sb, un)
+WBS_KERNEL(k_sim_quad_mc0_uni, WbsMcUni<0>, SIM_PARK_MC + SIM_GRF_PARK + SIM_SUB_PARK + SIM_UNI_PARK, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un), mc, gr, sb, un)
 
-// The one launch of a run with the rule on: mc null - the plain walk, else the disturbed one (noise: with the generator).  As wbs_sub_launch it leaves
-// the runtime's error state to the caller.
-void wbs_uni_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, const int* map, int n_steps, int n_samples, int total, const double* x0,
-                    double* xfinal, double* rows, double* trajX, double* trajU, const WbsMcArgs* mc, bool noise, const WbsGrfArgs* gr, const WbsSubArgs* sb, const WbsUniArgs* un) {
-#define UNI_LAUNCH(K, ...) hipLaunchKernelGGL(K, dim3(grid), dim3(64), 0, stream, ph, md, map, n_steps, n_samples, total, x0, xfinal, rows, trajX, trajU, __VA_ARGS__)
-    if (!mc) UNI_LAUNCH(k_sim_quad_uni, gr, sb, un);
-    else if (noise) UNI_LAUNCH(k_sim_quad_mc_uni, mc, gr, sb, un);
-    else UNI_LAUNCH(k_sim_quad_mc0_uni, mc, gr, sb, un);
-#undef UNI_LAUNCH
+void wbs_uni_launch(const WbsLaunch& L) {
+    if (L.pick.variant == SIM_VAR_PLAIN) wbs_launch(L, k_sim_quad_uni, L.gr, L.sb, L.un);
+    else wbs_launch(L, L.pick.variant == SIM_VAR_MC ? k_sim_quad_mc_uni : k_sim_quad_mc0_uni, L.mc, L.gr, L.sb, L.un);
 }
 
 }  // namespace hs

@@ -21,6 +21,7 @@
 // (Jc v of a foot is its velocity, which the bias pass leaves behind anyway; y = 0, so no product with L^T is needed.)
 #pragma once
 #include "wb_quad.hpp"
+#include "sim_pick.hpp"
 
 namespace hs {
 
@@ -998,56 +999,70 @@ template <class Q> HD void wbs_plant_impact(PhaseC* ph, const ModelDev& md, int 
     _Pragma("unroll") for (int j = 0; j < 3; j++) { Q::st(state, g * 36 + 24 + j, 3, o3[j]); Q::st(x0, g * 36 + 6 + j, 3, ql[j]); Q::st(x0, g * 36 + 24 + j, 3, o3[j]); }
 }
 
-#if !defined(HS_HOST_EMU) && !defined(HS_SIM_WALK_ONLY)      // (HS_SIM_WALK_ONLY: hsddp_sub.hip takes the walk and defines kernels of its own)
-// grid = ceil(B R / 16) waves of sixteen quads.  The loop is sequential in the knots, so a launch has B R / 16 waves whatever the window length.
+#if !defined(HS_HOST_EMU)
+// The kernels.  grid = ceil(B R / 16) waves of sixteen quads.  The loop is sequential in the knots, so a launch has B R / 16 waves whatever the window length.
 #ifndef SIM_WPE
 #define SIM_WPE 1      // waves per SIMD the kernel is compiled for (as k_rollout_quad: up to 512 registers)
 #endif
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))
-k_sim_quad(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU) {
-    __shared__ double stash[SIM_PARK * 64];      // lane t parks in column t (wbs_walk)
-    const int g = blockIdx.x * 16 + (threadIdx.x >> 2);
-    if (g >= total) return;      // (a quad leaves or stays as a whole)
-    wbs_walk<QS>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash);
-}
-// The disturbed walk (hsddp_mc_run): the same program with the WbsMc policy; mc points at the run's switches in device memory.  k_sim_quad_mc
-// draws noise, k_sim_quad_mc0 is the walk of a run without any (see WbsMc).
-#define WBS_MC_KERNEL(NAME, NOISE)                                                                                                                                             \
+// Every walk is this wrapper around wbs_walk: 64 lanes, one wave per SIMD, lane t parks in column t of `stash` (PARK doubles per lane: the sum of the
+// SIM_*_PARK of what the policy carries), and a quad leaves or stays as a whole.  PARAMS: the kernel's parameters behind the eleven common ones, WBS_P(...)
+// or nothing; the variadic tail: the same names, as the members of POLICY.  Names, types and order of the parameters are part of the mangled kernel
+// names, which the profiles and `make resources` key on.
+#define WBS_P(...) , __VA_ARGS__
+#define WBS_KERNEL(NAME, POLICY, PARK, PARAMS, ...)                                                                                                                            \
     __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))                                                                               \
-    NAME(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU, \
-         const WbsMcArgs* mc) {                                                                                                                                                \
-        __shared__ double stash[SIM_PARK_MC * 64];                                                                                                                             \
+    NAME(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU \
+         PARAMS) {                                                                                                                                                             \
+        __shared__ double stash[(PARK) * 64];                                                                                                                                  \
         const int g = blockIdx.x * 16 + (threadIdx.x >> 2);                                                                                                                    \
         if (g >= total) return;                                                                                                                                                \
-        wbs_walk<QS, WbsMc<NOISE>>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, WbsMc<NOISE>{mc});                         \
+        wbs_walk<QS, POLICY>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, POLICY{__VA_ARGS__});                            \
     }
-WBS_MC_KERNEL(k_sim_quad_mc, 1)
-WBS_MC_KERNEL(k_sim_quad_mc0, 0)
-#undef WBS_MC_KERNEL
-// The walks with contact-force records (hsddp_grf_set): the same three programs with GRF 1 in the policy; gr points at the thresholds and the
-// destinations in device memory.  The host picks one of the six kernels; with the records off it launches the three above.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))
-k_sim_quad_grf(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU,
-               const WbsGrfArgs* gr) {
-    __shared__ double stash[(SIM_PARK + SIM_GRF_PARK) * 64];
-    const int g = blockIdx.x * 16 + (threadIdx.x >> 2);
-    if (g >= total) return;
-    wbs_walk<QS, WbsGrf>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, WbsGrf{gr});
+
+// One launch of a walk, host side: the stream, the grid, the eleven common kernel arguments, which kernel (sim_pick.hpp) and the blocks of switches in
+// device memory that its policy points at (those of switches the pick leaves out are not read).
+struct WbsLaunch {
+    hipStream_t stream; unsigned grid;
+    const PhaseDev* ph; const ModelDev* md; const int* map; int n_steps, n_samples, total; const double* x0; double *xfinal, *rows, *trajX, *trajU;
+    SimPick pick;
+    const WbsMcArgs* mc; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsPlantArgs* pl;
+};
+template <class K, class... A> void wbs_launch(const WbsLaunch& L, K kernel, A... policy_args) {
+    hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(64), 0, L.stream, L.ph, *L.md, L.map, L.n_steps, L.n_samples, L.total, L.x0, L.xfinal, L.rows, L.trajX, L.trajU, policy_args...);
 }
-#define WBS_MC_GRF_KERNEL(NAME, NOISE)                                                                                                                                         \
-    __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM_WPE, SIM_WPE)))                                                                               \
-    NAME(const PhaseDev* ph_, ModelDev md, const int* map, int n_steps, int n_samples, int total, const double* x0, double* xfinal, double* rows, double* trajX, double* trajU, \
-         const WbsMcArgs* mc, const WbsGrfArgs* gr) {                                                                                                                          \
-        __shared__ double stash[(SIM_PARK_MC + SIM_GRF_PARK) * 64];                                                                                                            \
-        const int g = blockIdx.x * 16 + (threadIdx.x >> 2);                                                                                                                    \
-        if (g >= total) return;                                                                                                                                                \
-        wbs_walk<QS, WbsMcGrf<NOISE>>((PhaseC*)ph_, md, map, n_steps, g / n_samples, (size_t)g, x0, xfinal, rows, trajX, trajU, stash, WbsMcGrf<NOISE>{mc, gr});               \
-    }
-WBS_MC_GRF_KERNEL(k_sim_quad_mc_grf, 1)
-WBS_MC_GRF_KERNEL(k_sim_quad_mc0_grf, 0)
-#undef WBS_MC_GRF_KERNEL
+// The launcher of each family (SimFamily): it picks among its kernels by L.pick and launches one.  None of them looks at the runtime's error state: a
+// launch that fails is reported by the caller's hipGetLastError (reading the error here would reset it and hide the failure from that check).
+void wbs_base_launch(const WbsLaunch& L);       // below
+void wbs_sub_launch(const WbsLaunch& L);        // hsddp_sub.hip
+void wbs_uni_launch(const WbsLaunch& L);        // hsddp_uni.hip
+void wbs_ter_launch(const WbsLaunch& L);        // hsddp_ter.hip
+void wbs_plant_launch(const WbsLaunch& L);      // hsddp_plant.hip
+void wbs_plant_impact_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, int pi, int total, const int* frozen, int stride, double* state, double* x0,
+                             const WbsPlantArgs* pl);
+
+#if !defined(HS_SIM_WALK_ONLY)      // (HS_SIM_WALK_ONLY: hsddp_sub.hip and the like take the walk and the macro and instantiate kernels of their own)
+// The plain walk; the disturbed walk (hsddp_mc_run: mc points at the run's switches in device memory; k_sim_quad_mc draws noise, k_sim_quad_mc0 is the
+// walk of a run without any, see WbsMc); and the twins of the three with contact-force records (hsddp_grf_set: gr points at the thresholds and the
+// destinations in device memory).
+WBS_KERNEL(k_sim_quad, WbsPlain, SIM_PARK, , )
+WBS_KERNEL(k_sim_quad_mc, WbsMc<1>, SIM_PARK_MC, WBS_P(const WbsMcArgs* mc), mc)
+WBS_KERNEL(k_sim_quad_mc0, WbsMc<0>, SIM_PARK_MC, WBS_P(const WbsMcArgs* mc), mc)
+WBS_KERNEL(k_sim_quad_grf, WbsGrf, SIM_PARK + SIM_GRF_PARK, WBS_P(const WbsGrfArgs* gr), gr)
+WBS_KERNEL(k_sim_quad_mc_grf, WbsMcGrf<1>, SIM_PARK_MC + SIM_GRF_PARK, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr), mc, gr)
+WBS_KERNEL(k_sim_quad_mc0_grf, WbsMcGrf<0>, SIM_PARK_MC + SIM_GRF_PARK, WBS_P(const WbsMcArgs* mc, const WbsGrfArgs* gr), mc, gr)
 // The sub-stepped walks (hsddp_substep_set with S > 1) are six more instantiations with SUB 1 in the policy: hsddp_sub.hip, a translation unit of its own.
-// The walks with unilateral ground contact (hsddp_contact_set) are three more with UNI 1: hsddp_uni.hip, likewise.
+// The walks with unilateral ground contact (hsddp_contact_set) are three more with UNI 1: hsddp_uni.hip, likewise; so are hsddp_ter.hip and hsddp_plant.hip.
+void wbs_base_launch(const WbsLaunch& L) {
+    const bool noise = L.pick.variant == SIM_VAR_MC;
+    if (!L.pick.records) {
+        if (L.pick.variant == SIM_VAR_PLAIN) wbs_launch(L, k_sim_quad);
+        else wbs_launch(L, noise ? k_sim_quad_mc : k_sim_quad_mc0, L.mc);
+    } else {
+        if (L.pick.variant == SIM_VAR_PLAIN) wbs_launch(L, k_sim_quad_grf, L.gr);
+        else wbs_launch(L, noise ? k_sim_quad_mc_grf : k_sim_quad_mc0_grf, L.mc, L.gr);
+    }
+}
+#endif
 #endif
 
 }  // namespace hs

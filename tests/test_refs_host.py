@@ -23,8 +23,34 @@ def test_refs_header_symbols_match_binding_list():
     assert "hsddp_set_references" not in open(os.path.join(ROOT, "include", "hsddp.h")).read()
 
 
+LLVM_BIN = "/opt/rocm/lib/llvm/bin"
+
+
+def gfx950_kernels(so, tmp):
+    """Mangled names of the kernels in the gfx950 code objects of a library: its .hip_fatbin section is one offload bundle per translation unit (magic, entry
+    count, then offset / size / triple of each entry); a kernel is a symbol with a kernel descriptor NAME.kd in an entry for gfx950."""
+    fat = os.path.join(str(tmp), os.path.basename(str(so)) + ".fatbin")
+    subprocess.check_call([os.path.join(LLVM_BIN, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, str(so), os.devnull])
+    data, magic, names, n = open(fat, "rb").read(), b"__CLANG_OFFLOAD_BUNDLE__", set(), 0
+    assert data.startswith(magic)
+    for m in re.finditer(magic, data):
+        at, pos = m.start(), m.start() + len(magic) + 8
+        for _ in range(int.from_bytes(data[pos - 8:pos], "little")):
+            off, size, tl = (int.from_bytes(data[pos + 8 * i:pos + 8 * i + 8], "little") for i in range(3))
+            triple = data[pos + 24:pos + 24 + tl].decode(); pos += 24 + tl
+            if not triple.endswith("gfx950"):
+                continue
+            co = os.path.join(str(tmp), "%s.%d.co" % (os.path.basename(str(so)), n)); n += 1
+            open(co, "wb").write(data[at + off:at + off + size])
+            syms = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "-sW", co], capture_output=True, text=True, check=True).stdout
+            names |= {line.split()[-1][:-3] for line in syms.splitlines() if line.endswith(".kd") and " OBJECT " in line}
+    return names
+
+
 def test_fresh_hip_build_exports_the_refs_symbols(tmp_path):
-    """A fresh hipcc --offload-arch=gfx950 build of libhsddp_hip.so (the product Makefile's recipe, into a scratch directory)."""
+    """A fresh one-command hipcc --offload-arch=gfx950 build of libhsddp_hip.so from hsddp_hip.hip alone (the product Makefile's flags, into a scratch
+    directory): it exports the symbols, and its device code defines every kernel the product build of the Makefile defines - the files that build
+    compiles on their own are included where the device pass sees them."""
     so = tmp_path / "libhsddp_hip.so"
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "include"),
                            "-Wno-unused-value", "-DROLL_WPE=2", os.path.join(CSRC, "hsddp_hip.hip"), "-o", str(so)], timeout=1800)
@@ -32,6 +58,10 @@ def test_fresh_hip_build_exports_the_refs_symbols(tmp_path):
     for s in pkg._abi.REFS_EXPORTS + pkg._abi.EXPORTS:
         assert hasattr(lib, s), s
     pkg._abi.bind_refs(lib)
+    subprocess.check_call(["make", "-C", CSRC], stdout=subprocess.DEVNULL)      # the product library (what build() makes; nothing to do if it is current)
+    product, fresh = gfx950_kernels(os.path.join(ROOT, "cafe-mpc_amd", "libhsddp_hip.so"), tmp_path), gfx950_kernels(so, tmp_path)
+    assert len([k for k in product if "k_sim_quad" in k]) == 27 and any("k_episode_impact_plant" in k for k in product) and any("k_rollout_quad_term" in k for k in product)
+    assert sorted(product - fresh) == [], "kernels of the product build without device code in the one-command build"
 
 
 def test_bind_refs_refuses_a_library_without_it(oracle_lib):

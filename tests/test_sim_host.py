@@ -149,6 +149,18 @@ def test_sim_program_contains_a_diverging_sample(sim_emu, solved_trot):
     assert (rows0[:, 4] == -1).all()
 
 
+def test_dispatch_rule_names_every_walk_and_is_clean_under_the_sanitizers(tmp_path):
+    """tests/cpp/sim_pick_table.cpp, a stand-alone program around the rule that picks the walk of a run (cafe-mpc_amd/csrc/sim_pick.hpp): every setting of
+    the switches against a name composed from the suffix rules, exactly the 27 product walks reachable, the inert combinations inert.  Compiled with
+    -fsanitize=address,undefined and run directly; it has to finish clean."""
+    exe = str(tmp_path / "sim_pick_table")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-I" + os.path.join(ROOT, "cafe-mpc_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "sim_pick_table.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    print(r.stdout + r.stderr)
+    assert r.returncode == 0 and "sim_pick_table: clean" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
 def test_multiphase_ddp_header_compiles_with_simulate(tmp_path):
     """The C++ mirror: simulate() and hsddp::Simulation compile; code that does not call them still links against a library without the symbols
     (tests/test_abi.py links the header against the oracle)."""
