@@ -407,6 +407,33 @@ def bind_episode(lib):
     return lib
 
 
+# include/hsddp_latency.h: per-robot policy latency of the episodes (libhsddp_hip.so only)
+LATENCY_EXPORTS = ["hsddp_latency_set", "hsddp_latency_get", "hsddp_latency_get_policy"]
+LATENCY_ROW = 516      # doubles of a policy row: Xbar[k] | Xbar[k+1] | Ubar[k] | K[k]
+
+
+class LatencyRow(C.Structure):
+    """hsddp_latency_row_t"""
+    _fields_ = [("delay", C.c_int), ("n_stale", C.c_int)]
+
+
+LATENCY_ROW_DTYPE = np.dtype([(n, "<i4") for n, _ in LatencyRow._fields_])
+
+
+def bind_latency(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_latency.h (and of hsddp_episode.h, which it builds on).  Raises if the library
+    lacks any."""
+    missing = [s for s in LATENCY_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the latency entry points {missing}")
+    bind_episode(lib)
+    H = C.c_void_p
+    lib.hsddp_latency_set.argtypes = [H, C.c_int, C.c_void_p, C.c_int]
+    lib.hsddp_latency_get.argtypes = [H, C.c_int, C.c_int, C.c_void_p]
+    lib.hsddp_latency_get_policy.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return lib
+
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 

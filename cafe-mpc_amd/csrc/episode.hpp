@@ -9,10 +9,15 @@
 //                wbs_contact_dynamics in mode 1 with the phase's touchdown set and damping 0, the call of wbs_walk's phase boundary - and the state
 //                handed to the solver.  Launched only when the host sees the pending map (once per touchdown, not per step).
 //
-// Both are templates over the lane policy so that tests/_emu/episode_emu.cpp builds them for the host (EpiWaveH: the 64 lanes one after the other;
+//   epi_latency  (include/hsddp_latency.h) one WAVE per (problem, step) of n_exec + D steps, lanes over the 258 sixteen-byte pairs of a policy row: a
+//                step below n_exec composes the row the walk applies there - from the previous tick's stash if the step is stale for the problem,
+//                else from the handle - and a step from n_exec on writes the handle's row into the next stash.  A pure copy: no LDS, no atomics.
+//
+// All three are templates over the lane policy so that tests/_emu/episode_emu.cpp builds them for the host (EpiWaveH: the 64 lanes one after the other;
 // QH: the four lanes of a quad together).  cafe-mpc_amd/episode.py fold_rows is the definition of the commit.
 #pragma once
 #include "wb_sim.hpp"
+#include "latency_plan.hpp"
 
 namespace hs {
 
@@ -127,7 +132,70 @@ template <class Q> HD void epi_impact(PhaseC* ph, const ModelDev& md, int pi, si
     _Pragma("unroll") for (int j = 0; j < 3; j++) { Q::st(state, g * 36 + 24 + j, 3, o3[j]); Q::st(x0, g * 36 + 6 + j, 3, ql[j]); Q::st(x0, g * 36 + 24 + j, 3, o3[j]); }
 }
 
+// ---- policy latency.  The effective rows live step-major - Xe [n_exec][B][2][36], Ue [n_exec][B][12], Ke [n_exec][B][432] - so that descriptor s of the
+// table the walk is sent to (sim_host.hpp: a copy of the step's phase with h = 1 and Xbar, Ubar, K at slice s) makes the walk's own indexing,
+// (b (h+1) + k) 36, (b h + k) 12 and (b h + k) 432 with k = 0, land on problem b's row.  A stash row is the LAT_ROW doubles in one piece.
+// Every part of every row starts at a multiple of 16 bytes (288, 96, 3456 and 4128 bytes a row; the handle's arrays are aligned to 256), so a lane
+// moves sixteen bytes at a time and a wave-instruction covers 1 KiB of one row.
+typedef double EpiPair __attribute__((vector_size(16)));      // (a vector type, not a struct: its copies are values in registers, one dwordx4 each way)
+struct EpiLatArgs {
+    int n_exec, D, B, valid;                   // executed steps; largest delay; problems; 1: `prev` holds the rows the previous tick stashed
+    const int* map;                            // [3][n_exec + D] step -> phase, knot over n_exec + D steps of the CURRENT window (latency_plan.hpp: long_map)
+    const int* delay; int* n_stale;            // [B] delay of the problem in steps; stale steps executed while alive
+    const EpiRow* rows;                        // [B] the episode rows (end_reason: a frozen problem counts nothing)
+    const double* prev; double* next;          // the stashes [B][D][LAT_ROW]: read / written this tick
+    double *Xe, *Ue, *Ke;                      // the effective rows, as above
+};
+
+// 258 pairs of a row from (sx | su | sk) to (dx | du | dk): 36 + 6 + 216.  Pair i of the row is lane i's in round 0 - the only round that meets all
+// three parts: the lane selects its addresses, nothing branches - and pairs 64 .. 255 are K's in rounds 1 to 3; lanes 0 and 1 take the last two.  The
+// four loads of the full rounds are issued before the first store.
+HD void epi_lat_copy(int l, const HS_GLOBAL EpiPair* sx, const HS_GLOBAL EpiPair* su, const HS_GLOBAL EpiPair* sk, HS_GLOBAL EpiPair* dx, HS_GLOBAL EpiPair* du,
+                     HS_GLOBAL EpiPair* dk) {
+    const HS_GLOBAL EpiPair* const s0 = l < 36 ? sx + l : l < 42 ? su + (l - 36) : sk + (l - 42);
+    HS_GLOBAL EpiPair* const d0 = l < 36 ? dx + l : l < 42 ? du + (l - 36) : dk + (l - 42);
+    const EpiPair v0 = *s0, v1 = sk[l + 22], v2 = sk[l + 86], v3 = sk[l + 150];
+    *d0 = v0; dk[l + 22] = v1; dk[l + 86] = v2; dk[l + 150] = v3;
+    if (l < 2) dk[l + 214] = sk[l + 214];
+}
+
+template <class W> HD void epi_latency(PhaseC* ph, const EpiLatArgs& a, int b, int s) {
+    const int L = a.n_exec + a.D;
+    const size_t g = (size_t)b;
+    const int d = wbs_uniform(HS_AS_CONST(int, a.delay)[b]);
+    const bool stale = s < a.n_exec && a.valid != 0 && s < d;      // the same in every lane: a scalar branch
+    HS_GLOBAL EpiPair *dx, *du, *dk;
+    if (s < a.n_exec) {
+        const size_t o = (size_t)s * a.B + g;
+        dx = (HS_GLOBAL EpiPair*)(a.Xe + o * 72); du = (HS_GLOBAL EpiPair*)(a.Ue + o * 12); dk = (HS_GLOBAL EpiPair*)(a.Ke + o * 432);
+    } else {
+        double* const row = a.next + (g * a.D + (size_t)(s - a.n_exec)) * LAT_ROW;
+        dx = (HS_GLOBAL EpiPair*)(row + LAT_OX); du = (HS_GLOBAL EpiPair*)(row + LAT_OU); dk = (HS_GLOBAL EpiPair*)(row + LAT_OK);
+    }
+    const HS_GLOBAL EpiPair *sx, *su, *sk;
+    if (stale) {
+        const double* const row = a.prev + (g * a.D + (size_t)s) * LAT_ROW;
+        sx = (const HS_GLOBAL EpiPair*)(row + LAT_OX); su = (const HS_GLOBAL EpiPair*)(row + LAT_OU); sk = (const HS_GLOBAL EpiPair*)(row + LAT_OK);
+    } else {
+        PhaseC& P = ph[wbs_uniform(HS_AS_CONST(int, a.map)[s])];
+        const int k = wbs_uniform(HS_AS_CONST(int, a.map)[L + s]), h = P.h;
+        sx = (const HS_GLOBAL EpiPair*)(P.Xbar + (g * (h + 1) + k) * 36); su = (const HS_GLOBAL EpiPair*)(P.Ubar + (g * h + k) * 12);
+        sk = (const HS_GLOBAL EpiPair*)(P.K + (g * h + k) * 432);
+    }
+    W::each([&](int l) { epi_lat_copy(l, sx, su, sk, dx, du, dk); });
+    if (s == 0) W::each([&](int l) {      // the problem's counter: the stale steps of this tick, if it is alive at its start
+        if (l == 0 && a.valid != 0 && a.rows[b].end_reason == 0) a.n_stale[b] += d < a.n_exec ? d : a.n_exec;
+    });
+}
+
 #ifndef HS_HOST_EMU
+// k_episode_latency and its launcher: hsddp_lat.hip, a translation unit of its own like the walks beyond the first six, so that the code object of
+// hsddp_hip.hip and the list `make resources` prints stay what they were.  grid = min(B (n_exec + D), LAT_MAX_WAVES) waves: 32 waves for each of the 256
+// CUs; beyond that a launch only queues workgroups.
+constexpr int LAT_MAX_WAVES = 8192;
+void epi_latency_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const EpiLatArgs& a);
+#endif
+#if !defined(HS_HOST_EMU) && !defined(HS_EPISODE_BODIES_ONLY)      // (HS_EPISODE_BODIES_ONLY: hsddp_lat.hip takes the programs above and none of the kernels below)
 // grid = B waves
 __global__ void __launch_bounds__(64) k_episode_commit(const PhaseDev* ph_, EpiCommitArgs a) { epi_commit<EpiWaveD>((PhaseC*)ph_, a, (int)blockIdx.x); }
 // grid = ceil(B / 16) waves of sixteen quads, compiled for the register budget of the walk (the contact solve is the same code)

@@ -26,6 +26,7 @@
 #include "hsddp_plant.h"
 #include "hsddp_mc.h"
 #include "hsddp_episode.h"
+#include "hsddp_latency.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -198,6 +199,10 @@ __global__ void __launch_bounds__(64) ROLL_HKD_ATTR k_rollout_hkd(ROLL_ARGS) { _
 #endif
 #ifndef HS_PLANT_SEPARATE
 #include "hsddp_plant.hip"
+#endif
+// k_episode_latency (hsddp_latency.h) and its launcher, likewise (-DHS_LAT_SEPARATE here); the prototype is in episode.hpp either way.
+#ifndef HS_LAT_SEPARATE
+#include "hsddp_lat.hip"
 #endif
 
 // Batched line search, decision step (MultiPhaseDDP::line_search, MultiPhaseDDP.cpp:108-131, for the candidates of one probe launch): per

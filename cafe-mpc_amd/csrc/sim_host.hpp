@@ -1,5 +1,5 @@
 // Host side of the closed-loop policy simulation and of the MPC episodes: the C entry points of include/hsddp_sim.h, hsddp_mc.h, hsddp_grf.h,
-// hsddp_substep.h, hsddp_contact.h, hsddp_terrain.h, hsddp_plant.h and hsddp_episode.h.  Part of hsddp_hip.hip's translation unit, host pass only: that
+// hsddp_substep.h, hsddp_contact.h, hsddp_terrain.h, hsddp_plant.h, hsddp_episode.h and hsddp_latency.h.  Part of hsddp_hip.hip's translation unit, host pass only: that
 // file includes it inside its host-only region, behind hsddp_handle, HIPCK, Timed and drain_events, which this code uses.  The kernels are those of
 // wb_sim.hpp, hsddp_sub.hip, hsddp_uni.hip, hsddp_ter.hip, hsddp_plant.hip and episode.hpp; which walk a run launches is sim_pick's business (sim_pick.hpp).
 #pragma once
@@ -51,6 +51,9 @@ struct hsddp_sim {
     bool plant_on = false; int n_plants = 0;
     WbsPlantArgs* d_plant = nullptr; double* d_plant_P = nullptr; int* d_plant_of = nullptr; size_t plant_cap = 0;
     std::vector<double> plant_rows;
+    // policy latency of an episode (hsddp_latency.h): the descriptor table and the step map the NEXT launch walks instead of h->d_ph and d_map, set
+    // by hsddp_episode_advance around its walk and null otherwise
+    const PhaseDev* walk_ph = nullptr; const int* walk_map = nullptr;
 };
 static void sim_free(hsddp_sim* s) {
     if (!s) return;
@@ -162,7 +165,7 @@ static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, b
     HIPCK(hipEventRecord(s->ev0, h->stream));
     WbsLaunch L;
     L.stream = h->stream; L.grid = (unsigned)((total + 15) / 16);
-    L.ph = h->d_ph; L.md = &h->md; L.map = s->d_map; L.n_steps = s->n_steps; L.n_samples = s->R; L.total = (int)total;
+    L.ph = s->walk_ph ? s->walk_ph : h->d_ph; L.md = &h->md; L.map = s->walk_map ? s->walk_map : s->d_map; L.n_steps = s->n_steps; L.n_samples = s->R; L.total = (int)total;
     L.x0 = src_device ? x0 : s->d_x0; L.xfinal = s->d_final; L.rows = s->d_rows; L.trajX = s->d_X; L.trajU = s->d_U;
     L.pick = sim_pick(SimSwitches{s->plant_on, s->uni_on, s->ter_on, s->substeps, s->grf_on, mc, noise});
     L.mc = s->d_mc; L.gr = L.pick.records ? s->d_grf : s->d_uni_grf; L.sb = s->d_sub; L.un = s->d_uni; L.te = s->d_ter; L.pl = s->d_plant;
@@ -433,17 +436,35 @@ struct hsddp_episode {
     std::vector<EpiRow> row0;                               // [B] rows of a reset (source of the upload)
     double* d_state = nullptr; EpiRow* d_rows = nullptr;    // [B][36] ; [B]
     double *d_X = nullptr, *d_U = nullptr, *d_Y = nullptr;  // the log (keep): [B][max_ticks n_exec + 1][36], [B][max_ticks n_exec][12] twice
+    // policy latency (hsddp_latency.h): everything below is allocated by hsddp_latency_set.  lat_on: what later ticks do; lat_valid: stash lat_cur holds
+    // the rows the previous tick left; lat_ran: a tick has composed the effective rows; lat_dirty: the plan on the device is not that of (window, lat_D)
+    bool lat_on = false, lat_valid = false, lat_ran = false, lat_dirty = false;
+    int lat_D = 0, lat_cap = 0, lat_cur = 0;               // largest delay; rows a stash has room for; the stash the next tick READS
+    std::vector<int> lat_delay, lat_long, lat_walk, lat_long_new, lat_walk_new;      // [B]; the plan of latency_plan.hpp on the device / scratch
+    std::vector<LatPhase> lat_phases; std::vector<PhaseDev> lat_table;            // scratch of the plan; [n_exec] source of the table's upload
+    int *d_lat_delay = nullptr, *d_lat_stale = nullptr, *d_lat_long = nullptr, *d_lat_walk = nullptr;      // [B] twice; [3][2 n_exec]; [3][n_exec]
+    PhaseDev* d_lat_table = nullptr;                        // [n_exec] the descriptors the walk is sent to
+    double *d_lat_X = nullptr, *d_lat_U = nullptr, *d_lat_K = nullptr, *d_lat_stash[2] = {nullptr, nullptr};      // episode.hpp: EpiLatArgs
 };
 static void episode_free(hsddp_episode* e) {
     if (!e) return;
     hipSetDevice(e->h->device);
     if (e->h->stream) hipStreamSynchronize(e->h->stream);
     if (e->sim) sim_free(e->sim);
-    void* p[] = {e->d_state, e->d_rows, e->d_X, e->d_U, e->d_Y};
+    void* p[] = {e->d_state, e->d_rows, e->d_X, e->d_U, e->d_Y, e->d_lat_delay, e->d_lat_stale, e->d_lat_long, e->d_lat_walk, e->d_lat_table, e->d_lat_X, e->d_lat_U, e->d_lat_K,
+                 e->d_lat_stash[0], e->d_lat_stash[1]};
     for (void* q : p) if (q) hipFree(q);
     delete e;
 }
 static bool episode_range_ok(const hsddp_episode* e, int b0, int nb) { return e && nb > 0 && b0 >= 0 && b0 <= e->h->batch - nb; }
+// the plan of a tick with latency (latency_plan.hpp) for the handle's current window, into the scratch vectors; false: fewer than n_exec + lat_D leading whole-body knots
+static bool episode_lat_plan(hsddp_episode* e) {
+    const hsddp_handle* h = e->h;
+    e->lat_phases.resize((size_t)h->nph);
+    for (int i = 0; i < h->nph; i++) e->lat_phases[i] = LatPhase{h->ph[i].model == HSDDP_MODEL_WB ? 1 : 0, h->ph[i].h, h->ph[i].has_impact};
+    int pend = -1;
+    return lat_plan(e->lat_phases.data(), h->nph, e->n_exec, e->lat_D, e->lat_long_new.data(), e->lat_walk_new.data(), &pend);
+}
 // seed of tick t (hsddp_episode.h): the seed itself, then the raw outputs of SplitMix64(seed)
 static unsigned long long episode_tick_seed(unsigned long long seed, int t) {
     if (t == 0) return seed;
@@ -500,8 +521,9 @@ int hsddp_episode_reset(hsddp_episode_t* e, const double* x0, int src_device) {
     }
     if (e->sim->d_uni_F) HIPCK(hipMemsetAsync(e->sim->d_uni_F, 0, B * 4 * 8, h->stream));      // (hsddp_contact.h) every foot attached again
     if (e->sim->d_ter_E) HIPCK(hipMemsetAsync(e->sim->d_ter_E, 0, B * 4 * 8, h->stream));      // (hsddp_terrain.h) no swing foot held
+    if (e->d_lat_stale) HIPCK(hipMemsetAsync(e->d_lat_stale, 0, B * sizeof(int), h->stream));      // (hsddp_latency.h) nothing stale yet; the delays stay
     HIPCK(hipStreamSynchronize(h->stream));
-    e->tick = 0; e->n_impacts = 0; e->started = true;
+    e->tick = 0; e->n_impacts = 0; e->started = true; e->lat_valid = false;
     return HSDDP_OK;
 }
 
@@ -513,6 +535,7 @@ int hsddp_episode_advance(hsddp_episode_t* e, const hsddp_mc_dist_t* dist, const
     const bool moved = s->gen != h->window_gen;
     int pend = e->pending;
     if (moved && !sim_step_map(h, e->n_exec, e->map_new.data(), &pend)) return HSDDP_EINVAL;      // the window no longer leads with n_exec whole-body knots
+    if (e->lat_on && !episode_lat_plan(e)) return HSDDP_EINVAL;      // (hsddp_latency.h) ... or not with the lat_D more the stash reads
     HIPCK(hipSetDevice(h->device));
     // rebind: the step map of the new window into the simulation object's buffer (the walk below synchronises the stream).  It stays in place if the
     // walk then fails with a device error - the map is that of the handle's current window either way; "nothing changed" is promised for HSDDP_EINVAL
@@ -521,12 +544,40 @@ int hsddp_episode_advance(hsddp_episode_t* e, const hsddp_mc_dist_t* dist, const
         HIPCK(hipMemcpyAsync(s->d_map, e->map.data(), e->map.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
         s->gen = h->window_gen;
     }
+    // policy latency (hsddp_latency.h): the plan of the bound window on the device, then ONE launch composes the rows this tick applies and stashes the
+    // rows the next one may need - nothing between here and the end of the tick changes the handle's policy.  The walk is sent to the per-step table.
+    if (e->lat_on) {
+        const size_t B = (size_t)h->batch;
+        const int n = e->n_exec, L = n + e->lat_D;
+        if (moved || e->lat_dirty) {
+            e->lat_long.swap(e->lat_long_new); e->lat_walk.swap(e->lat_walk_new);
+            for (int q = 0; q < n; q++) {      // descriptor q: the step's phase with ONE knot, its policy at slice q of the effective rows
+                PhaseDev c = h->ph[e->lat_long[q]];
+                c.h = 1; c.Xbar = e->d_lat_X + (size_t)q * B * 72; c.Ubar = e->d_lat_U + (size_t)q * B * 12; c.K = e->d_lat_K + (size_t)q * B * 432;
+                e->lat_table[q] = c;
+            }
+            HIPCK(hipMemcpyAsync(e->d_lat_long, e->lat_long.data(), 3 * (size_t)L * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIPCK(hipMemcpyAsync(e->d_lat_walk, e->lat_walk.data(), 3 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIPCK(hipMemcpyAsync(e->d_lat_table, e->lat_table.data(), (size_t)n * sizeof(PhaseDev), hipMemcpyHostToDevice, h->stream));
+            e->lat_dirty = false;
+        }
+        EpiLatArgs la;
+        la.n_exec = n; la.D = e->lat_D; la.B = h->batch; la.valid = e->lat_valid ? 1 : 0;
+        la.map = e->d_lat_long; la.delay = e->d_lat_delay; la.n_stale = e->d_lat_stale; la.rows = e->d_rows;
+        la.prev = e->d_lat_stash[e->lat_cur]; la.next = e->d_lat_stash[e->lat_cur ^ 1];
+        la.Xe = e->d_lat_X; la.Ue = e->d_lat_U; la.Ke = e->d_lat_K;
+        { Timed t(h, "k_episode_latency"); epi_latency_launch(h->stream, (unsigned)std::min<size_t>(B * L, LAT_MAX_WAVES), h->d_ph, la); }
+        HIPCK(hipGetLastError());
+        e->lat_valid = e->lat_D > 0; e->lat_cur ^= 1; e->lat_ran = true;
+        s->walk_ph = e->d_lat_table; s->walk_map = e->d_lat_walk;
+    } else e->lat_valid = false;      // a tick without latency leaves no stash
     int rc;
     if (!dist) rc = hsddp_sim_run(s, e->d_state, 1);
     else {
         hsddp_mc_dist_t d = *dist; d.seed = episode_tick_seed(dist->seed, e->tick);
         rc = hsddp_mc_run(s, e->d_state, 1, &d, kick, kick_device);
     }
+    s->walk_ph = nullptr; s->walk_map = nullptr;
     if (rc != HSDDP_OK) return rc;
     EpiCommitArgs a;
     a.n_exec = e->n_exec; a.tick = e->tick; a.max_ticks = e->max_ticks; a.handoff = e->pending < 0 ? 1 : 0;
@@ -566,6 +617,68 @@ int hsddp_episode_get_log(hsddp_episode_t* e, int b0, int nb, double* X, double*
     if (X) HIPCK(hipMemcpy(X, e->d_X + (size_t)b0 * sx, (size_t)nb * sx * 8, hipMemcpyDeviceToHost));
     if (U) HIPCK(hipMemcpy(U, e->d_U + (size_t)b0 * su, (size_t)nb * su * 8, hipMemcpyDeviceToHost));
     if (Y) HIPCK(hipMemcpy(Y, e->d_Y + (size_t)b0 * su, (size_t)nb * su * 8, hipMemcpyDeviceToHost));
+    return HSDDP_OK;
+}
+
+int hsddp_latency_set(hsddp_episode_t* e, int on, const int* delay_of, int delay) {
+    if (!e) return HSDDP_EINVAL;
+    if (!on) { e->lat_on = false; e->lat_valid = false; return HSDDP_OK; }      // later ticks launch what they launched without it; the buffers and the delays are kept
+    hsddp_handle* h = e->h;
+    const size_t B = (size_t)h->batch, n = (size_t)e->n_exec;
+    int D = 0;
+    for (size_t b = 0; b < B; b++) {
+        const int d = delay_of ? delay_of[b] : delay;
+        if (d < 0 || d > e->n_exec) return HSDDP_EINVAL;
+        D = std::max(D, d);
+    }
+    HIPCK(hipSetDevice(h->device));
+    if (!e->d_lat_delay) SIM_CK(hipMalloc((void**)&e->d_lat_delay, B * sizeof(int)));      // (a failure: see SIM_CK - latency stays as it was)
+    if (!e->d_lat_stale) { SIM_CK(hipMalloc((void**)&e->d_lat_stale, B * sizeof(int))); HIPCK(hipMemsetAsync(e->d_lat_stale, 0, B * sizeof(int), h->stream)); }
+    if (!e->d_lat_long) SIM_CK(hipMalloc((void**)&e->d_lat_long, 3 * 2 * n * sizeof(int)));      // (room for the largest D there is, n_exec)
+    if (!e->d_lat_walk) SIM_CK(hipMalloc((void**)&e->d_lat_walk, 3 * n * sizeof(int)));
+    if (!e->d_lat_table) SIM_CK(hipMalloc((void**)&e->d_lat_table, n * sizeof(PhaseDev)));
+    if (!e->d_lat_X) SIM_CK(hipMalloc((void**)&e->d_lat_X, n * B * 72 * 8));
+    if (!e->d_lat_U) SIM_CK(hipMalloc((void**)&e->d_lat_U, n * B * 12 * 8));
+    if (!e->d_lat_K) SIM_CK(hipMalloc((void**)&e->d_lat_K, n * B * 432 * 8));
+    if (D > e->lat_cap) {      // the new pair first, so that a failure leaves the old one in place
+        double* nb[2] = {nullptr, nullptr};
+        SIM_CK(hipMalloc((void**)&nb[0], B * (size_t)D * LAT_ROW * 8));
+        SIM_CK_FREE(hipMalloc((void**)&nb[1], B * (size_t)D * LAT_ROW * 8), hipFree(nb[0]));
+        HIPCK(hipStreamSynchronize(h->stream));
+        for (int i = 0; i < 2; i++) { if (e->d_lat_stash[i]) hipFree(e->d_lat_stash[i]); e->d_lat_stash[i] = nb[i]; }
+        e->lat_cap = D;
+    }
+    e->lat_delay.resize(B);
+    for (size_t b = 0; b < B; b++) e->lat_delay[b] = delay_of ? delay_of[b] : delay;
+    e->lat_long.assign(3 * 2 * n, 0); e->lat_long_new.assign(3 * 2 * n, 0); e->lat_walk.assign(3 * n, 0); e->lat_walk_new.assign(3 * n, 0); e->lat_table.resize(n);
+    HIPCK(hipMemcpyAsync(e->d_lat_delay, e->lat_delay.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    e->lat_on = true; e->lat_D = D; e->lat_valid = false; e->lat_dirty = true;      // (the stash rows are laid out for the old D: the next tick runs fresh)
+    return HSDDP_OK;
+}
+
+int hsddp_latency_get(hsddp_episode_t* e, int b0, int nb, hsddp_latency_row_t* rows) {
+    if (!episode_range_ok(e, b0, nb) || !rows || !e->d_lat_stale) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(e->h->device));
+    std::vector<int> st((size_t)nb);
+    HIPCK(hipMemcpy(st.data(), e->d_lat_stale + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost));
+    for (int i = 0; i < nb; i++) { rows[i].delay = e->lat_delay[(size_t)b0 + i]; rows[i].n_stale = st[i]; }
+    return HSDDP_OK;
+}
+
+int hsddp_latency_get_policy(hsddp_episode_t* e, int b0, int nb, double* Xe, double* Ue, double* Ke) {
+    if (!episode_range_ok(e, b0, nb) || !e->lat_ran) return HSDDP_EINVAL;
+    HIPCK(hipSetDevice(e->h->device));
+    const size_t B = (size_t)e->h->batch, n = (size_t)e->n_exec;
+    std::vector<double> tmp((size_t)nb * 432);
+    const double* src[3] = {e->d_lat_X, e->d_lat_U, e->d_lat_K}; double* dst[3] = {Xe, Ue, Ke}; const size_t w[3] = {72, 12, 432};
+    for (int a = 0; a < 3; a++) {      // the device keeps the rows step-major (episode.hpp), the caller gets them problem-major
+        if (!dst[a]) continue;
+        for (size_t q = 0; q < n; q++) {
+            HIPCK(hipMemcpy(tmp.data(), src[a] + (q * B + (size_t)b0) * w[a], (size_t)nb * w[a] * 8, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < (size_t)nb; i++) memcpy(dst[a] + (i * n + q) * w[a], tmp.data() + i * w[a], w[a] * 8);
+        }
+    }
     return HSDDP_OK;
 }
 

@@ -7,14 +7,15 @@ whole-body dynamics, with the simulated state handed to the next solve on the de
     ep.set_contact(0.0, 0.0)                                        # optional: unilateral ground contact (include/hsddp_contact.h)
     ep.set_terrain(sim.Terrain(H=heights, cx=0.05, cy=0.05, early=True, w_td=0.05))      # optional, with it: terrain and early touchdown (include/hsddp_terrain.h)
     ep.set_plant(sim.Plant(rows, plant_of=idx))                     # optional: a plant row per robot, idx int [B] (include/hsddp_plant.h)
+    ep.set_latency([0, 1, 2, ...])                                  # optional: policy latency in control steps per robot, int or int [B] (include/hsddp_latency.h)
     ep.reset(x0)                                                    # [B, 36]; also the solver's initial condition
     solver.solve(opt)
     out = run_mhpc(solver, pd, phases, opt_rt, 50, dist=Disturbance(seed=7, sigma_u=0.2, fall_height=0.12), episode=ep)
     rows, x_now = ep.rows(); X, U, Y = ep.log(); tick, n_alive, n_impacts = ep.status()
 
 Nothing here computes anything on the product path: the walk is the kernel of sim.Simulation, the commit and the pending reset map are
-k_episode_commit / k_episode_impact (csrc/episode.hpp).  tick_seed and fold_rows state the seed schedule and the commit in numpy: the
-definitions the library mirrors."""
+k_episode_commit / k_episode_impact (csrc/episode.hpp), and with latency k_episode_latency composes the policy rows the walk applies.  tick_seed,
+fold_rows and compose_policy state the seed schedule, the commit and the composition in numpy: the definitions the library mirrors."""
 import ctypes as C
 import dataclasses
 
@@ -95,6 +96,54 @@ def step_refs(solver, smap):
     xr = np.stack([refs[int(p)]["xr"][:, k] for p, k in zip(smap[0], smap[1])], axis=1)
     ur = np.stack([refs[int(p)]["ur"][:, k] for p, k in zip(smap[0], smap[1])], axis=1)
     return xr, ur
+
+
+def latency_step_map(phases, n_steps):
+    """The step map (3 x n_steps: phase, knot, reset map behind the step) over the leading whole-body control knots of a window given as the
+    builder's phase dicts: what hsddp_sim_create lays out, and with n_steps = n_exec + D the long map of a tick with latency."""
+    out = []
+    for i, p in enumerate(phases):
+        d = p["desc"]
+        if d.model != 0:
+            break
+        td = any(d.contact[l] == 0 and d.next_contact[l] == 1 for l in range(4))
+        for k in range(d.horizon):
+            out.append([i, k, 1 if (td and k == d.horizon - 1) else 0])
+    if len(out) < n_steps:
+        raise ValueError(f"the window leads with {len(out)} whole-body knots, not {n_steps}")
+    out = out[:n_steps]
+    out[-1][2] = 0
+    return np.ascontiguousarray(np.array(out, dtype=np.int32).T)
+
+
+def policy_rows(solver, smap, fields=None):
+    """[B, n, 516]: the policy rows Xbar[k] | Xbar[k+1] | Ubar[k] | K[k] (K column-major 12 x 36, the handle's order) of the (phase, knot) pairs of a
+    step map.  fields: {phase: (XBAR, UBAR, K)} as Solver.field returns them - a snapshot taken earlier; None reads the solver now."""
+    ph = sorted(set(int(p) for p in smap[0]))
+    if fields is None:
+        fields = {p: (solver.field(p, "XBAR"), solver.field(p, "UBAR"), solver.field(p, "K")) for p in ph}
+    rows = []
+    for p, k in zip(smap[0], smap[1]):
+        X, U, K = fields[int(p)]
+        rows.append(np.concatenate([X[:, k], X[:, k + 1], U[:, k], K[:, k].transpose(0, 2, 1).reshape(K.shape[0], 432)], axis=1))
+    return np.ascontiguousarray(np.stack(rows, axis=1))
+
+
+def compose_policy(prev_rows, cur_rows, delay_of, valid):
+    """The effective policy of a tick with latency (k_episode_latency), [B, n_exec, 516].  cur_rows [B, n_exec, 516]: the rows of the handle's
+    current policy at steps 0 .. n_exec - 1; prev_rows [B, D, 516] or None: the rows the PREVIOUS tick's policy held at its steps n_exec ..
+    n_exec + D - 1, the same physical time; delay_of int [B]; valid: the previous advance left those rows (it ran with latency on, after the last
+    reset).  Step s of robot b takes prev_rows[b, s] if valid and s < delay_of[b], else cur_rows[b, s]."""
+    out = np.array(cur_rows, dtype=np.float64, copy=True)
+    if valid:
+        for b, d in enumerate(np.asarray(delay_of).reshape(-1)):
+            out[b, :d] = prev_rows[b, :d]
+    return out
+
+
+def split_policy(rows):
+    """[B, n, 516] rows -> (Xe [B, n, 2, 36], Ue [B, n, 12], Ke [B, n, 432]), the layout of hsddp_latency_get_policy."""
+    return rows[..., :72].reshape(rows.shape[:-1] + (2, 36)), rows[..., 72:84], rows[..., 84:]
 
 
 class Episode:
@@ -202,6 +251,46 @@ class Episode:
         if rc != 0:
             raise RuntimeError(f"hsddp_plant_set failed rc={rc}")
 
+    def set_latency(self, delay):
+        """Per-robot policy latency (include/hsddp_latency.h) for every later tick: delay, an int for all or int [batch], in control steps within
+        [0, n_exec].  The first steps of a tick then apply the policy of the previous tick.  The next tick runs fresh."""
+        lib = _abi.bind_latency(self.lib)
+        if np.ndim(delay) == 0:
+            rc = lib.hsddp_latency_set(self.e, 1, None, int(delay))
+        else:
+            d = np.ascontiguousarray(delay, dtype=np.int32).reshape(-1)
+            if d.shape != (self.solver.batch,):
+                raise ValueError(f"delay has {d.size} entries, not {self.solver.batch}")
+            rc = lib.hsddp_latency_set(self.e, 1, d.ctypes.data, 0)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_latency_set failed rc={rc}")
+
+    def clear_latency(self):
+        """Latency off: later ticks apply the handle's policy from their first step, with the launches of an episode that never had it on."""
+        rc = _abi.bind_latency(self.lib).hsddp_latency_set(self.e, 0, None, 0)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_latency_set failed rc={rc}")
+
+    def latency_rows(self, b0=0, nb=None):
+        """Structured array [nb] of hsddp_latency_row_t: delay, and the stale steps executed while alive since the reset."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0),), dtype=_abi.LATENCY_ROW_DTYPE)
+        rc = _abi.bind_latency(self.lib).hsddp_latency_get(self.e, b0, nb, rows.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_latency_get failed rc={rc}")
+        return rows
+
+    def applied_policy(self, b0=0, nb=None):
+        """(Xe [nb, n_exec, 2, 36], Ue [nb, n_exec, 12], Ke [nb, n_exec, 432]): the effective policy the last tick walked, which has to be one with
+        latency on.  Xe[:, s, 1] is the knot behind step s in its phase; Ke is column-major 12 x 36."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        n = self.n_exec
+        Xe = np.zeros((max(nb, 0), n, 2, 36)); Ue = np.zeros((max(nb, 0), n, 12)); Ke = np.zeros((max(nb, 0), n, 432))
+        rc = _abi.bind_latency(self.lib).hsddp_latency_get_policy(self.e, b0, nb, Xe.ctypes.data, Ue.ctypes.data, Ke.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_latency_get_policy failed rc={rc}")
+        return Xe, Ue, Ke
+
     def terrain_rows(self, b0=0, nb=None):
         """Structured array [nb] of hsddp_terrain_row_t of the last tick, which has to be one with the contact rule and the terrain on."""
         nb = self.solver.batch - b0 if nb is None else nb
@@ -262,16 +351,19 @@ class Episode:
         return t.value, a.value, i.value
 
 
-def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False):
+def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None):
     """The receding-horizon loop of MHPCLocomotion::update with the SIMULATED state fed back, for the whole batch.  solver: solved for the window
     `phases` of pd (builder.MHPCProblemData).  Per tick: episode.advance, pd.update(), builder.shift_solver_in_place, hook(tick, phases) - the
     place for solver.set_references - and solver.solve(opt_rt).  kicks: {tick: (kick_step, [B, 36])}.  episode: an Episode already reset; None
-    creates one (n_exec = dt_mpc / dt_wb, max_ticks = n_ticks) and resets it to the solver's Xbar[0].  Returns a dict: episode, phases (the last
+    creates one (n_exec = dt_mpc / dt_wb, max_ticks = n_ticks) and resets it to the solver's Xbar[0].  delay: None leaves the episode as it is; an int
+    or int [B] is Episode.set_latency before the first tick (include/hsddp_latency.h: the loop moves the window by n_exec knots a tick, as that needs).  Returns a dict: episode, phases (the last
     window), n_iters / n_ls_iters / n_reg_iters / cost [n_ticks, B], alive [n_ticks]."""
     from . import builder
     if episode is None:
         episode = Episode(solver, int(round(float(pd.cfg["dt_mpc"]) / pd.dt_wb)), n_ticks, keep_log)
         episode.reset(np.ascontiguousarray(solver.field(0, "XBAR")[:, 0]))
+    if delay is not None:
+        episode.set_latency(delay)
     out = dict(n_iters=[], n_ls_iters=[], n_reg_iters=[], cost=[], alive=[])
     for t in range(n_ticks):
         d, k = dist, None

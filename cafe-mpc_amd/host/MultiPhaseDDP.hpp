@@ -26,6 +26,7 @@
 #include "hsddp_terrain.h"
 #include "hsddp_plant.h"
 #include "hsddp_episode.h"
+#include "hsddp_latency.h"
 
 namespace hsddp {
 
@@ -148,6 +149,14 @@ public:
     bool set_terrain(bool on, const hsddp_terrain_t* t = nullptr, const double* H = nullptr, const int* map_of = nullptr) { rc_ = e_ ? hsddp_terrain_set(hsddp_episode_sim(e_), on ? 1 : 0, t, H, map_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // a plant row per robot for the whole episode (include/hsddp_plant.h): plant_of [batch] or null
     bool set_plant(bool on, int n_plants = 0, const double* P = nullptr, const int* plant_of = nullptr) { rc_ = e_ ? hsddp_plant_set(hsddp_episode_sim(e_), on ? 1 : 0, n_plants, P, plant_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // per-robot policy latency for every later tick (include/hsddp_latency.h): delay_of [batch] in control steps, or null and one delay for all
+    bool set_latency(bool on, const int* delay_of = nullptr, int delay = 0) { rc_ = e_ ? hsddp_latency_set(e_, on ? 1 : 0, delay_of, delay) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // the delays and the stale steps executed so far
+    std::vector<hsddp_latency_row_t> latency() {
+        std::vector<hsddp_latency_row_t> r((size_t)batch_);
+        rc_ = e_ ? hsddp_latency_get(e_, 0, batch_, r.data()) : HSDDP_EINVAL;
+        return r;
+    }
     std::vector<hsddp_episode_row_t> rows(std::vector<double>* x_now = nullptr) {
         std::vector<hsddp_episode_row_t> r((size_t)batch_);
         if (x_now) x_now->resize((size_t)batch_ * 36);
