@@ -370,6 +370,31 @@ def bind_plant(lib):
     return lib
 
 
+# include/hsddp_friction.h: Coulomb friction in a simulation object (libhsddp_hip.so only).  A list and a binder of their own, as above.
+FRICTION_EXPORTS = ["hsddp_friction_set", "hsddp_friction_get_params", "hsddp_friction_get"]
+# hsddp_friction_row_t
+FRICTION_ROW_DTYPE = np.dtype([("first_slide", "<i4"), ("n_onset", "<i4"), ("n_slide", "<i4"), ("n_restick", "<i4"), ("slide_final", "<i4"), ("pad", "<i4"),
+                               ("max_speed", "<f8"), ("distance", "<f8")])
+
+
+class FrictionParams(C.Structure):
+    """hsddp_friction_t"""
+    _fields_ = [("v_stick", C.c_double), ("n_mu", C.c_int), ("pad", C.c_int)]
+
+
+def bind_friction(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_friction.h (and of hsddp_terrain.h, which it includes).  Raises if the library lacks any."""
+    missing = [s for s in FRICTION_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the friction entry points {missing}")
+    bind_terrain(lib)
+    H = C.c_void_p
+    lib.hsddp_friction_set.argtypes = [H, C.c_int, C.POINTER(FrictionParams), C.c_void_p, C.c_void_p]
+    lib.hsddp_friction_get_params.argtypes = [H, IP, C.POINTER(FrictionParams)]
+    lib.hsddp_friction_get.argtypes = [H, C.c_int, C.c_int, C.c_void_p]
+    return lib
+
+
 # include/hsddp_episode.h: batched closed-loop MPC episodes (libhsddp_hip.so only)
 EPISODE_EXPORTS = ["hsddp_episode_create", "hsddp_episode_destroy", "hsddp_episode_reset", "hsddp_episode_advance", "hsddp_episode_get_rows",
                    "hsddp_episode_get_log", "hsddp_episode_device_state", "hsddp_episode_sim", "hsddp_episode_status"]
@@ -689,7 +714,7 @@ class Solver:
                  "get_references")
         return out
 
-    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None, plant=None):
+    def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None, plant=None, friction=None):
         """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)
         over the first n_steps whole-body control knots (include/hsddp_sim.h): dict with rows (structured array [batch, R] of dev_q, dev_v,
         min_height, max_torque, first_bad), x_final [batch, R, 36] and, with keep_traj, X [batch, R, n_steps + 1, 36] and U [batch, R, n_steps, 12].
@@ -704,7 +729,7 @@ class Solver:
         early_final, max_pen).  plant = sim.Plant(...): a plant row per sample - trunk and link inertias, torque gain, joint friction
         (include/hsddp_plant.h); no new output, the existing ones show the effect."""
         from . import sim
-        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps, contact=contact, terrain=terrain, plant=plant)
+        return sim.simulate(self, x0, n_steps, keep_traj, dist=dist, kick=kick, grf=grf, substeps=substeps, contact=contact, terrain=terrain, plant=plant, friction=friction)
 
     def episode(self, n_exec, max_ticks, keep_log=False):
         """An episode.Episode on this solver (include/hsddp_episode.h): batched closed-loop MPC ticks with the simulated state handed to the next

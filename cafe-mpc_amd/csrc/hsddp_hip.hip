@@ -24,6 +24,7 @@
 #include "hsddp_contact.h"
 #include "hsddp_terrain.h"
 #include "hsddp_plant.h"
+#include "hsddp_friction.h"
 #include "hsddp_mc.h"
 #include "hsddp_episode.h"
 #include "hsddp_latency.h"
@@ -199,6 +200,9 @@ __global__ void __launch_bounds__(64) ROLL_HKD_ATTR k_rollout_hkd(ROLL_ARGS) { _
 #endif
 #ifndef HS_PLANT_SEPARATE
 #include "hsddp_plant.hip"
+#endif
+#ifndef HS_FRIC_SEPARATE      // the walks with Coulomb friction (hsddp_friction.h), likewise
+#include "hsddp_fric.hip"
 #endif
 // k_episode_latency (hsddp_latency.h) and its launcher, likewise (-DHS_LAT_SEPARATE here); the prototype is in episode.hpp either way.
 #ifndef HS_LAT_SEPARATE

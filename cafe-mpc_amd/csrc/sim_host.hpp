@@ -1,7 +1,7 @@
 // Host side of the closed-loop policy simulation and of the MPC episodes: the C entry points of include/hsddp_sim.h, hsddp_mc.h, hsddp_grf.h,
-// hsddp_substep.h, hsddp_contact.h, hsddp_terrain.h, hsddp_plant.h, hsddp_episode.h and hsddp_latency.h.  Part of hsddp_hip.hip's translation unit, host pass only: that
+// hsddp_substep.h, hsddp_contact.h, hsddp_terrain.h, hsddp_plant.h, hsddp_friction.h, hsddp_episode.h and hsddp_latency.h.  Part of hsddp_hip.hip's translation unit, host pass only: that
 // file includes it inside its host-only region, behind hsddp_handle, HIPCK, Timed and drain_events, which this code uses.  The kernels are those of
-// wb_sim.hpp, hsddp_sub.hip, hsddp_uni.hip, hsddp_ter.hip, hsddp_plant.hip and episode.hpp; which walk a run launches is sim_pick's business (sim_pick.hpp).
+// wb_sim.hpp, hsddp_sub.hip, hsddp_uni.hip, hsddp_ter.hip, hsddp_plant.hip, hsddp_fric.hip and episode.hpp; which walk a run launches is sim_pick's business (sim_pick.hpp).
 #pragma once
 #include "plant_host.hpp"
 
@@ -51,6 +51,14 @@ struct hsddp_sim {
     bool plant_on = false; int n_plants = 0;
     WbsPlantArgs* d_plant = nullptr; double* d_plant_P = nullptr; int* d_plant_of = nullptr; size_t plant_cap = 0;
     std::vector<double> plant_rows;
+    // Coulomb friction (hsddp_friction.h): allocated by hsddp_friction_set calls that switch it on (the table again when it grows: fric_cap rows).  fric_on:
+    // what later runs ask for - it acts while uni_on is set too; last_fric: the last run launched the _fric kernels.  d_fric_Sl / d_fric_NF: the sliding
+    // flags and lagged normal forces an episode carries from tick to tick (uni_keep), under the hold of d_uni_F.  d_fric_ter: the one-cell flat map without
+    // early touchdown the _fric kernels are given while the terrain is off (d_fric_H its cell, d_fric_tmap its all-zero index, d_fric_trows its unread rows)
+    bool fric_on = false, last_fric = false;
+    hsddp_friction_t fric = {};
+    WbsFricArgs* d_fric = nullptr; double *d_fric_mu = nullptr, *d_fric_rows = nullptr, *d_fric_Sl = nullptr, *d_fric_NF = nullptr; int* d_fric_of = nullptr; size_t fric_cap = 0;
+    WbsTerArgs* d_fric_ter = nullptr; double *d_fric_H = nullptr, *d_fric_trows = nullptr; int* d_fric_tmap = nullptr;
     // policy latency of an episode (hsddp_latency.h): the descriptor table and the step map the NEXT launch walks instead of h->d_ph and d_map, set
     // by hsddp_episode_advance around its walk and null otherwise
     const PhaseDev* walk_ph = nullptr; const int* walk_map = nullptr;
@@ -60,7 +68,8 @@ static void sim_free(hsddp_sim* s) {
     hipSetDevice(s->h->device);
     if (s->h->stream) hipStreamSynchronize(s->h->stream);
     void* p[] = {s->d_map, s->d_x0, s->d_final, s->d_rows, s->d_X, s->d_U, s->d_extra, s->d_kick, s->d_mc, s->d_grf_rows, s->d_Y, s->d_grf, s->d_sub, s->d_uni, s->d_uni_rows, s->d_uni_F, s->d_uni_grows, s->d_uni_grf,
-                 s->d_ter, s->d_ter_H, s->d_ter_rows, s->d_ter_E, s->d_ter_map, s->d_plant, s->d_plant_P, s->d_plant_of};
+                 s->d_ter, s->d_ter_H, s->d_ter_rows, s->d_ter_E, s->d_ter_map, s->d_plant, s->d_plant_P, s->d_plant_of,
+                 s->d_fric, s->d_fric_mu, s->d_fric_rows, s->d_fric_Sl, s->d_fric_NF, s->d_fric_of, s->d_fric_ter, s->d_fric_H, s->d_fric_trows, s->d_fric_tmap};
     for (void* q : p) if (q) hipFree(q);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -132,6 +141,10 @@ static int sim_grow(hsddp_handle* h, double*& d_table, size_t& cap, size_t need,
     return HSDDP_OK;
 }
 
+// (hsddp_friction.h) friction and the per-sample plant would both act in the next run: every entry point that starts one - hsddp_sim_run, hsddp_mc_run,
+// hsddp_episode_advance - asks this FIRST and answers HSDDP_ENOTSUP before it allocates, copies or launches anything (the rule itself is sim_pick's)
+static bool sim_unsupported(const hsddp_sim* s) { return sim_pick(SimSwitches{s->plant_on, s->uni_on, s->ter_on, s->substeps, s->grf_on, false, false, s->fric_on}).unsupported; }
+
 extern "C" {
 
 int hsddp_sim_create(hsddp_handle_t* h, int n_samples, int n_steps, int keep_traj, hsddp_sim_t** out) {
@@ -161,25 +174,29 @@ void hsddp_sim_destroy(hsddp_sim_t* s) { sim_free(s); }
 static int sim_launch(hsddp_sim* s, const double* x0, int src_device, bool mc, bool noise = false) {
     hsddp_handle* h = s->h;
     const size_t total = (size_t)h->batch * s->R;
+    const SimPick pick = sim_pick(SimSwitches{s->plant_on, s->uni_on, s->ter_on, s->substeps, s->grf_on, mc, noise, s->fric_on});
+    if (pick.unsupported) return HSDDP_ENOTSUP;      // (the entry points have asked sim_unsupported already; kept for a caller that does not)
     if (!src_device) HIPCK(hipMemcpyAsync(s->d_x0, x0, total * 36 * 8, hipMemcpyHostToDevice, h->stream));
     HIPCK(hipEventRecord(s->ev0, h->stream));
     WbsLaunch L;
     L.stream = h->stream; L.grid = (unsigned)((total + 15) / 16);
     L.ph = s->walk_ph ? s->walk_ph : h->d_ph; L.md = &h->md; L.map = s->walk_map ? s->walk_map : s->d_map; L.n_steps = s->n_steps; L.n_samples = s->R; L.total = (int)total;
     L.x0 = src_device ? x0 : s->d_x0; L.xfinal = s->d_final; L.rows = s->d_rows; L.trajX = s->d_X; L.trajU = s->d_U;
-    L.pick = sim_pick(SimSwitches{s->plant_on, s->uni_on, s->ter_on, s->substeps, s->grf_on, mc, noise});
+    L.pick = pick;
     L.mc = s->d_mc; L.gr = L.pick.records ? s->d_grf : s->d_uni_grf; L.sb = s->d_sub; L.un = s->d_uni; L.te = s->d_ter; L.pl = s->d_plant;
+    if (L.pick.family == SIM_FAM_FRIC) { L.fc = s->d_fric; if (L.pick.contact != SIM_TERRAIN) L.te = s->d_fric_ter; }      // (terrain off: the flat map)
     switch (L.pick.family) {      // (the launchers leave the runtime's error state alone: a failed launch is caught by the hipGetLastError below)
         case SIM_FAM_BASE: wbs_base_launch(L); break;
         case SIM_FAM_SUB: wbs_sub_launch(L); break;
         case SIM_FAM_UNI: wbs_uni_launch(L); break;
         case SIM_FAM_TER: wbs_ter_launch(L); break;
         case SIM_FAM_PLANT: wbs_plant_launch(L); break;
+        case SIM_FAM_FRIC: wbs_fric_launch(L); break;
     }
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(s->ev1, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    s->timed = true; s->last_grf = s->grf_on; s->last_uni = s->uni_on; s->last_ter = L.pick.contact == SIM_TERRAIN;
+    s->timed = true; s->last_grf = s->grf_on; s->last_uni = s->uni_on; s->last_ter = L.pick.contact == SIM_TERRAIN; s->last_fric = L.pick.family == SIM_FAM_FRIC;
     return HSDDP_OK;
 }
 
@@ -187,6 +204,7 @@ int hsddp_sim_run(hsddp_sim_t* s, const double* x0, int src_device) {
     if (!s || !x0) return HSDDP_EINVAL;
     hsddp_handle* h = s->h;
     if (s->gen != h->window_gen) return HSDDP_EINVAL;      // hsddp_reconfigure moved the window: the step map is that of the old one
+    if (sim_unsupported(s)) return HSDDP_ENOTSUP;
     HIPCK(hipSetDevice(h->device));
     const int rc = sim_launch(s, x0, src_device, false);
     if (rc == HSDDP_OK) s->last_mc = 0;
@@ -198,6 +216,7 @@ int hsddp_mc_run(hsddp_sim_t* s, const double* x0, int x0_device, const hsddp_mc
     hsddp_handle* h = s->h;
     if (s->gen != h->window_gen) return HSDDP_EINVAL;
     if (!mc_dist_ok(s, d, kick)) return HSDDP_EINVAL;
+    if (sim_unsupported(s)) return HSDDP_ENOTSUP;
     HIPCK(hipSetDevice(h->device));
     if (!kick && d->sigma_u == 0.0 && d->sigma_q == 0.0 && d->sigma_v == 0.0 && d->u_max <= 0.0 && d->fall_height <= 0.0) {      // nothing switched on: the plain kernel
         const int rc = sim_launch(s, x0, x0_device, false);
@@ -376,6 +395,62 @@ int hsddp_terrain_get(hsddp_sim_t* s, int b0, int nb, hsddp_terrain_row_t* rows)
     });
 }
 
+int hsddp_friction_set(hsddp_sim_t* s, int on, const hsddp_friction_t* f, const double* mu, const int* mu_of) {
+    if (!s) return HSDDP_EINVAL;
+    if (!on) { s->fric_on = false; return HSDDP_OK; }      // later runs launch the kernels without friction; the buffers and the table are kept
+    if (!f || !mu || f->n_mu < 1 || f->n_mu > 65536 || !std::isfinite(f->v_stick) || f->v_stick < 0.0) return HSDDP_EINVAL;
+    for (int i = 0; i < f->n_mu; i++) {
+        const double ms = mu[2 * i], mk = mu[2 * i + 1];
+        if (!std::isfinite(ms) || !std::isfinite(mk) || mk < 0.0 || mk > ms) return HSDDP_EINVAL;
+    }
+    hsddp_handle* h = s->h;
+    const size_t total = (size_t)h->batch * s->R;
+    if (mu_of) for (size_t i = 0; i < total; i++) if (mu_of[i] < 0 || mu_of[i] >= f->n_mu) return HSDDP_EINVAL;
+    if (h->f32) return HSDDP_ENOTSUP;
+    HIPCK(hipSetDevice(h->device));
+    if (!s->d_fric) SIM_CK(hipMalloc((void**)&s->d_fric, sizeof(WbsFricArgs)));      // (a failure: see SIM_CK - friction stays as it was)
+    if (!s->d_fric_rows) SIM_CK(hipMalloc((void**)&s->d_fric_rows, total * SIM_FRIC_ROW * 8));
+    if (!s->d_fric_of) SIM_CK(hipMalloc((void**)&s->d_fric_of, total * sizeof(int)));
+    if (s->uni_keep && !s->d_fric_Sl) { SIM_CK(hipMalloc((void**)&s->d_fric_Sl, total * 4 * 8)); HIPCK(hipMemsetAsync(s->d_fric_Sl, 0, total * 4 * 8, h->stream)); }
+    if (s->uni_keep && !s->d_fric_NF) { SIM_CK(hipMalloc((void**)&s->d_fric_NF, total * 4 * 8)); HIPCK(hipMemsetAsync(s->d_fric_NF, 0, total * 4 * 8, h->stream)); }
+    if (!s->d_fric_H) { SIM_CK(hipMalloc((void**)&s->d_fric_H, 8)); HIPCK(hipMemsetAsync(s->d_fric_H, 0, 8, h->stream)); }
+    if (!s->d_fric_tmap) { SIM_CK(hipMalloc((void**)&s->d_fric_tmap, total * sizeof(int))); HIPCK(hipMemsetAsync(s->d_fric_tmap, 0, total * sizeof(int), h->stream)); }
+    if (!s->d_fric_trows) SIM_CK(hipMalloc((void**)&s->d_fric_trows, total * SIM_TER_ROW * 8));
+    if (!s->d_fric_ter) {      // the flat map of runs with the terrain off: one cell of height 0, no early touchdown, E never carried (it stays empty)
+        SIM_CK(hipMalloc((void**)&s->d_fric_ter, sizeof(WbsTerArgs)));
+        WbsTerArgs t;
+        t.H = s->d_fric_H; t.map_of = s->d_fric_tmap; t.nx = 1; t.ny = 1; t.n_maps = 1; t.early = 0;
+        t.x0 = 0.0; t.y0 = 0.0; t.cx = 1.0; t.cy = 1.0; t.w_td = 0.0; t.rows = s->d_fric_trows; t.E = nullptr;
+        HIPCK(hipMemcpyAsync(s->d_fric_ter, &t, sizeof(t), hipMemcpyHostToDevice, h->stream));
+    }
+    int rc = sim_ensure_records_and_trip_count(s);
+    if (rc == HSDDP_OK) rc = sim_grow(h, s->d_fric_mu, s->fric_cap, (size_t)f->n_mu, 2);
+    if (rc != HSDDP_OK) return rc;
+    HIPCK(hipMemcpyAsync(s->d_fric_mu, mu, (size_t)f->n_mu * 2 * 8, hipMemcpyHostToDevice, h->stream));
+    if (mu_of) HIPCK(hipMemcpyAsync(s->d_fric_of, mu_of, total * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    else HIPCK(hipMemsetAsync(s->d_fric_of, 0, total * sizeof(int), h->stream));
+    WbsFricArgs a;
+    a.mu = s->d_fric_mu; a.mu_of = s->d_fric_of; a.n_mu = f->n_mu; a.pad = 0; a.v_stick = f->v_stick; a.rows = s->d_fric_rows; a.Sl = s->d_fric_Sl; a.NF = s->d_fric_NF;      // (both or neither: a set call that failed between the two allocations returned above)
+    HIPCK(hipMemcpyAsync(s->d_fric, &a, sizeof(a), hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));      // mu and mu_of are the caller's: they may go once the call returns
+    s->fric_on = true; s->fric.v_stick = f->v_stick; s->fric.n_mu = f->n_mu; s->fric.pad = 0;
+    return HSDDP_OK;
+}
+
+int hsddp_friction_get_params(hsddp_sim_t* s, int* on, hsddp_friction_t* f) {
+    if (!s || !on || !f) return HSDDP_EINVAL;
+    *on = s->fric_on ? 1 : 0; *f = s->fric;
+    return HSDDP_OK;
+}
+
+int hsddp_friction_get(hsddp_sim_t* s, int b0, int nb, hsddp_friction_row_t* rows) {
+    if (!sim_range_ok(s, b0, nb) || !rows || !s->last_fric) return HSDDP_EINVAL;
+    return sim_fetch_rows(s, b0, nb, s->d_fric_rows, SIM_FRIC_ROW, [&](size_t i, const double* q) {
+        rows[i].first_slide = (int)q[0]; rows[i].n_onset = (int)q[1]; rows[i].n_slide = (int)q[2]; rows[i].n_restick = (int)q[3]; rows[i].slide_final = (int)q[4]; rows[i].pad = 0;
+        rows[i].max_speed = q[5]; rows[i].distance = q[6];
+    });
+}
+
 int hsddp_plant_set(hsddp_sim_t* s, int on, int n_plants, const double* P, const int* plant_of) {
     if (!s) return HSDDP_EINVAL;
     if (!on) { s->plant_on = false; return HSDDP_OK; }      // later runs launch the kernels without the plant; the buffers and the table are kept
@@ -521,6 +596,8 @@ int hsddp_episode_reset(hsddp_episode_t* e, const double* x0, int src_device) {
     }
     if (e->sim->d_uni_F) HIPCK(hipMemsetAsync(e->sim->d_uni_F, 0, B * 4 * 8, h->stream));      // (hsddp_contact.h) every foot attached again
     if (e->sim->d_ter_E) HIPCK(hipMemsetAsync(e->sim->d_ter_E, 0, B * 4 * 8, h->stream));      // (hsddp_terrain.h) no swing foot held
+    if (e->sim->d_fric_Sl) HIPCK(hipMemsetAsync(e->sim->d_fric_Sl, 0, B * 4 * 8, h->stream));      // (hsddp_friction.h) no foot sliding
+    if (e->sim->d_fric_NF) HIPCK(hipMemsetAsync(e->sim->d_fric_NF, 0, B * 4 * 8, h->stream));
     if (e->d_lat_stale) HIPCK(hipMemsetAsync(e->d_lat_stale, 0, B * sizeof(int), h->stream));      // (hsddp_latency.h) nothing stale yet; the delays stay
     HIPCK(hipStreamSynchronize(h->stream));
     e->tick = 0; e->n_impacts = 0; e->started = true; e->lat_valid = false;
@@ -536,6 +613,7 @@ int hsddp_episode_advance(hsddp_episode_t* e, const hsddp_mc_dist_t* dist, const
     int pend = e->pending;
     if (moved && !sim_step_map(h, e->n_exec, e->map_new.data(), &pend)) return HSDDP_EINVAL;      // the window no longer leads with n_exec whole-body knots
     if (e->lat_on && !episode_lat_plan(e)) return HSDDP_EINVAL;      // (hsddp_latency.h) ... or not with the lat_D more the stash reads
+    if (sim_unsupported(s)) return HSDDP_ENOTSUP;      // (hsddp_friction.h) before the rebind and the latency launch: the tick leaves nothing behind
     HIPCK(hipSetDevice(h->device));
     // rebind: the step map of the new window into the simulation object's buffer (the walk below synchronises the stream).  It stays in place if the
     // walk then fails with a device error - the map is that of the handle's current window either way; "nothing changed" is promised for HSDDP_EINVAL

@@ -85,6 +85,43 @@ template <class S> struct wbs_is_plant_io<WbsPlantIO<S>> { static constexpr bool
 template <class Q, class S> HD S wbs_lane_flag(int, WbsPlantIO<S>* io) { return io->cl; }
 template <class... LO> HD const double* wbs_plant_row(LO*...) { return nullptr; }
 template <class S> HD const double* wbs_plant_row(WbsPlantIO<S>* io) { return io->row; }
+// Coulomb friction (include/hsddp_friction.h): the exchange of WbsTerIO plus the lane's friction COLUMN, `col` with `stride` doubles between its slots - on
+// the device the lane's own column of the parked LDS block, so that nothing of it sits in registers across the solve's register peak.  Slots the solve
+// reads: SL (1: the lane's foot is in the sliding set), FRESH (1: it joined the set in this substep), NF (the lagged normal force), TX / TY (the direction
+// of a fresh foot's friction).  Slots it writes: EFF (1: this solve treated the foot as sliding - 0 for a foot that re-sticks), FX / FY (the friction force
+// it applied), WX / WY (the tangential velocity of the foot point at the state it was given).  mur: the sample's row (mu_s, mu_k) of the table; vstick:
+// the re-stick speed.  A sliding foot keeps its z row alone: its x and y columns of X, its right-hand side and its multipliers are masked, its Gram block
+// gets the identity on those two diagonals, and the known force enters tau - h through J^T f_t.  An element type of its own: every other solve
+// instantiates what it did before.
+enum { FRIC_SL = 0, FRIC_FRESH, FRIC_NF, FRIC_TX, FRIC_TY, FRIC_FIRST, FRIC_NONSET, FRIC_NSLIDE, FRIC_NRESTICK, FRIC_VMAX, FRIC_DIST, FRIC_EFF, FRIC_FX, FRIC_FY, FRIC_WX, FRIC_WY, FRIC_SLOTS };
+template <class S> struct WbsFricIO { S cl, pz, wz, px, py; V3<S> lam; S* col; int stride; const double* mur; double vstick; };
+template <class T> struct wbs_is_fric_io { static constexpr bool value = false; };
+template <class S> struct wbs_is_fric_io<WbsFricIO<S>> { static constexpr bool value = true; };
+template <class Q, class S> HD S wbs_lane_flag(int, WbsFricIO<S>* io) { return io->cl; }
+#ifdef HS_HOST_EMU
+inline Q4 wbs_sqrt(const Q4& x) { return Q4(std::sqrt(x.v[0]), std::sqrt(x.v[1]), std::sqrt(x.v[2]), std::sqrt(x.v[3])); }
+template <class S> inline S& wbs_fric_slot(WbsFricIO<S>* io, int i) { return io->col[i * io->stride]; }
+#else
+HD double wbs_sqrt(double x) { return ::sqrt(x); }
+// the offset is laundered: every use is a read of LDS where it stands, never a value the compiler carries from an earlier one
+template <class S> HD S& wbs_fric_slot(WbsFricIO<S>* io, int i) { int o = i * io->stride; asm volatile("" : "+v"(o)); return io->col[o]; }
+#endif
+// What a sliding solve needs, formed where fvel is known: the effective flag and the friction force.  A fresh foot is pushed along its stored
+// direction; any other sliding foot against its tangential velocity if that is faster than vstick, and re-sticks otherwise (selects, no products with a
+// flag: the direction of a foot at rest is 0 / 0).  m0: 1 in mode 0, 0 in mode 1 - an impact holds every foot with three rows.
+template <class Q, class S> HD void wbs_fric_force(WbsFricIO<S>* io, const V3<S>& fvel, double m0) {
+    const S zero = S(0.0), one = S(1.0);
+    const S wt = wbs_sqrt(fvel.x * fvel.x + fvel.y * fvel.y);
+    const typename Q::B sliding = Q::gt(io->cl * wbs_fric_slot(io, FRIC_SL) * m0, S(0.5)), isfresh = Q::gt(wbs_fric_slot(io, FRIC_FRESH), S(0.5)), moving = Q::gt(wt, S(io->vstick));
+    const S eff = Q::sel(sliding, Q::sel(isfresh, one, Q::sel(moving, one, zero)), zero);
+    const S rw = Q::rcp(wt), mag = Q::ld(io->mur, 1, 0) * wbs_fric_slot(io, FRIC_NF);
+    const S dx = Q::sel(isfresh, wbs_fric_slot(io, FRIC_TX), -(fvel.x * rw)), dy = Q::sel(isfresh, wbs_fric_slot(io, FRIC_TY), -(fvel.y * rw));
+    const typename Q::B act = Q::gt(eff, S(0.5));
+    wbs_fric_slot(io, FRIC_EFF) = eff; wbs_fric_slot(io, FRIC_FX) = Q::sel(act, mag * dx, zero); wbs_fric_slot(io, FRIC_FY) = Q::sel(act, mag * dy, zero);
+    wbs_fric_slot(io, FRIC_WX) = fvel.x; wbs_fric_slot(io, FRIC_WY) = fvel.y;
+}
+template <class S, class... LO> HD WbsFricIO<S>* wbs_fric_ptr(LO*...) { return nullptr; }
+template <class S> HD WbsFricIO<S>* wbs_fric_ptr(WbsFricIO<S>* io) { return io; }
 // rbi_link with a mass that is a value of the lane (wb_quad.hpp's takes a literal): the same operations in the same order
 template <class S> HD RBI<S> wbs_plant_link(S m, S cx, S cy, S cz, S ixx, S ixy, S ixz, S iyy, S iyz, S izz) {
     RBI<S> R; R.m = m; R.h = {m * cx, m * cy, m * cz};
@@ -277,6 +314,12 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         Jb[0][0] = S(1.0); Jb[0][1] = zero; Jb[0][2] = zero; Jb[1][0] = zero; Jb[1][1] = S(1.0); Jb[1][2] = zero; Jb[2][0] = zero; Jb[2][1] = zero; Jb[2][2] = S(1.0);
         Jb[0][3] = j3.x; Jb[1][3] = j3.y; Jb[2][3] = j3.z; Jb[0][4] = j4.x; Jb[1][4] = j4.y; Jb[2][4] = j4.z; Jb[0][5] = j5.x; Jb[1][5] = j5.y; Jb[2][5] = j5.z;
     }
+    // (hsddp_friction.h) the lane's flag of the x and y force directions - cl for a sticking foot, 0 for a sliding one; c_z stays cl - and the known
+    // tangential force of a sliding foot through J^T: ftl the lane's three leg rows, ftb the six base rows summed over the quad
+    constexpr bool FRIC = (wbs_is_fric_io<LO>::value || ...);
+    WbsFricIO<S>* const fio = wbs_fric_ptr<S>(lam_out...);      // (null without friction, and then never used)
+    if constexpr (FRIC) wbs_fric_force<Q, S>(fio, fvel, m0);
+    auto cxy_of = [&]() { return cl * (S(1.0) - wbs_fric_slot(fio, FRIC_EFF)); };      // (friction only) read from the column at every use
     // ---- contact solve, block form.  L = [ blockdiag(L_l) 0 ; E  L_S ],  E_l = Ct L_l^-T (6 x 3),  S = B - sum_l E_l E_l^T
     const Chol3<S> Ll = chol3<Q, S>(d_aa, d_ha, d_hh, d_ka, d_kh, d_kk);
     S E[6][3];
@@ -289,18 +332,28 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
     for (int i = 0; i < 6; i++) _Pragma("unroll") for (int j = 0; j <= i; j++) LS[tri(i, j)] = Bm[tri(i, j)] - Q::sum(E[i][0] * E[j][0] + E[i][1] * E[j][1] + E[i][2] * E[j][2]);
     chol6<Q, S>(LS, rdS);
     // y = L^-1 (tau - h): leg part in the lane, base part replicated (mode 1: no bias, y = 0)
-    const V3<S> yl = fwd3(Ll, V3<S>{m0 * (ul[0] - hl[0]), m0 * (ul[1] - hl[1]), m0 * (ul[2] - hl[2])});
+    V3<S> yl_; S ftb[6];
+    if constexpr (FRIC) {
+        const S fx = wbs_fric_slot(fio, FRIC_FX), fy = wbs_fric_slot(fio, FRIC_FY);
+        _Pragma("unroll") for (int c = 0; c < 6; c++) ftb[c] = Q::sum(Jb[0][c] * fx + Jb[1][c] * fy);
+        yl_ = fwd3(Ll, V3<S>{m0 * (ul[0] - hl[0]) + (Ja.r[0].x * fx + Ja.r[1].x * fy), m0 * (ul[1] - hl[1]) + (Ja.r[0].y * fx + Ja.r[1].y * fy), m0 * (ul[2] - hl[2]) + (Ja.r[0].z * fx + Ja.r[1].z * fy)});
+    } else yl_ = fwd3(Ll, V3<S>{m0 * (ul[0] - hl[0]), m0 * (ul[1] - hl[1]), m0 * (ul[2] - hl[2])});
+    const V3<S> yl = yl_;
     S yb[6];
+    if constexpr (FRIC) { _Pragma("unroll") for (int c = 0; c < 6; c++) yb[c] = (ftb[c] - m0 * hb[c]) - Q::sum(E[c][0] * yl.x + E[c][1] * yl.y + E[c][2] * yl.z); }
+    else
     _Pragma("unroll") for (int c = 0; c < 6; c++) yb[c] = -(m0 * hb[c]) - Q::sum(E[c][0] * yl.x + E[c][1] * yl.y + E[c][2] * yl.z);
     fwd6(LS, rdS, yb);
     // X = L^-1 Jc^T for the lane's foot (zero for a swing leg): Xt (3 leg rows x 3 force directions), Xb (6 base rows x 3)
     M33<S> Xt; S Xb[6][3];      // Xt.r[d] = column d (force direction d) as a 3-vector over the leg rows ; Xb[c][d]
     _Pragma("unroll")
     for (int d = 0; d < 3; d++) {
-        const V3<S> xt = scale(cl, fwd3(Ll, Ja.r[d]));      // L_l^-1 (row d of Ja)^T
+        S cd = cl;      // the lane's flag of force direction d
+        if constexpr (FRIC) { if (d < 2) cd = cxy_of(); }
+        const V3<S> xt = scale(cd, fwd3(Ll, Ja.r[d]));      // L_l^-1 (row d of Ja)^T
         Xt.r[d] = xt;
         S w[6];
-        _Pragma("unroll") for (int c = 0; c < 6; c++) w[c] = cl * Jb[d][c] - (E[c][0] * xt.x + E[c][1] * xt.y + E[c][2] * xt.z);
+        _Pragma("unroll") for (int c = 0; c < 6; c++) w[c] = cd * Jb[d][c] - (E[c][0] * xt.x + E[c][1] * xt.y + E[c][2] * xt.z);
         fwd6(LS, rdS, w);
         _Pragma("unroll") for (int c = 0; c < 6; c++) Xb[c][d] = w[c];
     }
@@ -324,10 +377,12 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
     M33<S> Gd;
     {
         const S dg = 1.0 - cl;      // (the damping enters at the factorisation)
+        S dgx = dg;                 // (friction) a masked direction gets the identity too
+        if constexpr (FRIC) dgx = 1.0 - cxy_of();
         _Pragma("unroll")
         for (int r = 0; r < 3; r++) {
             const S e0 = dot3(Xt.r[r], Xt.r[0]), e1 = dot3(Xt.r[r], Xt.r[1]), e2 = dot3(Xt.r[r], Xt.r[2]);
-            Gd.r[r] = {e0 + (r == 0 ? dg : zero), e1 + (r == 1 ? dg : zero), e2 + (r == 2 ? dg : zero)};
+            Gd.r[r] = {e0 + (r == 0 ? dgx : zero), e1 + (r == 1 ? dgx : zero), e2 + (r == 2 ? dg : zero)};
         }
         // added to G[own lane]: by selects on the lane's leg
         const S m0 = Q::legc(1, 0, 0, 0), m1 = Q::legc(0, 1, 0, 0), m2 = Q::legc(0, 0, 1, 0), m3 = Q::legc(0, 0, 0, 1);
@@ -344,6 +399,8 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         // mode 0: gam = Jdot v + 2 alpha J v (WBM.cpp:392-408) ; mode 1: the right-hand side is -Jc v, and J v of a foot is its velocity
         const double a2 = 2.0 * bg_alpha;
         const V3<S> gam = {m0 * (jdv.x + a2 * fvel.x) + m1 * fvel.x, m0 * (jdv.y + a2 * fvel.y) + m1 * fvel.y, m0 * (jdv.z + a2 * fvel.z) + m1 * fvel.z};
+        if constexpr (FRIC) { const S cxy = cxy_of(); rhs = {cxy * (-xy[0] - gam.x), cxy * (-xy[1] - gam.y), cl * (-xy[2] - gam.z)}; }
+        else
         rhs = {cl * (-xy[0] - gam.x), cl * (-xy[1] - gam.y), cl * (-xy[2] - gam.z)};
     }
     // block Cholesky of G over the quad: block column kc is finished by lane kc (its diagonal block), then lanes f > kc form L_f,kc.
@@ -359,7 +416,9 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         auto right_solve = [&](M33<S>& A, const Chol3<S>& Lk) { _Pragma("unroll") for (int r = 0; r < 3; r++) { V3<S> a = A.r[r], x; x.x = a.x * Lk.r0; x.y = (a.y - x.x * Lk.l10) * Lk.r1; x.z = (a.z - x.x * Lk.l20 - x.y * Lk.l21) * Lk.r2; A.r[r] = x; } };
         // own diagonal block = G[own]: picked by selects (each lane needs ITS block at ITS step; every lane runs every step)
         const S dmp = cl * damping;
-        auto own_diag = [&](const M33<S>& Gk) { return chol3<Q, S>(Gk.r[0].x + dmp, Gk.r[1].x, Gk.r[1].y + dmp, Gk.r[2].x, Gk.r[2].y, Gk.r[2].z + dmp); };
+        S dmpx = dmp;      // (friction) the damping goes to constrained directions only
+        if constexpr (FRIC) dmpx = cxy_of() * damping;
+        auto own_diag = [&](const M33<S>& Gk) { return chol3<Q, S>(Gk.r[0].x + dmpx, Gk.r[1].x, Gk.r[1].y + dmpx, Gk.r[2].x, Gk.r[2].y, Gk.r[2].z + dmp); };
         // step 0: lane 0's diagonal block is final
         Chol3<S> L0 = own_diag(G[0]);                       // meaningful in lane 0
         const Chol3<S> L00 = bcastL(J0{}, L0);
@@ -405,8 +464,11 @@ HD void wbs_contact_dynamics(const ModelDev& md, int cmask, int mode, double dam
         V3<S> lam0 = bwd3(Ld, z - w30 - w20 - w10);                           // valid in lane 0
         rhs = {pick(lam0.x, lam1.x, lam2.x, lam3.x), pick(lam0.y, lam1.y, lam2.y, lam3.y), pick(lam0.z, lam1.z, lam2.z, lam3.z)};
     }
-    const V3<S> lam = scale(cl, rhs);      // contact force of the lane's foot (world axes); zero for a swing leg
-    if constexpr (PLANT || (wbs_is_ter_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z, lam_out->px = fpos.x, lam_out->py = fpos.y), ...); }
+    V3<S> lam_;
+    if constexpr (FRIC) { const S cxy = cxy_of(); lam_ = {cxy * rhs.x, cxy * rhs.y, cl * rhs.z}; }      // (a sliding foot's tangential multipliers are zero: its force there is f_t)
+    else lam_ = scale(cl, rhs);
+    const V3<S> lam = lam_;      // contact force of the lane's foot (world axes); zero for a swing leg
+    if constexpr (PLANT || FRIC || (wbs_is_ter_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z, lam_out->px = fpos.x, lam_out->py = fpos.y), ...); }
     else if constexpr ((wbs_is_uni_io<LO>::value || ...)) { ((lam_out->lam = lam, lam_out->pz = fpos.z, lam_out->wz = fvel.z), ...); }
     else if constexpr (sizeof...(LO) > 0) { ((lam_out != nullptr ? (void)(*lam_out = lam) : (void)0), ...); }
     // qdd = L^-T (y + X lam): base part replicated, leg part in the lane
@@ -448,8 +510,8 @@ struct WbsMcArgs {
 // NOISE 0: the walk of a run whose three sigmas are zero, compiled without the generator.  Measured (MI355X, config 3 x 16 samples x 200 steps, plain
 // run 9.88 ms): with the generator compiled in and branched over, a run with only u_max set took 11.74 ms - the register allocation of the whole
 // loop pays for code that does not run; without it 9.83 ms.  So the host picks the instantiation, and every other switch stays a run-time branch.
-struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0, UNI = 0, TER = 0, PLANT = 0; };
-template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0, UNI = 0, TER = 0, PLANT = 0; const WbsMcArgs* a; };
+struct WbsPlain { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 0, UNI = 0, TER = 0, PLANT = 0, FRIC = 0; };
+template <int NOISE_> struct WbsMc { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 0, UNI = 0, TER = 0, PLANT = 0, FRIC = 0; const WbsMcArgs* a; };
 constexpr int SIM_PARK_MC = SIM_PARK + 2;       // ... and n_sat, first_fall
 // Contact-force records (include/hsddp_grf.h): GRF 1 in the policy.  The walk takes the lane's multiplier of every mode-0 solve, keeps five running
 // values per lane (lane = leg) - smallest / largest stance fz, smallest cone margin, first violating step, violations - and joins them over the
@@ -462,8 +524,8 @@ struct WbsGrfArgs {
 constexpr int SIM_GRF_ROW = 5;     // min_fz | min_cone | max_fz | first_slip | n_slip
 constexpr int SIM_GRF_PARK = 5;    // the lane's running values, parked behind the others
 constexpr double SIM_GRF_NONE = 1e18;      // first_slip of a lane without a violation while the walk runs: above every step index
-struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0, UNI = 0, TER = 0, PLANT = 0; const WbsGrfArgs* gr; };
-template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0, UNI = 0, TER = 0, PLANT = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
+struct WbsGrf { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 0, UNI = 0, TER = 0, PLANT = 0, FRIC = 0; const WbsGrfArgs* gr; };
+template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 0, UNI = 0, TER = 0, PLANT = 0, FRIC = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; };
 // Sub-stepped integration (include/hsddp_substep.h): SUB 1 in the policy.  A control knot is S forward-Euler steps of dt / S under the knot's torque
 // (zero-order hold): the feedback, the noise and every record of the state stay once per control step, the contact solve, the divergence test and
 // the force records run once per substep.  S is a run-time trip count read from device memory through a laundered pointer, as the other switches
@@ -471,10 +533,10 @@ template <int NOISE_> struct WbsMcGrf { static constexpr int MC = 1, NOISE = NOI
 // constexpr (D::SUB)` below is this code, and the six policies above compile to what they compiled to without it.
 struct WbsSubArgs { int substeps, pad; };      // 2 .. 64 (the host launches the kernels above for 1)
 constexpr int SIM_SUB_PARK = 3;
-struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1, UNI = 0, TER = 0, PLANT = 0; const WbsSubArgs* sb; };
-template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1, UNI = 0, TER = 0, PLANT = 0; const WbsMcArgs* a; const WbsSubArgs* sb; };
-struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
-template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+struct WbsSub { static constexpr int MC = 0, NOISE = 0, GRF = 0, SUB = 1, UNI = 0, TER = 0, PLANT = 0, FRIC = 0; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 0, SUB = 1, UNI = 0, TER = 0, PLANT = 0, FRIC = 0; const WbsMcArgs* a; const WbsSubArgs* sb; };
+struct WbsGrfSub { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 0, FRIC = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
+template <int NOISE_> struct WbsMcGrfSub { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 0, FRIC = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; };
 // Unilateral ground contact (include/hsddp_contact.h): UNI 1 in the policy, always with the records and the sub-step loop (GRF 1, SUB 1; S = 1 too).
 // The lane (= leg) carries F, 1 if its foot is a scheduled stance foot that is FREE, and the contact flag of every solve is the lane's own: attached =
 // scheduled and not free.  The trip loop of a control step becomes a small state machine around the ONE call site of the solve -
@@ -491,8 +553,8 @@ struct WbsUniArgs {
 };
 constexpr int SIM_UNI_ROW = 6;      // first_release | n_release | n_land | n_free | free_final | max_lift
 constexpr int SIM_UNI_PARK = 7;     // F, T, first_release, n_release, n_land, n_free, max_lift of the lane, parked behind everything else
-struct WbsUni { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
-template <int NOISE_> struct WbsMcUni { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
+struct WbsUni { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 0, FRIC = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
+template <int NOISE_> struct WbsMcUni { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 0, FRIC = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; };
 // Terrain and early swing-foot touchdown (include/hsddp_terrain.h): TER 1 in the policy, on top of UNI = GRF = SUB = 1.  The landing test compares with
 // a looked-up height instead of a constant, the tested set grows by the swing feet, and the attached set of a solve by the swing feet that landed: the
 // lane carries E, 1 if its foot is a SWING foot that is attached.  The solve hands the foot's x and y back through WbsTerIO; the lookup is one per-lane
@@ -508,8 +570,8 @@ struct WbsTerArgs {
 };
 constexpr int SIM_TER_ROW = 6;      // first_early | n_early | n_early_release | n_held | early_final | max_pen
 constexpr int SIM_TER_PARK = 6;     // E, first_early, n_early, n_early_release, n_held, max_pen of the lane
-struct WbsTer { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
-template <int NOISE_> struct WbsMcTer { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
+struct WbsTer { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 0, FRIC = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
+template <int NOISE_> struct WbsMcTer { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 0, FRIC = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; };
 template <bool TER, class S> struct wbs_io_of { using type = WbsUniIO<S>; };
 template <class S> struct wbs_io_of<true, S> { using type = WbsTerIO<S>; };
 // Plant-model mismatch (include/hsddp_plant.h): PLANT 1 in the policy, always with the records and the sub-step loop (GRF 1, SUB 1; S = 1 too), on top of
@@ -524,14 +586,34 @@ struct WbsPlantArgs {
     const int* plant_of;          // [B R] the row of a sample, checked against n_plants by the host
     int n_plants, pad;
 };
-struct WbsPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsPlantArgs* pl; };
-template <int NOISE_> struct WbsMcPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsPlantArgs* pl; };
-struct WbsUniPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsPlantArgs* pl; };
-template <int NOISE_> struct WbsMcUniPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsPlantArgs* pl; };
-struct WbsTerPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsPlantArgs* pl; };
-template <int NOISE_> struct WbsMcTerPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsPlantArgs* pl; };
+struct WbsPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 1, FRIC = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsPlantArgs* pl; };
+template <int NOISE_> struct WbsMcPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 0, TER = 0, PLANT = 1, FRIC = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsPlantArgs* pl; };
+struct WbsUniPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 1, FRIC = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsPlantArgs* pl; };
+template <int NOISE_> struct WbsMcUniPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 0, PLANT = 1, FRIC = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsPlantArgs* pl; };
+struct WbsTerPlant { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 1, FRIC = 0; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsPlantArgs* pl; };
+template <int NOISE_> struct WbsMcTerPlant { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 1, FRIC = 0; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsPlantArgs* pl; };
 template <bool PLANT, bool TER, class S> struct wbs_io_sel { using type = typename wbs_io_of<TER, S>::type; };
 template <bool TER, class S> struct wbs_io_sel<true, TER, S> { using type = WbsPlantIO<S>; };
+// Coulomb friction (include/hsddp_friction.h): FRIC 1 in the policy, on top of UNI = TER = GRF = SUB = 1 (with the terrain off the host binds a one-cell
+// flat map with early = 0, which is the contact rule alone).  The lane carries the sliding flag of its foot, the fresh flag, the lagged normal force and
+// the direction of a fresh foot's friction; every mode-0 solve takes them through WbsFricIO and treats a sliding foot with its z row alone.  Behind the
+// lift-off test of a solve comes the onset test - the sticking attached foot with the smallest circular-cone margin mu_s lambda_z - |lambda_t| joins the
+// sliding set if that margin is negative - as one more reason to solve again.  The flags, n_f, the direction and the six running values of the row are
+// parked behind everything else.  Every `if constexpr (D::FRIC)` below is this code, and the policies above compile to what they compiled to without it.
+struct WbsFricArgs {
+    const double* mu;             // [n_mu][2] mu_s | mu_k
+    const int* mu_of;             // [B R] the row of a sample, checked against n_mu by the host
+    int n_mu, pad;
+    double v_stick;               // a sliding foot slower than this re-sticks
+    double* rows;                 // [B R][SIM_FRIC_ROW]
+    double *Sl, *NF;              // [B R][4] twice: the sliding flags and lagged normal forces carried from run to run (episodes), as WbsUniArgs::F (and under its hold); null: Sl starts empty
+};
+constexpr int SIM_FRIC_ROW = 7;      // first_slide | n_onset | n_slide | n_restick | slide_final | max_speed | distance
+constexpr int SIM_FRIC_PARK = FRIC_SLOTS;    // sl, fresh, n_f, t_x, t_y, first_slide, n_onset, n_slide, n_restick, max_speed, distance of the lane, and the five slots the solve writes (WbsFricIO)
+struct WbsFric { static constexpr int MC = 0, NOISE = 0, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 0, FRIC = 1; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsFricArgs* fc; };
+template <int NOISE_> struct WbsMcFric { static constexpr int MC = 1, NOISE = NOISE_, GRF = 1, SUB = 1, UNI = 1, TER = 1, PLANT = 0, FRIC = 1; const WbsMcArgs* a; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsFricArgs* fc; };
+template <bool FRIC, bool PLANT, bool TER, class S> struct wbs_io_pick { using type = typename wbs_io_sel<PLANT, TER, S>::type; };
+template <bool PLANT, bool TER, class S> struct wbs_io_pick<true, PLANT, TER, S> { using type = WbsFricIO<S>; };
 // Height of map m at the foot point (px, py), relative to z_ground (sim.terrain_height is the definition).  The cell index is clamped as a double - fmax
 // sends a NaN to 0, fmin an infinity to the last cell - BEFORE it becomes an integer: no address outside the grid can be formed, whatever the state holds.
 HD double wbs_ter_height_lane(const WbsTerArgs& t, int m, double px, double py) {
@@ -574,6 +656,7 @@ inline const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { return p; }
 inline const WbsUniArgs* wbs_uni_fresh(const WbsUniArgs* p) { return p; }
 inline const WbsTerArgs* wbs_ter_fresh(const WbsTerArgs* p) { return p; }
 inline const WbsPlantArgs* wbs_plant_fresh(const WbsPlantArgs* p) { return p; }
+inline const WbsFricArgs* wbs_fric_fresh(const WbsFricArgs* p) { return p; }
 inline Q4 wbs_ter_height(const WbsTerArgs& t, int m, const Q4& px, const Q4& py) { return Q4(wbs_ter_height_lane(t, m, px.v[0], py.v[0]), wbs_ter_height_lane(t, m, px.v[1], py.v[1]), wbs_ter_height_lane(t, m, px.v[2], py.v[2]), wbs_ter_height_lane(t, m, px.v[3], py.v[3])); }
 inline bool wbs_any(const Q4& f) { return f.v[0] > 0.5 || f.v[1] > 0.5 || f.v[2] > 0.5 || f.v[3] > 0.5; }      // (host: the quad is the whole wave)
 #else
@@ -586,6 +669,7 @@ HD const WbsSubArgs* wbs_sub_fresh(const WbsSubArgs* p) { asm volatile("" : "+s"
 HD const WbsUniArgs* wbs_uni_fresh(const WbsUniArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsTerArgs* wbs_ter_fresh(const WbsTerArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD const WbsPlantArgs* wbs_plant_fresh(const WbsPlantArgs* p) { asm volatile("" : "+s"(p)); return p; }
+HD const WbsFricArgs* wbs_fric_fresh(const WbsFricArgs* p) { asm volatile("" : "+s"(p)); return p; }
 HD double wbs_ter_height(const WbsTerArgs& t, int m, double px, double py) { return wbs_ter_height_lane(t, m, px, py); }
 // true if the 0 / 1 flag is set in ANY active lane of the wave: a ballot, so the answer is wave-uniform and the branch on it a scalar one
 HD bool wbs_any(double f) { return __builtin_amdgcn_ballot_w64(f > 0.5) != 0ull; }
@@ -613,6 +697,23 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
     // and held (foot, substep) pairs of the lane's foot; largest depth of the foot below the ground at a landing
     S er = zero, efirst = S(-1.0), nearly = zero, nerel = zero, nheld = zero, mpen = S(-HUGE_VAL);
     if constexpr (D::TER) { const WbsTerArgs ta = *wbs_ter_fresh(dist.te); if (ta.E != nullptr) er = Q::ld(ta.E, g * 4, 1); }
+    // (friction only) the lane's friction column (the slots of WbsFricIO): of the lane's foot - in the sliding set, 0 / 1; joined it in this substep; the
+    // lagged normal force; the direction of a fresh foot's friction; first control step with an onset (the quad's, replicated); onsets, sliding (foot,
+    // substep) pairs and re-sticks; largest sliding speed; path.  On the device it LIVES in the lane's column of the parked block, behind the terrain's
+    // values, and every use reads or writes it there: carried in registers, its eleven doubles spilled at the feedback's register peak.
+#ifdef HS_HOST_EMU
+    S fcol[D::FRIC ? (int)FRIC_SLOTS : 1];
+    WbsFricIO<S> fcell; fcell.col = fcol; fcell.stride = 1;
+#else
+    WbsFricIO<S> fcell; fcell.col = stash + threadIdx.x + 64 * ((D::MC ? SIM_PARK_MC : SIM_PARK) + SIM_GRF_PARK + SIM_SUB_PARK + SIM_UNI_PARK + SIM_TER_PARK); fcell.stride = 64;
+#endif
+    auto fs = [&](int i) -> S& { return wbs_fric_slot(&fcell, i); };
+    if constexpr (D::FRIC) {
+        const WbsFricArgs fa = *wbs_fric_fresh(dist.fc);
+        _Pragma("unroll") for (int i = 0; i < FRIC_SLOTS; i++) fs(i) = zero;
+        fs(FRIC_FIRST) = S(-1.0);
+        if (fa.Sl != nullptr) { fs(FRIC_SL) = Q::ld(fa.Sl, g * 4, 1); fs(FRIC_NF) = Q::ld(fa.NF, g * 4, 1); }
+    }
     // deviation of the state from row `kx` of a phase's Xbar: base part replicated, the lane's leg
     auto deviation = [&](PhaseC& P, size_t kx, S (&eb)[6], S (&wb)[6], S (&el)[3], S (&wl)[3]) {
         _Pragma("unroll") for (int i = 0; i < 6; i++) { eb[i] = qb[i] - Q::ld(P.Xbar, kx + i, 0); wb[i] = vb[i] - Q::ld(P.Xbar, kx + 18 + i, 0); }
@@ -645,6 +746,7 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
         constexpr int U0 = G0 + (D::GRF ? SIM_GRF_PARK : 0);    // (substeps) the torques behind those
         constexpr int N0 = U0 + (D::SUB ? SIM_SUB_PARK : 0);    // (unilateral contact) F, T, the counters and max_lift behind those
         constexpr int T0 = N0 + (D::UNI ? SIM_UNI_PARK : 0);    // (terrain) E, its counters and max_pen behind those
+        // (friction: the SIM_FRIC_PARK doubles behind those are never in registers across a step, see fcell above)
         if (out) {
             _Pragma("unroll") for (int i = 0; i < 24; i++) c[64 * i] = *v[i]; if constexpr (D::MC) { c[64 * 24] = nsat; c[64 * 25] = ffall; }
             if constexpr (D::GRF) { c[64 * G0] = gfmin; c[64 * (G0 + 1)] = gcmin; c[64 * (G0 + 2)] = gfmax; c[64 * (G0 + 3)] = gfirst; c[64 * (G0 + 4)] = gslip; }
@@ -766,13 +868,18 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
             auto flag = [](int m) { return Q::legc((m & 1) ? 1.0 : 0.0, (m & 2) ? 1.0 : 0.0, (m & 4) ? 1.0 : 0.0, (m & 8) ? 1.0 : 0.0); };      // the lane's bit of a wave-uniform mask, formed at every use
             fr = Q::sel(Q::gt(alive, S(0.5)), fr * flag(cm_dyn), fr);      // F <- F n C: does something at a phase change only
             if constexpr (D::TER) er = Q::sel(Q::gt(alive, S(0.5)), er * (one - flag(cm_dyn)), er);      // E <- E \ C: such a foot is an ordinary attached stance foot now
+            if constexpr (D::FRIC) fs(FRIC_SL) = Q::sel(Q::gt(alive, S(0.5)), fs(FRIC_SL) * (flag(cm_dyn) * (one - fr) + (one - flag(cm_dyn)) * er), fs(FRIC_SL));      // Sl <- Sl n A: a foot that left the stance set leaves Sl
             int sub = 0, stg = 0;
             _Pragma("nounroll")
             for (;;) {
                 const int mode = (stg == 1 || stg == 3) ? 1 : 0;
-                typename wbs_io_sel<D::PLANT != 0, D::TER != 0, S>::type io;
+                typename wbs_io_pick<D::FRIC != 0, D::PLANT != 0, D::TER != 0, S>::type io;
                 io.cl = stg == 1 ? tl : stg == 3 ? flag(cm_td) : flag(cm_dyn) * (one - fr);
                 if constexpr (D::TER) { if (mode == 0) io.cl = io.cl + (one - flag(cm_dyn)) * er; }      // A = (C \ F) u E
+                if constexpr (D::FRIC) {      // the lane's friction column, read by the solve where it needs it, and the sample's row of the table
+                    const WbsFricArgs fa = *wbs_fric_fresh(dist.fc);
+                    io.col = fcell.col; io.stride = fcell.stride; io.mur = fa.mu + 2 * (size_t)fa.mu_of[g]; io.vstick = fa.v_stick;
+                }
                 S ob[6]; V3<S> ol;
                 if constexpr (D::PLANT) {      // the quad's row: inertias for the solve, gain and friction on the torque it is given
                     const WbsPlantArgs pa = *wbs_plant_fresh(dist.pl);
@@ -822,6 +929,11 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                     }
                     if (wbs_any(Q::sum(tl))) { stg = 1; continue; }
                 }
+                if constexpr (D::FRIC) {      // a sliding foot the solve found at rest was held with three rows: it leaves Sl (a repeat of the solve sees a sticking foot).
+                                              // Behind the landing test: a solve whose wave goes on to a landing impact decides nothing
+                    const S rs = alive * att * fs(FRIC_SL) * (one - fs(FRIC_EFF));
+                    fs(FRIC_SL) = fs(FRIC_SL) - rs; fs(FRIC_NRESTICK) = fs(FRIC_NRESTICK) + rs;
+                }
                 {   // lift-off test: the attached foot with the smallest normal force, lowest leg on a tie, if that force is below fz_rel
                     const S lz = Q::sel(Q::gt(att, S(0.5)), io.lam.z, S(HUGE_VAL)), mz = Q::vmin(lz);
                     const S need = alive * Q::sel(Q::gt(S(ua.fz_rel), mz), one, zero);
@@ -833,6 +945,7 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                             const S rs = rel * flag(cm_dyn), re = rel - rs;
                             fr = fr + rs; nrel = nrel + rs; er = er - re; nerel = nerel + re;
                             ufirst = Q::sel(Q::gt(Q::sum(rs) * Q::sel(Q::gt(zero, ufirst), one, zero), S(0.5)), S((double)s), ufirst);
+                            if constexpr (D::FRIC) { fs(FRIC_SL) = fs(FRIC_SL) * (one - rel); fs(FRIC_FRESH) = fs(FRIC_FRESH) * (one - rel); }      // a released foot leaves Sl
                         } else {
                         fr = fr + rel; nrel = nrel + rel;
                         ufirst = Q::sel(Q::gt(need * Q::sel(Q::gt(zero, ufirst), one, zero), S(0.5)), S((double)s), ufirst);
@@ -841,15 +954,49 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
                         continue;
                     }
                 }
+                if constexpr (D::FRIC) {      // onset test, reached only when no quad of the wave released a foot: the sticking attached foot with the smallest cone margin
+                    const WbsFricArgs fa = *wbs_fric_fresh(dist.fc);
+                    const S mus = S(fa.mu[2 * (size_t)fa.mu_of[g]]);
+                    const S stick = att * (one - fs(FRIC_SL));
+                    const S lt = wbs_sqrt(io.lam.x * io.lam.x + io.lam.y * io.lam.y);
+                    const S mf = Q::sel(Q::gt(stick, S(0.5)), mus * io.lam.z - lt, S(HUGE_VAL)), mm = Q::vmin(mf);
+                    const S ons = alive * Q::sel(Q::gt(zero, mm), one, zero);
+                    if (wbs_any(ons)) {
+                        const S lane = Q::legc(0.0, 1.0, 2.0, 3.0);
+                        const S pick = Q::vmin(Q::sel(Q::gt(mf, mm), S(4.0), lane));
+                        const typename Q::B join = Q::gt(ons * Q::sel(Q::gt(wbs_abs<Q, S>(lane - pick), S(0.5)), zero, one), S(0.5));
+                        const typename Q::B pull = Q::gt(lt, zero);      // (lambda_t = 0: the foot leaves the cone through its tip and has no direction)
+                        const S rl = Q::rcp(lt);
+                        fs(FRIC_SL) = Q::sel(join, one, fs(FRIC_SL)); fs(FRIC_FRESH) = Q::sel(join, one, fs(FRIC_FRESH)); fs(FRIC_NF) = Q::sel(join, wbs_max<Q, S>(io.lam.z, zero), fs(FRIC_NF));
+                        fs(FRIC_TX) = Q::sel(join, Q::sel(pull, io.lam.x * rl, zero), fs(FRIC_TX)); fs(FRIC_TY) = Q::sel(join, Q::sel(pull, io.lam.y * rl, zero), fs(FRIC_TY));
+                        fs(FRIC_NONSET) = fs(FRIC_NONSET) + Q::sel(join, one, zero);
+                        fs(FRIC_FIRST) = Q::sel(Q::gt(ons * Q::sel(Q::gt(zero, fs(FRIC_FIRST)), one, zero), S(0.5)), S((double)s), fs(FRIC_FIRST));
+                        stg = 2;
+                        continue;
+                    }
+                }
                 {   // ---- the last solve of the substep.  Records as below, over the ATTACHED feet; a free foot's force is exactly zero
                     const WbsGrfArgs ga = *wbs_grf_fresh(dist.gr);
                     const typename Q::B isa = Q::gt(att, S(0.5));
-                    const V3<S> lam = {Q::sel(isa, io.lam.x, zero), Q::sel(isa, io.lam.y, zero), Q::sel(isa, io.lam.z, zero)};
+                    V3<S> lam_ = {Q::sel(isa, io.lam.x, zero), Q::sel(isa, io.lam.y, zero), Q::sel(isa, io.lam.z, zero)};
+                    S cfl = alive * att;      // the feet whose cone margin counts: with friction the STICKING attached feet
+                    if constexpr (D::FRIC) {      // a sliding foot's force is (f_t, lambda_z); end of the substep: n_f, the fresh flags and the row's running values
+                        const S sl = fs(FRIC_SL);
+                        const typename Q::B isl = Q::gt(alive * att * sl, S(0.5));
+                        lam_.x = Q::sel(Q::gt(att * sl, S(0.5)), fs(FRIC_FX), lam_.x); lam_.y = Q::sel(Q::gt(att * sl, S(0.5)), fs(FRIC_FY), lam_.y);
+                        cfl = alive * att * (one - sl);
+                        const S wx = fs(FRIC_WX), wy = fs(FRIC_WY), wt = wbs_sqrt(wx * wx + wy * wy);
+                        const double hs_ = dt / (double)wbs_uniform(wbs_sub_fresh(dist.sb)->substeps);
+                        fs(FRIC_NF) = Q::sel(isl, wbs_max<Q, S>(io.lam.z, zero), fs(FRIC_NF));
+                        fs(FRIC_FRESH) = Q::sel(Q::gt(alive, S(0.5)), zero, fs(FRIC_FRESH));
+                        fs(FRIC_NSLIDE) = fs(FRIC_NSLIDE) + Q::sel(isl, one, zero); fs(FRIC_DIST) = fs(FRIC_DIST) + Q::sel(isl, wt * hs_, zero); fs(FRIC_VMAX) = Q::sel(isl, wbs_max<Q, S>(fs(FRIC_VMAX), wt), fs(FRIC_VMAX));
+                    }
+                    const V3<S> lam = lam_;
                     const typename Q::B on = Q::gt(alive * att, S(0.5));
                     const S cone = ga.mu * lam.z - wbs_max<Q, S>(wbs_abs<Q, S>(lam.x), wbs_abs<Q, S>(lam.y));
                     const S bad = wbs_max<Q, S>(Q::sel(Q::gt(S(ga.fz_min), lam.z), one, zero), Q::sel(Q::gt(zero, cone), one, zero));
-                    const typename Q::B slip = Q::gt(alive * att * bad, S(0.5));
-                    gfmin = Q::sel(on, Q::min(gfmin, lam.z), gfmin); gcmin = Q::sel(on, Q::min(gcmin, cone), gcmin); gfmax = Q::sel(on, wbs_max<Q, S>(gfmax, lam.z), gfmax);
+                    const typename Q::B slip = Q::gt(cfl * bad, S(0.5));
+                    gfmin = Q::sel(on, Q::min(gfmin, lam.z), gfmin); gcmin = Q::sel(Q::gt(cfl, S(0.5)), Q::min(gcmin, cone), gcmin); gfmax = Q::sel(on, wbs_max<Q, S>(gfmax, lam.z), gfmax);
                     gfirst = Q::sel(slip, Q::min(gfirst, S((double)s)), gfirst); gslip = gslip + Q::sel(slip, one, zero);
                     nfree = nfree + alive * fr;
                     if constexpr (D::TER) nheld = nheld + alive * er;
@@ -972,6 +1119,13 @@ HD void wbs_walk(PhaseC* ph, const ModelDev& md, const int* map, int n_steps, in
             Q::st0(ta.rows, g * SIM_TER_ROW + 5, Q::sel(Q::gt(S(-1e300), deep), zero, deep));
             if (ta.E != nullptr && (ua.hold == nullptr || ua.hold[g * (size_t)ua.hold_stride] == 0)) Q::st(ta.E, g * 4, 1, er);
         }
+        if constexpr (D::FRIC) {      // the friction row; Sl and n_f back to where they came from under the same hold
+            const WbsFricArgs fa = *wbs_fric_fresh(dist.fc);
+            Q::st0(fa.rows, g * SIM_FRIC_ROW, fs(FRIC_FIRST)); Q::st0(fa.rows, g * SIM_FRIC_ROW + 1, Q::sum(fs(FRIC_NONSET))); Q::st0(fa.rows, g * SIM_FRIC_ROW + 2, Q::sum(fs(FRIC_NSLIDE)));
+            Q::st0(fa.rows, g * SIM_FRIC_ROW + 3, Q::sum(fs(FRIC_NRESTICK))); Q::st0(fa.rows, g * SIM_FRIC_ROW + 4, Q::sum(fs(FRIC_SL) * Q::legc(1.0, 2.0, 4.0, 8.0)));
+            Q::st0(fa.rows, g * SIM_FRIC_ROW + 5, wbs_qmax<Q, S>(fs(FRIC_VMAX))); Q::st0(fa.rows, g * SIM_FRIC_ROW + 6, Q::sum(fs(FRIC_DIST)));
+            if (fa.Sl != nullptr && (ua.hold == nullptr || ua.hold[g * (size_t)ua.hold_stride] == 0)) { Q::st(fa.Sl, g * 4, 1, fs(FRIC_SL)); Q::st(fa.NF, g * 4, 1, fs(FRIC_NF)); }
+        }
     }
     if (trajX != nullptr) store_state((g * (size_t)(n_steps + 1) + n_steps) * 36);
     _Pragma("unroll") for (int i = 0; i < 6; i++) { Q::st0(xfinal, g * 36 + i, qb[i]); Q::st0(xfinal, g * 36 + 18 + i, vb[i]); }
@@ -1026,6 +1180,7 @@ struct WbsLaunch {
     const PhaseDev* ph; const ModelDev* md; const int* map; int n_steps, n_samples, total; const double* x0; double *xfinal, *rows, *trajX, *trajU;
     SimPick pick;
     const WbsMcArgs* mc; const WbsGrfArgs* gr; const WbsSubArgs* sb; const WbsUniArgs* un; const WbsTerArgs* te; const WbsPlantArgs* pl;
+    const WbsFricArgs* fc = nullptr;      // (hsddp_friction.h) read by the friction family alone
 };
 template <class K, class... A> void wbs_launch(const WbsLaunch& L, K kernel, A... policy_args) {
     hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(64), 0, L.stream, L.ph, *L.md, L.map, L.n_steps, L.n_samples, L.total, L.x0, L.xfinal, L.rows, L.trajX, L.trajU, policy_args...);
@@ -1037,6 +1192,7 @@ void wbs_sub_launch(const WbsLaunch& L);        // hsddp_sub.hip
 void wbs_uni_launch(const WbsLaunch& L);        // hsddp_uni.hip
 void wbs_ter_launch(const WbsLaunch& L);        // hsddp_ter.hip
 void wbs_plant_launch(const WbsLaunch& L);      // hsddp_plant.hip
+void wbs_fric_launch(const WbsLaunch& L);       // hsddp_fric.hip
 void wbs_plant_impact_launch(hipStream_t stream, unsigned grid, const PhaseDev* ph, const ModelDev& md, int pi, int total, const int* frozen, int stride, double* state, double* x0,
                              const WbsPlantArgs* pl);
 

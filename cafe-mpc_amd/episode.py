@@ -235,6 +235,32 @@ class Episode:
         if rc != 0:
             raise RuntimeError(f"hsddp_terrain_set failed rc={rc}")
 
+    def set_friction(self, friction, on=True):
+        """Coulomb friction (include/hsddp_friction.h) for every later tick with the contact rule on; `friction`: a sim.Friction whose mu_of, if
+        given, is int [batch] or [batch, 1].  The sliding feet of a robot and their lagged normal forces are carried from tick to tick and cleared by
+        reset.  on = False: every attached foot is held with three rows again.  A tick with friction and a plant both on raises (HSDDP_ENOTSUP)."""
+        lib = _abi.bind_friction(self.lib)
+        if not on:
+            rc = lib.hsddp_friction_set(self.lib.hsddp_episode_sim(self.e), 0, None, None, None)
+        else:
+            mu = friction.table()
+            mo = None if friction.mu_of is None else np.ascontiguousarray(friction.mu_of, dtype=np.int32).reshape(-1)
+            if mo is not None and mo.shape != (self.solver.batch,):
+                raise ValueError(f"Friction.mu_of has {mo.size} entries, not {self.solver.batch}")
+            f = _abi.FrictionParams(friction.v_stick, mu.shape[0], 0)
+            rc = lib.hsddp_friction_set(self.lib.hsddp_episode_sim(self.e), 1, C.byref(f), mu.ctypes.data, None if mo is None else mo.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_friction_set failed rc={rc}")
+
+    def friction_rows(self, b0=0, nb=None):
+        """Structured array [nb] of hsddp_friction_row_t of the last tick, which has to be one with the contact rule and friction on."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0),), dtype=_abi.FRICTION_ROW_DTYPE)
+        rc = _abi.bind_friction(self.lib).hsddp_friction_get(self.lib.hsddp_episode_sim(self.e), b0, nb, rows.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_friction_get failed rc={rc}")
+        return rows
+
     def set_plant(self, plant, on=True):
         """A plant row per robot for every later tick (include/hsddp_plant.h); `plant`: a sim.Plant whose plant_of, if given, is int [batch] or
         [batch, 1].  Each robot keeps its plant for the whole episode: the table survives reconfigure and reset, and the reset map that is pending
@@ -351,12 +377,13 @@ class Episode:
         return t.value, a.value, i.value
 
 
-def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None):
+def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None, friction=None):
     """The receding-horizon loop of MHPCLocomotion::update with the SIMULATED state fed back, for the whole batch.  solver: solved for the window
     `phases` of pd (builder.MHPCProblemData).  Per tick: episode.advance, pd.update(), builder.shift_solver_in_place, hook(tick, phases) - the
     place for solver.set_references - and solver.solve(opt_rt).  kicks: {tick: (kick_step, [B, 36])}.  episode: an Episode already reset; None
     creates one (n_exec = dt_mpc / dt_wb, max_ticks = n_ticks) and resets it to the solver's Xbar[0].  delay: None leaves the episode as it is; an int
-    or int [B] is Episode.set_latency before the first tick (include/hsddp_latency.h: the loop moves the window by n_exec knots a tick, as that needs).  Returns a dict: episode, phases (the last
+    or int [B] is Episode.set_latency before the first tick (include/hsddp_latency.h: the loop moves the window by n_exec knots a tick, as that needs).
+    friction: None leaves the episode as it is; a sim.Friction is Episode.set_friction before the first tick (it acts while the contact rule is on).  Returns a dict: episode, phases (the last
     window), n_iters / n_ls_iters / n_reg_iters / cost [n_ticks, B], alive [n_ticks]."""
     from . import builder
     if episode is None:
@@ -364,6 +391,8 @@ def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=No
         episode.reset(np.ascontiguousarray(solver.field(0, "XBAR")[:, 0]))
     if delay is not None:
         episode.set_latency(delay)
+    if friction is not None:
+        episode.set_friction(friction)
     out = dict(n_iters=[], n_ls_iters=[], n_reg_iters=[], cost=[], alive=[])
     for t in range(n_ticks):
         d, k = dist, None

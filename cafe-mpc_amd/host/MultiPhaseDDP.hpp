@@ -24,6 +24,7 @@
 #include "hsddp_substep.h"
 #include "hsddp_contact.h"
 #include "hsddp_terrain.h"
+#include "hsddp_friction.h"
 #include "hsddp_plant.h"
 #include "hsddp_episode.h"
 #include "hsddp_latency.h"
@@ -81,6 +82,10 @@ public:
     // terrain height maps and early swing-foot touchdown for every later run with the contact rule on (include/hsddp_terrain.h): H [n_maps][ny][nx] and
     // map_of [batch][n_samples] (or null: map 0) are host arrays, copied by the call; on = false ignores the rest
     bool set_terrain(bool on, const hsddp_terrain_t* t = nullptr, const double* H = nullptr, const int* map_of = nullptr) { rc_ = s_ ? hsddp_terrain_set(s_, on ? 1 : 0, t, H, map_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // Coulomb friction for every later run with the contact rule on (include/hsddp_friction.h): mu [n_mu][2] rows (mu_s, mu_k), mu_of [batch][n_samples]
+    // or null; rows of the last run, which has to be one with the contact rule and friction on: batch x n_samples
+    bool set_friction(bool on, const hsddp_friction_t* f = nullptr, const double* mu = nullptr, const int* mu_of = nullptr) { rc_ = s_ ? hsddp_friction_set(s_, on ? 1 : 0, f, mu, mu_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    bool friction(hsddp_friction_row_t* rows) { rc_ = s_ ? hsddp_friction_get(s_, 0, batch_, rows) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // rows of the last run, which has to be one with the contact rule and the terrain on: batch x n_samples
     bool terrain(hsddp_terrain_row_t* rows) { rc_ = s_ ? hsddp_terrain_get(s_, 0, batch_, rows) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // a plant row per sample for every later run (include/hsddp_plant.h): P [n_plants][HSDDP_PLANT_ROW] and plant_of [batch][n_samples] (or null: row 0)
@@ -145,6 +150,14 @@ public:
     bool set_substeps(int substeps) { rc_ = e_ ? hsddp_substep_set(hsddp_episode_sim(e_), substeps) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // unilateral ground contact for every later tick; the free feet are carried from tick to tick (include/hsddp_contact.h)
     bool set_contact(bool on, double fz_rel = 0.0, double z_ground = 0.0) { rc_ = e_ ? hsddp_contact_set(hsddp_episode_sim(e_), on ? 1 : 0, fz_rel, z_ground) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // Coulomb friction for every later tick; a robot's sliding feet and their lagged normal forces are carried from tick to tick (include/hsddp_friction.h)
+    bool set_friction(bool on, const hsddp_friction_t* f = nullptr, const double* mu = nullptr, const int* mu_of = nullptr) { rc_ = e_ ? hsddp_friction_set(hsddp_episode_sim(e_), on ? 1 : 0, f, mu, mu_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // the friction rows of the last tick, which has to be one with the contact rule and friction on
+    std::vector<hsddp_friction_row_t> friction() {
+        std::vector<hsddp_friction_row_t> r((size_t)batch_);
+        rc_ = e_ ? hsddp_friction_get(hsddp_episode_sim(e_), 0, batch_, r.data()) : HSDDP_EINVAL;
+        return r;
+    }
     // terrain and early touchdown for every later tick; the swing feet a robot holds are carried from tick to tick (include/hsddp_terrain.h)
     bool set_terrain(bool on, const hsddp_terrain_t* t = nullptr, const double* H = nullptr, const int* map_of = nullptr) { rc_ = e_ ? hsddp_terrain_set(hsddp_episode_sim(e_), on ? 1 : 0, t, H, map_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // a plant row per robot for the whole episode (include/hsddp_plant.h): plant_of [batch] or null

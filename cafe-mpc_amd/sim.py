@@ -74,6 +74,24 @@ class Terrain:
         return _abi.TerrainParams(H.shape[2], H.shape[1], H.shape[0], 1 if self.early else 0, self.x0, self.y0, self.cx, self.cy, self.w_td)
 
 
+class Friction:
+    """The friction table of include/hsddp_friction.h: mu [n_mu, 2] rows (mu_s, mu_k) with 0 <= mu_k <= mu_s - a pair (mu_s, mu_k) is one row, a number
+    mu means (mu, mu) - mu_of int [batch, R] or None (row 0 for every sample), and v_stick (m/s), the speed below which a sliding foot sticks again."""
+
+    def __init__(self, mu, mu_of=None, v_stick=0.01):
+        self.mu, self.mu_of, self.v_stick = mu, mu_of, float(v_stick)
+
+    def table(self):
+        m = np.asarray(self.mu, dtype=np.float64)
+        if m.ndim == 0:
+            m = np.array([[float(m), float(m)]])
+        if m.ndim == 1:
+            m = m[None]
+        if m.ndim != 2 or m.shape[1] != 2:
+            raise ValueError(f"Friction: mu has shape {m.shape}")
+        return np.ascontiguousarray(m)
+
+
 def terrain_height(terrain, p_xy, m=0):
     """Height of map m of `terrain` above z_ground at the points p_xy [..., 2]: the definition of the lookup.  ix = clamp(floor((p_x - x0) / cx), 0,
     nx - 1), iy likewise, H[m, iy, ix]: outside the grid the edge cell holds, and a NaN coordinate reads cell 0 (fmax / fmin drop a NaN).  m: an int
@@ -227,6 +245,7 @@ class Simulation:
         self.contact_on = False
         self.terrain_on = False
         self.plant_on = False
+        self.friction_on = False
         self.solver, self.R, self.n_steps, self.keep_traj = solver, int(n_samples), int(n_steps), bool(keep_traj)
         self.s = C.c_void_p()
         rc = self.lib.hsddp_sim_create(solver.h, self.R, self.n_steps, 1 if keep_traj else 0, C.byref(self.s))
@@ -371,6 +390,44 @@ class Simulation:
             raise RuntimeError(f"hsddp_terrain_get failed rc={rc}")
         return rows
 
+    def set_friction(self, friction):
+        """Coulomb friction (include/hsddp_friction.h) for every later run with the contact rule on; `friction`: a Friction.  The table and the index
+        are copied.  A run with friction and a plant both on raises (HSDDP_ENOTSUP)."""
+        mu = friction.table()
+        mo = None if friction.mu_of is None else np.ascontiguousarray(friction.mu_of, dtype=np.int32)
+        if mo is not None and mo.shape != (self.solver.batch, self.R):
+            raise ValueError(f"Friction.mu_of has shape {mo.shape}, not {(self.solver.batch, self.R)}")
+        f = _abi.FrictionParams(friction.v_stick, mu.shape[0], 0)
+        rc = _abi.bind_friction(self.lib).hsddp_friction_set(self.s, 1, C.byref(f), mu.ctypes.data, None if mo is None else mo.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_friction_set failed rc={rc}")
+        self.friction_on = True
+
+    def clear_friction(self):
+        """Later runs hold every attached foot with three rows again (the kernels without friction)."""
+        rc = _abi.bind_friction(self.lib).hsddp_friction_set(self.s, 0, None, None, None)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_friction_set failed rc={rc}")
+        self.friction_on = False
+
+    @property
+    def friction(self):
+        """(on, dict of v_stick, n_mu) as later runs use them (hsddp_friction_get_params)."""
+        on = C.c_int(); f = _abi.FrictionParams()
+        rc = _abi.bind_friction(self.lib).hsddp_friction_get_params(self.s, C.byref(on), C.byref(f))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_friction_get_params failed rc={rc}")
+        return bool(on.value), dict(v_stick=f.v_stick, n_mu=f.n_mu)
+
+    def friction_rows(self, b0=0, nb=None):
+        """Structured array [nb, R] of hsddp_friction_row_t of the last run, which has to be one with the contact rule and friction on."""
+        nb = self.solver.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0), self.R), dtype=_abi.FRICTION_ROW_DTYPE)
+        rc = _abi.bind_friction(self.lib).hsddp_friction_get(self.s, b0, nb, rows.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_friction_get failed rc={rc}")
+        return rows
+
     def set_plant(self, plant):
         """A plant row per sample for every later run (include/hsddp_plant.h); `plant`: a Plant.  The table and the index are copied."""
         P = plant.table()
@@ -454,12 +511,13 @@ class Simulation:
         return float(ms.value)
 
 
-def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None, plant=None):
+def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None, plant=None, friction=None):
     """One-off simulation on `solver`: dict with rows, x_final and, with keep_traj, X and U (see Simulation); a disturbed run (dist / kick given)
     returns extra too; grf = (mu, fz_min) adds the contact-force records grf and, with keep_traj, Y; substeps = S > 1 integrates every control
     knot in S steps (include/hsddp_substep.h); contact = (fz_rel, z_ground) switches unilateral ground contact on (include/hsddp_contact.h) and
     adds the rows contact; terrain = Terrain(...) beside it switches height maps and early touchdown on (include/hsddp_terrain.h) and adds the rows
-    terrain; plant = Plant(...) gives every sample a plant row (include/hsddp_plant.h)."""
+    terrain; plant = Plant(...) gives every sample a plant row (include/hsddp_plant.h); friction = Friction(...) beside contact lets attached feet slide
+    (include/hsddp_friction.h) and adds the rows friction."""
     sim = Simulation(solver, x0.shape[1], n_steps, keep_traj)
     try:
         if substeps != 1:
@@ -472,6 +530,8 @@ def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=Non
             sim.set_terrain(terrain)
         if plant is not None:
             sim.set_plant(plant)
+        if friction is not None:
+            sim.set_friction(friction)
         sim.run(x0, dist=dist, kick=kick)
         rows, xf = sim.rows()
         out = dict(rows=rows, x_final=xf)
@@ -488,6 +548,8 @@ def simulate(solver, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=Non
             out["contact"] = sim.contact_rows()
         if sim.contact_on and sim.terrain_on:
             out["terrain"] = sim.terrain_rows()
+        if sim.contact_on and sim.friction_on:
+            out["friction"] = sim.friction_rows()
         return out
     finally:
         sim.close()
