@@ -3,11 +3,11 @@ raw-row conversions between the walk's device layout and the ctypes mirrors, and
 (tests/_emu/episode_emu.cpp) behind numpy arguments."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
 import sim_common
+import walk_ref
 from conftest import ROOT
 
 TREE = os.path.join(ROOT, "tests", "golden", "cafe_tree")
@@ -32,10 +32,7 @@ def bound_problem(pkg, n_updates=START_WINDOW):
 
 def build_host(tmpdir, source, name):
     """A host build of a kernel program: tests/_emu/<source> compiled with g++ into tmpdir, as tests/test_sim_host.py compiles sim_emu.cpp."""
-    out = os.path.join(str(tmpdir), name)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cafe-mpc_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "_emu", source), "-o", out])
-    return ctypes.CDLL(out)
+    return walk_ref.build_so(tmpdir, source, name)
 
 
 def build_emu(tmpdir):

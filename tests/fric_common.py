@@ -1,9 +1,9 @@
 """Shared by tests/test_friction_host.py and tests/test_friction_gpu.py: the reference of a closed-loop window with COULOMB FRICTION
 (include/hsddp_friction.h), the host build of the program (tests/_emu/fric_emu.cpp) behind numpy arguments, and the comparison.
 
-Reference: ter_common.oracle_walk_ter extended by the rules of the header, in numpy.  Every solve is fric_ref_dynamics of tests/_emu/fric_ref.cpp - the
+Reference: walk_ref.reference_walk with the contact rule and friction, in numpy.  Every solve is fric_ref_dynamics of tests/_emu/fric_ref.cpp - the
 whole oracle plus wb_forward restated with a row mask per foot and an added foot force, built into a temporary directory with the oracle's flags -
-oracle_wb_foot_kin gives the foot velocities the kinetic direction and the re-stick test read, oracle_wb_impact the landings.  The walk is started from
+oracle_wb_foot_kin gives the foot velocities the kinetic direction and the re-stick test read.  The walk is started from
 given (F, E, Sl, n_f) and returns, beside what oracle_walk_ter returns, the friction rows, (Sl, n_f) at the end, the sliding set of every substep's last
 solve, and the margins of its new decisions.
 
@@ -16,8 +16,6 @@ ONE such sample per case (uni_common.near_samples asserts it on the reference, b
   - re-stick: | |w_t| - v_stick | of every non-fresh sliding foot of every solve, against the trajectory bound (folded into kin_margin).
 The kinetic direction divides by |w_t| > v_stick; the cases use v_stick >= 1e-2 m/s, which keeps a 1e-12 velocity error below the force bound."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
@@ -26,30 +24,18 @@ import mc_common as mc
 import grf_common as gc
 import uni_common as un
 import ter_common as tc
-from conftest import ROOT
+import walk_ref as wr
+from walk_ref import DP, IP
 
-DP = un.DP
-IP = un.IP
-_dp = un._dp
 INTS_F = ("first_slide", "n_onset", "n_slide", "n_restick", "slide_final")
 INTS_C = ("first_release", "n_release", "n_land", "n_free", "free_final")
 
 
 def build_ref(pkg, tmpdir):
     """The oracle with fric_ref_dynamics (tests/_emu/fric_ref.cpp), with the flags of oracle/Makefile."""
-    out = os.path.join(str(tmpdir), "liboracle_fric_ref.so")
-    subprocess.check_call(["g++", "-O3", "-march=native", "-std=c++17", "-fPIC", "-fopenmp", "-ffp-contract=off", "-shared", "-Wno-unused-variable", "-Wno-unused-but-set-variable",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests", "_emu", "fric_ref.cpp"), "-o", out])
-    lib = pkg._abi.bind(C.CDLL(out))
+    lib = pkg._abi.bind(wr.build_so(tmpdir, "fric_ref.cpp", "liboracle_fric_ref.so", wr.ORACLE_FLAGS))
     lib.fric_ref_dynamics.argtypes = [DP, DP, IP, IP, DP, C.c_double, C.c_double, C.c_double, C.c_double, DP, DP, DP]; lib.fric_ref_dynamics.restype = None
     return lib
-
-
-def table_of(fric, shape):
-    """(mu_s, mu_k) of every sample: two arrays [B, R]."""
-    mu = fric.table()
-    mo = np.zeros(shape, dtype=np.int64) if fric.mu_of is None else np.asarray(fric.mu_of).reshape(shape)
-    return mu[mo, 0], mu[mo, 1]
 
 
 def oracle_walk_fric(pkg, ref_lib, phases, policy, smap, x0, S, fz_rel, z_ground, ter, fric, dist=None, kick=None, F0=None, E0=None, Sl0=None, NF0=None):
@@ -57,208 +43,8 @@ def oracle_walk_fric(pkg, ref_lib, phases, policy, smap, x0, S, fz_rel, z_ground
     NF0: None or float [B, R, 4].  Returns the dict of ter_common.oracle_walk_ter plus frows (FRICTION_ROW_DTYPE [B, R]), Sl and NF [B, R, 4] at the end,
     slide [B, R, n, S, 4] (the sliding set of every substep's last solve), onset_margin / which_margin / stick_margin [B, R] (already folded into
     force_margin and kin_margin), and events: per sample a list of (step, substep, kind, leg), kind in onset / kinetic (the solve applied the kinetic force on the foot's non-fresh branch) / restick / release_sliding / phase_in_sl / slide_e (a foot of E in Sl at a substep's end)."""
-    d = dist if dist is not None else pkg.sim.Disturbance()
-    if ter is None:
-        ter = pkg.sim.Terrain(H=np.zeros((1, 1, 1)), early=False)
-    B, R = x0.shape[:2]
-    n = smap.shape[1]
-    H = ter.grid()
-    MUS, MUK = table_of(fric, (B, R))
-    X = np.zeros((B, R, n + 1, 36)); U = np.zeros((B, R, n, 12)); Y = np.zeros((B, R, n, S, 12)); counted = np.zeros((B, R, n, S), dtype=bool)
-    att = np.zeros((B, R, n, S, 4), dtype=bool); slide = np.zeros((B, R, n, S, 4), dtype=bool)
-    first_bad = -np.ones((B, R), dtype=np.int32); first_fall = -np.ones((B, R), dtype=np.int32); n_sat = np.zeros((B, R), dtype=np.int32)
-    sat_margin = np.full((B, R), np.inf); fall_margin = np.full((B, R), np.inf)
-    rows = np.zeros((B, R), dtype=pkg._abi.CONTACT_ROW_DTYPE); rows["first_release"] = -1
-    trows = np.zeros((B, R), dtype=pkg._abi.TERRAIN_ROW_DTYPE); trows["first_early"] = -1
-    frows = np.zeros((B, R), dtype=pkg._abi.FRICTION_ROW_DTYPE); frows["first_slide"] = -1
-    Fend = np.zeros((B, R, 4), dtype=bool); Eend = np.zeros((B, R, 4), dtype=bool); Slend = np.zeros((B, R, 4), dtype=bool); NFend = np.zeros((B, R, 4))
-    solves = np.zeros((B, R), dtype=np.int64)
-    force_margin = np.full((B, R), np.inf); kin_margin = np.full((B, R), np.inf); raw_kin = [np.inf, np.inf]
-    onset_margin = np.full((B, R), np.inf); which_margin = np.full((B, R), np.inf); stick_margin = np.full((B, R), np.inf)
-    events = [[[] for _ in range(R)] for _ in range(B)]
-    D = [p["desc"] for p in phases]
-    contact = [np.array([dd.contact[l] for l in range(4)], dtype=np.int32) for dd in D]
-    nxt = [np.array([dd.next_contact[l] for l in range(4)], dtype=np.int32) for dd in D]
-    noisy = d.sigma_u > 0 or d.sigma_q > 0 or d.sigma_v > 0
-    zero4 = np.zeros(4, dtype=np.int32)
-
-    def foot_kin(x):
-        pos = np.zeros((4, 3)); vel = np.zeros((4, 3)); J = np.zeros((4, 3, 18)); Jv = np.zeros((4, 3, 18))
-        ref_lib.oracle_wb_foot_kin(_dp(x), C.c_double(mc.PSI_DYN), C.c_double(np.pi), _dp(pos), _dp(vel), _dp(J), _dp(Jv))
-        return pos, vel
-    for b in range(B):
-        for r in range(R):
-            x = x0[b, r].astype(np.float64).copy(); alive = True
-            F = np.zeros(4, dtype=bool) if F0 is None else np.array(F0[b, r], dtype=bool)
-            E = np.zeros(4, dtype=bool) if E0 is None else np.array(E0[b, r], dtype=bool)
-            Sl = np.zeros(4, dtype=bool) if Sl0 is None else np.array(Sl0[b, r], dtype=bool)
-            NF = np.zeros(4) if NF0 is None else np.array(NF0[b, r], dtype=np.float64)
-            mus, muk = float(MUS[b, r]), float(MUK[b, r])
-            m = 0 if ter.map_of is None else int(np.asarray(ter.map_of)[b, r])
-            lift = -np.inf; pen = -np.inf; vmax = 0.0; dist_sl = 0.0
-            ev = events[b][r]
-
-            def fall_test(idx):
-                if d.fall_height > 0:
-                    fall_margin[b, r] = min(fall_margin[b, r], abs(x[2] - d.fall_height))
-                    if x[2] < d.fall_height and first_fall[b, r] < 0:
-                        first_fall[b, r] = idx
-            for s in range(n):
-                p, k, reset = (int(v) for v in smap[:, s])
-                if alive and kick is not None and s == d.kick_step:
-                    x = x + kick[b, r]
-                X[b, r, s] = x
-                if alive:
-                    fall_test(s)
-                z = pkg.sim.mc_normals(d.seed, d.first_problem + b, r, s) if noisy else np.zeros(48)
-                e = np.zeros(36)
-                if d.sigma_q > 0:
-                    e[:18] = d.sigma_q * z[12:30]
-                if d.sigma_v > 0:
-                    e[18:] = d.sigma_v * z[30:48]
-                u = policy["UBAR"][p][b, k] + policy["K"][p][b, k] @ ((x + e) - policy["XBAR"][p][b, k])
-                if d.sigma_u > 0:
-                    u = u + d.sigma_u * z[:12]
-                if d.u_max > 0:
-                    if alive:
-                        sat_margin[b, r] = min(sat_margin[b, r], float(np.abs(np.abs(u) - d.u_max).min()))
-                        n_sat[b, r] += int((np.abs(u) > d.u_max).sum())
-                    u = np.clip(u, -d.u_max, d.u_max)
-                U[b, r, s] = u
-                if not alive:
-                    continue
-                u = np.ascontiguousarray(u)
-                Cs = contact[p] > 0
-                F = F & Cs                                   # rule 4: F <- F n C, E <- E \ C, Sl <- Sl n A at a phase change
-                E = E & ~Cs
-                for f in np.flatnonzero(Sl & ((Cs & ~F) | E)):
-                    if k == 0 and s > 0:
-                        ev.append((s, 0, "phase_in_sl", int(f)))
-                Sl = Sl & ((Cs & ~F) | E)
-                h = D[p].dt / S
-
-                def solve(A, Sm, ft):
-                    xn = np.zeros(36); y = np.zeros(12); wt = np.zeros((4, 2))
-                    ref_lib.fric_ref_dynamics(_dp(x), _dp(u), np.ascontiguousarray(A, dtype=np.int32).ctypes.data_as(IP), np.ascontiguousarray(Sm, dtype=np.int32).ctypes.data_as(IP),
-                                              _dp(np.ascontiguousarray(ft)), C.c_double(mc.PSI_DYN), C.c_double(np.pi), C.c_double(D[p].BG_alpha), C.c_double(h), _dp(xn), _dp(y), _dp(wt))
-                    solves[b, r] += 1
-                    return xn, y, wt
-                for j in range(S):
-                    counted[b, r, s, j] = True
-                    fresh = np.zeros(4, dtype=bool); tdir = np.zeros((4, 2))
-                    tested = (F & Cs) | ((~Cs & ~E) if ter.early else np.zeros(4, dtype=bool))
-                    if tested.any():                         # rule 1: landing
-                        pos, vel = foot_kin(x)
-                        zg = z_ground + pkg.sim.terrain_height(ter, pos[:, :2], m)
-                        dz = pos[:, 2] - zg; wz = vel[:, 2]
-                        thr = np.where(Cs, 0.0, -ter.w_td)
-                        if (F & Cs).any():
-                            lift = max(lift, float(dz[F & Cs].max()))
-                        T = tested & (dz <= 0.0) & (wz < thr)
-                        for f in np.flatnonzero(tested):
-                            wv = wz[f] - thr[f]
-                            raw_kin[0] = min(raw_kin[0], abs(dz[f])); raw_kin[1] = min(raw_kin[1], abs(wv))
-                            mg = min(abs(dz[f]), abs(wv)) if T[f] else max(abs(dz[f]) if dz[f] > 0.0 else 0.0, abs(wv) if wv >= 0.0 else 0.0)
-                            kin_margin[b, r] = min(kin_margin[b, r], mg, tc._edge_margin(ter, H, m, pos[f, :2]))
-                        if T.any():
-                            pen = max(pen, float((-dz[T]).max()))
-                            xi = np.zeros(36)
-                            ref_lib.oracle_wb_impact(_dp(x), zero4.ctypes.data_as(IP), T.astype(np.int32).ctypes.data_as(IP), C.c_double(mc.PSI_DYN), C.c_double(np.pi), 1, _dp(xi), None)
-                            x = xi; F = F & ~T; rows["n_land"][b, r] += int((T & Cs).sum())
-                            Te = T & ~Cs
-                            if Te.any():
-                                E = E | Te; trows["n_early"][b, r] += int(Te.sum())
-                                if trows["first_early"][b, r] < 0:
-                                    trows["first_early"][b, r] = s
-                    wtk = foot_kin(x)[1][:, :2] if Sl.any() else np.zeros((4, 2))      # the tangential foot velocities at the state every solve of this substep starts from
-                    while True:
-                        A = (Cs & ~F) | E
-                        ft = np.zeros((4, 2))
-                        for f in np.flatnonzero(Sl):             # the solve's own decisions: kinetic direction or re-stick
-                            if fresh[f]:
-                                ft[f] = muk * NF[f] * tdir[f]
-                                continue
-                            sp = float(np.hypot(wtk[f, 0], wtk[f, 1]))
-                            stick_margin[b, r] = min(stick_margin[b, r], abs(sp - fric.v_stick))
-                            if sp > fric.v_stick:
-                                ft[f] = -muk * NF[f] * wtk[f] / sp
-                                if not ev or ev[-1] != (s, j, "kinetic", int(f)):      # (once per substep: the solve may be repeated)
-                                    ev.append((s, j, "kinetic", int(f)))
-                            else:
-                                Sl = Sl.copy(); Sl[f] = False
-                                frows["n_restick"][b, r] += 1; ev.append((s, j, "restick", int(f)))
-                        xn, y, wt = solve(A, Sl, ft)
-                        lam = y.reshape(4, 3)
-                        lz = lam[:, 2]
-                        if A.any():
-                            force_margin[b, r] = min(force_margin[b, r], float(np.abs(lz[A] - fz_rel).min()))
-                        if A.any() and lz[A].min() < fz_rel:     # rule 2: lift-off, first
-                            cand = np.where(A, lz, np.inf)
-                            f = int(np.argmin(cand))                 # (the lowest leg index on a tie)
-                            if A.sum() > 1:
-                                force_margin[b, r] = min(force_margin[b, r], float(np.sort(cand)[1] - cand[f]))
-                            if Sl[f]:
-                                ev.append((s, j, "release_sliding", f)); Sl = Sl.copy(); Sl[f] = False
-                            if Cs[f]:
-                                F = F.copy(); F[f] = True
-                                rows["n_release"][b, r] += 1
-                                if rows["first_release"][b, r] < 0:
-                                    rows["first_release"][b, r] = s
-                            else:
-                                E = E.copy(); E[f] = False
-                                trows["n_early_release"][b, r] += 1
-                            continue
-                        stick = A & ~Sl                          # rule 2b: onset
-                        if stick.any():
-                            lt = np.hypot(lam[:, 0], lam[:, 1])
-                            mf = np.where(stick, mus * lz - lt, np.inf)
-                            onset_margin[b, r] = min(onset_margin[b, r], float(np.abs(mf[stick]).min()))
-                            if mf.min() < 0.0:
-                                f = int(np.argmin(mf))
-                                if stick.sum() > 1:
-                                    which_margin[b, r] = min(which_margin[b, r], float(np.sort(mf)[1] - mf[f]))
-                                Sl = Sl.copy(); Sl[f] = True; fresh[f] = True
-                                NF[f] = max(lz[f], 0.0); tdir[f] = lam[f, :2] / lt[f] if lt[f] > 0.0 else 0.0
-                                frows["n_onset"][b, r] += 1; ev.append((s, j, "onset", f))
-                                if frows["first_slide"][b, r] < 0:
-                                    frows["first_slide"][b, r] = s
-                                continue
-                        break
-                    yy = y.copy().reshape(4, 3)
-                    for f in np.flatnonzero(Sl):                 # end of the substep: a sliding foot's force is (f_t, lambda_z); n_f; the row's running values
-                        yy[f, :2] = ft[f]
-                        NF[f] = max(lz[f], 0.0)
-                        sp = float(np.hypot(wt[f, 0], wt[f, 1]))
-                        dist_sl += sp * h; vmax = max(vmax, sp)
-                    frows["n_slide"][b, r] += int(Sl.sum())
-                    for f in np.flatnonzero(Sl & ~Cs):
-                        ev.append((s, j, "slide_e", int(f)))
-                    Y[b, r, s, j] = yy.ravel(); att[b, r, s, j] = A; slide[b, r, s, j] = Sl
-                    rows["n_free"][b, r] += int((F & Cs).sum()); trows["n_held"][b, r] += int(E.sum())
-                    nsq = float(xn @ xn)
-                    if not (nsq <= 1e12):      # rule 3: the state the failing step was taken from is kept, nothing further is counted
-                        first_bad[b, r] = s; alive = False
-                        break
-                    x = xn
-                if alive and reset:
-                    xi = np.zeros(36)
-                    ref_lib.oracle_wb_impact(_dp(x), contact[p].ctypes.data_as(IP), nxt[p].ctypes.data_as(IP), C.c_double(mc.PSI_DYN), C.c_double(np.pi), 1, _dp(xi), None)
-                    x = xi
-            X[b, r, n] = x
-            if alive:
-                fall_test(n)
-            Fend[b, r] = F; Eend[b, r] = E; Slend[b, r] = Sl; NFend[b, r] = NF
-            bits = lambda v: int(sum(1 << l for l in range(4) if v[l]))
-            rows["free_final"][b, r] = bits(F); rows["max_lift"][b, r] = lift if np.isfinite(lift) else 0.0
-            trows["early_final"][b, r] = bits(E); trows["max_pen"][b, r] = pen if np.isfinite(pen) else 0.0
-            frows["slide_final"][b, r] = bits(Sl); frows["max_speed"][b, r] = vmax; frows["distance"][b, r] = dist_sl
-    force_margin = np.minimum(force_margin, np.minimum(onset_margin, which_margin))
-    kin_margin = np.minimum(kin_margin, stick_margin)
-    for a in (X, U, Y, counted, att, slide):
-        a.setflags(write=False)
-    return dict(X=X, U=U, Y=Y, counted=counted, att=att, first_bad=first_bad, first_fall=first_fall, n_sat=n_sat, sat_margin=sat_margin, fall_margin=fall_margin,
-                rows=rows, F=Fend, solves=solves, force_margin=force_margin, kin_margin=kin_margin, raw_kin=tuple(raw_kin), trows=trows, E=Eend,
-                frows=frows, Sl=Slend, NF=NFend, slide=slide, onset_margin=onset_margin, which_margin=which_margin, stick_margin=stick_margin, events=events)
+    w = wr.reference_walk(pkg, ref_lib, phases, policy, smap, x0, S, contact=(fz_rel, z_ground), ter=ter, fric=fric, dist=dist, kick=kick, F0=F0, E0=E0, Sl0=Sl0, NF0=NF0)
+    return wr.pick(w, wr.KEYS_FRIC)
 
 
 def grf_rows_fric(pkg, ref, mu, fz_min):
@@ -333,10 +119,7 @@ def compare_case(tag, pkg, res, ref, xbar, mu=0.0, fz_min=0.0, fz_rel=None):
 # ---- the host build of the program
 
 def build_emu(tmpdir):
-    out = os.path.join(str(tmpdir), "libhsddp_fric_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cafe-mpc_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "_emu", "fric_emu.cpp"), "-o", out])
-    lib = C.CDLL(out)
+    lib = wr.build_so(tmpdir, "fric_emu.cpp", "libhsddp_fric_emu.so")
     assert [lib.fric_emu_park_doubles(m) for m in (0, 1)] == [61, 63]      # the parked column of the three kernels, doubles per lane: 32 256 B at most
     return lib
 
@@ -344,40 +127,20 @@ def build_emu(tmpdir):
 def emu_run(lib, pkg, so, b, x0, smap, S, fz_rel, z_ground, ter, fric, mu_of=None, map_of=None, dist=None, kick=None, mu=0.0, fz_min=0.0, F=None, E=None, Sl=None, NF=None, hold=None, expect=0):
     """The host build on problem b of a solved handle; x0, kick: [R, 36]; ter: sim.Terrain or None; mu_of, map_of: None or int [R]; F, E, Sl, NF: None or
     float [R, 4], updated in place.  Returns raw arrays (expect != 0: the return code the call must give, and None)."""
-    nph, hor, dt, al, ct, td, xb, ub, kk = tc.emu_args(pkg, so, b, x0, smap)
-    ptrs = lambda arrs: (C.c_void_p * nph)(*[a.ctypes.data for a in arrs])
-    n, R = smap.shape[1], x0.shape[0]
-    x0 = np.ascontiguousarray(x0); smap = np.ascontiguousarray(smap, dtype=np.int32)
-    xf = np.zeros((R, 36)); rows = np.zeros((R, 5)); X = np.zeros((R, n + 1, 36)); U = np.zeros((R, n, 12)); extra = np.full((R, 2), np.nan)
-    g = np.full((R, 5), np.nan); Y = np.full((R, n, 12), np.nan); c = np.full((R, 6), np.nan); tr = np.full((R, 6), np.nan); fr = np.full((R, 7), np.nan)
-    use_mc = dist is not None or kick is not None
-    d = dist if dist is not None else pkg.sim.Disturbance()
-    sw = np.array([d.sigma_u, d.sigma_q, d.sigma_v, d.u_max, d.fall_height])
-    kick = None if kick is None else np.ascontiguousarray(kick)
-    hold = None if hold is None else np.ascontiguousarray(hold, dtype=np.int32)
-    mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
+    R = x0.shape[0]
+    args, out, keep = wr.emu_prefix(pkg, so, b, x0, smap, S, dist, kick, mu, fz_min)
+    ctail, out["c"] = wr.emu_contact_args(R, fz_rel, z_ground, F, hold, E, Sl, NF)
+    ttail, out["t"] = wr.emu_terrain_args(R, ter, map_of, E)
     fo = None if mu_of is None else np.ascontiguousarray(mu_of, dtype=np.int32)
-    for a in (F, E, Sl, NF):
-        assert a is None or (a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (R, 4))
-    H = None if ter is None else ter.grid()
-    t = None if ter is None else ter.to_c()
     mu_t = fric.table(); fp = pkg._abi.FrictionParams(fric.v_stick, mu_t.shape[0], 0)
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    rc = lib.fric_emu_run(nph, vp(hor), vp(dt), vp(al), vp(ct), vp(td), ptrs(xb), ptrs(ub), ptrs(kk), C.c_double(mc.PSI_DYN), vp(smap), n, R, vp(x0), vp(xf), vp(rows),
-                          vp(X), vp(U), int(S), 1 if use_mc else 0, C.c_ulonglong(d.seed), d.first_problem + b, vp(sw), d.kick_step, vp(kick), vp(extra),
-                          C.c_double(mu), C.c_double(fz_min), vp(g), vp(Y), C.c_double(fz_rel), C.c_double(z_ground), vp(c), vp(F), vp(hold),
-                          None if t is None else C.byref(t), vp(H), vp(mo), vp(tr), vp(E), C.byref(fp), vp(mu_t), vp(fo), vp(fr), vp(Sl), vp(NF))
+    out["f"] = np.full((R, 7), np.nan)
+    rc = lib.fric_emu_run(*args, *ctail, *ttail, C.byref(fp), wr.vp(mu_t), wr.vp(fo), wr.vp(out["f"]), wr.vp(Sl), wr.vp(NF))
     assert rc == expect, (rc, expect)
-    return None if expect else dict(xf=xf, rows=rows, X=X, U=U, extra=extra, g=g, Y=Y, c=c, t=tr, f=fr)
+    return None if expect else out
 
 
 def friction_rows_of(pkg, raw):
-    assert np.array_equal(raw[..., :5], np.round(raw[..., :5]))      # the counters are whole numbers in doubles
-    out = np.zeros(raw.shape[:-1], dtype=pkg._abi.FRICTION_ROW_DTYPE)
-    for i, f in enumerate(INTS_F):
-        out[f] = raw[..., i]
-    out["max_speed"] = raw[..., 5]; out["distance"] = raw[..., 6]
-    return out
+    return wr.struct_rows(raw, pkg._abi.FRICTION_ROW_DTYPE)
 
 
 def host_run(lib, pkg, so, xs, smap, S, fz_rel, z_ground, ter, fric, d=None, k=None, mu=0.0):

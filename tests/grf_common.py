@@ -13,6 +13,8 @@ bound."""
 import numpy as np
 
 import sim_common as sc
+import walk_ref as wr
+from conftest import pkg
 
 MARGIN_FACTOR = 1000.0
 
@@ -78,31 +80,8 @@ def compare_records(tag, pkg, rows, Y, Yref, contact, mu, fz_min):
 
 
 def oracle_walk_forces(oracle_lib, phases, policy, smap, x0, psi_dyn=3.1415):
-    """The undisturbed window walked knot by knot with the oracle's model probes and the policy rows given as arrays (mc_common.policy_of: read from
-    the handle under test, so the comparison isolates the simulation from the parity of the solve), as mc_common.oracle_walk does, keeping the
-    contact forces the probe returns.  x0: [B, R, 36].  Returns Y [B, R, n, 12]."""
-    import ctypes as C
-    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
-    dp = lambda a: a.ctypes.data_as(DP)
-    B, R = x0.shape[:2]
-    n = smap.shape[1]
-    D = [p["desc"] for p in phases]
-    contact = [np.array([dd.contact[l] for l in range(4)], dtype=np.int32) for dd in D]
-    nxt = [np.array([dd.next_contact[l] for l in range(4)], dtype=np.int32) for dd in D]
-    Y = np.zeros((B, R, n, 12))
-    for b in range(B):
-        for r in range(R):
-            x = x0[b, r].astype(np.float64).copy()
-            for s in range(n):
-                p, k, reset = (int(v) for v in smap[:, s])
-                u = np.ascontiguousarray(policy["UBAR"][p][b, k] + policy["K"][p][b, k] @ (x - policy["XBAR"][p][b, k]))
-                xn = np.zeros(36); y = np.zeros(12)
-                oracle_lib.oracle_wb_dynamics(dp(x), dp(u), contact[p].ctypes.data_as(IP), C.c_double(psi_dyn), C.c_double(np.pi), C.c_double(D[p].BG_alpha),
-                                              C.c_double(D[p].dt), dp(xn), dp(y))
-                Y[b, r, s] = y
-                x = xn
-                if reset:
-                    xi = np.zeros(36)
-                    oracle_lib.oracle_wb_impact(dp(x), contact[p].ctypes.data_as(IP), nxt[p].ctypes.data_as(IP), C.c_double(psi_dyn), C.c_double(np.pi), 1, dp(xi), None)
-                    x = xi
-    return Y
+    """The undisturbed window walked knot by knot (walk_ref.reference_walk, one solve per step, no contact rule) with the policy rows given as arrays
+    (mc_common.policy_of), keeping the contact forces the probe returns.  x0: [B, R, 36].  Returns Y [B, R, n, 12]."""
+    w = wr.reference_walk(pkg, oracle_lib, phases, policy, smap, x0, psi_dyn=psi_dyn)
+    assert (w["first_bad"] < 0).all()
+    return np.ascontiguousarray(w["Y"][..., 0, :])

@@ -1,10 +1,9 @@
 """Shared by tests/test_terrain_host.py and tests/test_terrain_gpu.py: the reference of a closed-loop window with TERRAIN HEIGHT MAPS AND EARLY SWING-FOOT
 TOUCHDOWN (include/hsddp_terrain.h), the host build of the program (tests/_emu/ter_emu.cpp) behind numpy arguments, and the comparison.
 
-Reference: uni_common.oracle_walk_uni extended by the rules of the header, in numpy on the oracle's existing probes only - oracle_wb_foot_kin for
-the landing tests, oracle_wb_dynamics with the contact array set to the attached feet A = (C \\ F) u E, oracle_wb_impact(x, 0, T) for a landing;
-sim.terrain_height is the lookup.  The walk is started from given (F, E) and returns, beside what oracle_walk_uni returns, the terrain rows, E at the
-end, and what the cases assert their non-vacuity on (the raw cell indices and the cells of the tested feet).
+Reference: walk_ref.reference_walk with the contact rule and a terrain, in numpy on the oracle's existing probes only; sim.terrain_height is the
+lookup.  The walk is started from given (F, E) and returns, beside what oracle_walk_uni returns, the terrain rows, E at the end, and what the cases
+assert their non-vacuity on (the raw cell indices and the cells of the tested feet).
 
 Tolerances: the project's own, uni_common's.  Floats 1e-8 x scale (sim_common / grf_common), the integers, free_final and early_final EXACTLY, but
 for a sample whose REFERENCE comes within grf_common.MARGIN_FACTOR x the bound of a decision; at most ONE such sample per case (uni_common.near_samples
@@ -13,193 +12,21 @@ asserts it on the reference).  The decisions and their margins: the two kinds of
   - a swing foot's landing test (p_z <= z_g and w_z < -w_td): true - the smaller of |p_z - z_g| and |w_z + w_td|; false - the larger over the
     conditions that fail;
   - for a tested foot whose neighbouring cell holds a different height: the distance of p_x / p_y to that cell edge."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
 import sim_common as sc
-import mc_common as mc
-import grf_common as gc
-import sub_common as sub
 import uni_common as un
-from conftest import ROOT
+import walk_ref as wr
 
-DP = un.DP
-IP = un.IP
-_dp = un._dp
 INTS_T = ("first_early", "n_early", "n_early_release", "n_held", "early_final")
-
-
-def _edge_margin(ter, H, m, p):
-    """Distance of the point p (x, y) to the nearest cell edge behind which map m holds another height (inf if there is none)."""
-    fx, fy = (p[0] - ter.x0) / ter.cx, (p[1] - ter.y0) / ter.cy
-    ix, iy = np.floor(fx), np.floor(fy)
-    h = lambda i, j: H[m, int(min(max(j, 0), H.shape[1] - 1)), int(min(max(i, 0), H.shape[2] - 1))]      # (outside the grid the edge cell holds)
-    out = np.inf
-    if h(ix - 1, iy) != h(ix, iy):
-        out = min(out, (fx - ix) * ter.cx)
-    if h(ix + 1, iy) != h(ix, iy):
-        out = min(out, (ix + 1 - fx) * ter.cx)
-    if h(ix, iy - 1) != h(ix, iy):
-        out = min(out, (fy - iy) * ter.cy)
-    if h(ix, iy + 1) != h(ix, iy):
-        out = min(out, (iy + 1 - fy) * ter.cy)
-    return out
 
 
 def oracle_walk_ter(pkg, oracle_lib, phases, policy, smap, x0, S, fz_rel, z_ground, ter, dist=None, kick=None, F0=None, E0=None):
     """x0: [B, R, 36]; ter: sim.Terrain (map_of None or [B, R]); F0, E0: None or bool [B, R, 4].  Returns the dict of uni_common.oracle_walk_uni (att
     holds the feet of E too) plus trows (TERRAIN_ROW_DTYPE [B, R]), E [B, R, 4] at the end, raw_ix / raw_iy (smallest and largest raw cell index of a
     tested foot), cells (the set of (m, iy, ix) a tested foot read), pz_final [B, R, 4] (foot heights of the final state), land_z [B, R, 2] (lowest and highest p_z of a foot of a landing set T; NaN: none)."""
-    d = dist if dist is not None else pkg.sim.Disturbance()
-    B, R = x0.shape[:2]
-    n = smap.shape[1]
-    H = ter.grid()
-    X = np.zeros((B, R, n + 1, 36)); U = np.zeros((B, R, n, 12)); Y = np.zeros((B, R, n, S, 12)); counted = np.zeros((B, R, n, S), dtype=bool)
-    att = np.zeros((B, R, n, S, 4), dtype=bool)
-    first_bad = -np.ones((B, R), dtype=np.int32); first_fall = -np.ones((B, R), dtype=np.int32); n_sat = np.zeros((B, R), dtype=np.int32)
-    sat_margin = np.full((B, R), np.inf); fall_margin = np.full((B, R), np.inf)
-    rows = np.zeros((B, R), dtype=pkg._abi.CONTACT_ROW_DTYPE); rows["first_release"] = -1
-    trows = np.zeros((B, R), dtype=pkg._abi.TERRAIN_ROW_DTYPE); trows["first_early"] = -1
-    Fend = np.zeros((B, R, 4), dtype=bool); Eend = np.zeros((B, R, 4), dtype=bool); solves = np.zeros((B, R), dtype=np.int64)
-    force_margin = np.full((B, R), np.inf); kin_margin = np.full((B, R), np.inf); raw_kin = [np.inf, np.inf]
-    raw_ix = [np.inf, -np.inf]; raw_iy = [np.inf, -np.inf]; cells = set(); pz_final = np.zeros((B, R, 4)); land_z = np.full((B, R, 2), np.nan)
-    D = [p["desc"] for p in phases]
-    contact = [np.array([dd.contact[l] for l in range(4)], dtype=np.int32) for dd in D]
-    nxt = [np.array([dd.next_contact[l] for l in range(4)], dtype=np.int32) for dd in D]
-    noisy = d.sigma_u > 0 or d.sigma_q > 0 or d.sigma_v > 0
-    zero4 = np.zeros(4, dtype=np.int32)
-
-    def foot_kin(x):
-        pos = np.zeros((4, 3)); vel = np.zeros((4, 3)); J = np.zeros((4, 3, 18)); Jv = np.zeros((4, 3, 18))
-        oracle_lib.oracle_wb_foot_kin(_dp(x), C.c_double(mc.PSI_DYN), C.c_double(np.pi), _dp(pos), _dp(vel), _dp(J), _dp(Jv))
-        return pos, vel
-    for b in range(B):
-        for r in range(R):
-            x = x0[b, r].astype(np.float64).copy(); alive = True
-            F = np.zeros(4, dtype=bool) if F0 is None else np.array(F0[b, r], dtype=bool)
-            E = np.zeros(4, dtype=bool) if E0 is None else np.array(E0[b, r], dtype=bool)
-            m = 0 if ter.map_of is None else int(np.asarray(ter.map_of)[b, r])
-            lift = -np.inf; pen = -np.inf
-
-            def fall_test(idx):
-                if d.fall_height > 0:
-                    fall_margin[b, r] = min(fall_margin[b, r], abs(x[2] - d.fall_height))
-                    if x[2] < d.fall_height and first_fall[b, r] < 0:
-                        first_fall[b, r] = idx
-            for s in range(n):
-                p, k, reset = (int(v) for v in smap[:, s])
-                if alive and kick is not None and s == d.kick_step:
-                    x = x + kick[b, r]
-                X[b, r, s] = x
-                if alive:
-                    fall_test(s)
-                z = pkg.sim.mc_normals(d.seed, d.first_problem + b, r, s) if noisy else np.zeros(48)
-                e = np.zeros(36)
-                if d.sigma_q > 0:
-                    e[:18] = d.sigma_q * z[12:30]
-                if d.sigma_v > 0:
-                    e[18:] = d.sigma_v * z[30:48]
-                u = policy["UBAR"][p][b, k] + policy["K"][p][b, k] @ ((x + e) - policy["XBAR"][p][b, k])
-                if d.sigma_u > 0:
-                    u = u + d.sigma_u * z[:12]
-                if d.u_max > 0:
-                    if alive:
-                        sat_margin[b, r] = min(sat_margin[b, r], float(np.abs(np.abs(u) - d.u_max).min()))
-                        n_sat[b, r] += int((np.abs(u) > d.u_max).sum())
-                    u = np.clip(u, -d.u_max, d.u_max)
-                U[b, r, s] = u
-                if not alive:
-                    continue
-                u = np.ascontiguousarray(u)
-                Cs = contact[p] > 0
-                F = F & Cs                                   # rule 4: F <- F n C, E <- E \ C at a phase change
-                E = E & ~Cs
-                h = D[p].dt / S
-
-                def solve(A):
-                    xn = np.zeros(36); y = np.zeros(12)
-                    oracle_lib.oracle_wb_dynamics(_dp(x), _dp(u), np.ascontiguousarray(A, dtype=np.int32).ctypes.data_as(IP), C.c_double(mc.PSI_DYN), C.c_double(np.pi),
-                                                  C.c_double(D[p].BG_alpha), C.c_double(h), _dp(xn), _dp(y))
-                    solves[b, r] += 1
-                    return xn, y
-                for j in range(S):
-                    counted[b, r, s, j] = True
-                    tested = (F & Cs) | ((~Cs & ~E) if ter.early else np.zeros(4, dtype=bool))
-                    if tested.any():                         # rule 1: landing
-                        pos, vel = foot_kin(x)
-                        zg = z_ground + pkg.sim.terrain_height(ter, pos[:, :2], m)
-                        dz = pos[:, 2] - zg; wz = vel[:, 2]
-                        thr = np.where(Cs, 0.0, -ter.w_td)
-                        if (F & Cs).any():
-                            lift = max(lift, float(dz[F & Cs].max()))
-                        T = tested & (dz <= 0.0) & (wz < thr)
-                        for f in np.flatnonzero(tested):
-                            wv = wz[f] - thr[f]
-                            raw_kin[0] = min(raw_kin[0], abs(dz[f])); raw_kin[1] = min(raw_kin[1], abs(wv))
-                            mg = min(abs(dz[f]), abs(wv)) if T[f] else max(abs(dz[f]) if dz[f] > 0.0 else 0.0, abs(wv) if wv >= 0.0 else 0.0)
-                            kin_margin[b, r] = min(kin_margin[b, r], mg, _edge_margin(ter, H, m, pos[f, :2]))
-                            ix = np.floor((pos[f, 0] - ter.x0) / ter.cx); iy = np.floor((pos[f, 1] - ter.y0) / ter.cy)
-                            raw_ix[0] = min(raw_ix[0], ix); raw_ix[1] = max(raw_ix[1], ix); raw_iy[0] = min(raw_iy[0], iy); raw_iy[1] = max(raw_iy[1], iy)
-                            cells.add((m, int(np.clip(iy, 0, H.shape[1] - 1)), int(np.clip(ix, 0, H.shape[2] - 1))))
-                        if T.any():
-                            pen = max(pen, float((-dz[T]).max()))
-                            land_z[b, r] = np.nanmin([land_z[b, r, 0], pos[T, 2].min()]), np.nanmax([land_z[b, r, 1], pos[T, 2].max()])
-                            xi = np.zeros(36)
-                            oracle_lib.oracle_wb_impact(_dp(x), zero4.ctypes.data_as(IP), T.astype(np.int32).ctypes.data_as(IP), C.c_double(mc.PSI_DYN), C.c_double(np.pi), 1, _dp(xi), None)
-                            x = xi; F = F & ~T; rows["n_land"][b, r] += int((T & Cs).sum())
-                            Te = T & ~Cs
-                            if Te.any():
-                                E = E | Te; trows["n_early"][b, r] += int(Te.sum())
-                                if trows["first_early"][b, r] < 0:
-                                    trows["first_early"][b, r] = s
-                    while True:                              # rule 2: lift-off
-                        A = (Cs & ~F) | E
-                        xn, y = solve(A)
-                        lz = y.reshape(4, 3)[:, 2]
-                        if A.any():
-                            force_margin[b, r] = min(force_margin[b, r], float(np.abs(lz[A] - fz_rel).min()))
-                        if not A.any() or not (lz[A].min() < fz_rel):
-                            break
-                        cand = np.where(A, lz, np.inf)
-                        f = int(np.argmin(cand))                 # (the lowest leg index on a tie)
-                        if A.sum() > 1:
-                            force_margin[b, r] = min(force_margin[b, r], float(np.sort(cand)[1] - cand[f]))
-                        if Cs[f]:
-                            F = F.copy(); F[f] = True
-                            rows["n_release"][b, r] += 1
-                            if rows["first_release"][b, r] < 0:
-                                rows["first_release"][b, r] = s
-                        else:
-                            E = E.copy(); E[f] = False
-                            trows["n_early_release"][b, r] += 1
-                    Y[b, r, s, j] = y; att[b, r, s, j] = A
-                    rows["n_free"][b, r] += int((F & Cs).sum()); trows["n_held"][b, r] += int(E.sum())
-                    nsq = float(xn @ xn)
-                    if not (nsq <= 1e12):      # rule 3: the state the failing step was taken from is kept, nothing further is counted
-                        first_bad[b, r] = s; alive = False
-                        break
-                    x = xn
-                if alive and reset:
-                    xi = np.zeros(36)
-                    oracle_lib.oracle_wb_impact(_dp(x), contact[p].ctypes.data_as(IP), nxt[p].ctypes.data_as(IP), C.c_double(mc.PSI_DYN), C.c_double(np.pi), 1, _dp(xi), None)
-                    x = xi
-            X[b, r, n] = x
-            if alive:
-                fall_test(n)
-            Fend[b, r] = F; Eend[b, r] = E
-            rows["free_final"][b, r] = int(sum(1 << l for l in range(4) if F[l]))
-            rows["max_lift"][b, r] = lift if np.isfinite(lift) else 0.0
-            trows["early_final"][b, r] = int(sum(1 << l for l in range(4) if E[l]))
-            trows["max_pen"][b, r] = pen if np.isfinite(pen) else 0.0
-            pz_final[b, r] = foot_kin(x)[0][:, 2] if np.isfinite(x).all() else np.nan
-    for a in (X, U, Y, counted, att):
-        a.setflags(write=False)
-    return dict(X=X, U=U, Y=Y, counted=counted, att=att, first_bad=first_bad, first_fall=first_fall, n_sat=n_sat, sat_margin=sat_margin, fall_margin=fall_margin,
-                rows=rows, F=Fend, solves=solves, force_margin=force_margin, kin_margin=kin_margin, raw_kin=tuple(raw_kin),
-                trows=trows, E=Eend, raw_ix=tuple(raw_ix), raw_iy=tuple(raw_iy), cells=cells, pz_final=pz_final, land_z=land_z)
+    w = wr.reference_walk(pkg, oracle_lib, phases, policy, smap, x0, S, contact=(fz_rel, z_ground), ter=ter, dist=dist, kick=kick, F0=F0, E0=E0)
+    return wr.pick(w, wr.KEYS_TER)
 
 
 def report(tag, ref):
@@ -225,61 +52,30 @@ def compare_case(tag, pkg, res, ref, xbar, mu=0.0, fz_min=0.0, fz_rel=None):
 # ---- the host build of the program
 
 def build_emu(tmpdir):
-    out = os.path.join(str(tmpdir), "libhsddp_ter_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cafe-mpc_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "_emu", "ter_emu.cpp"), "-o", out])
-    lib = C.CDLL(out)
+    lib = wr.build_so(tmpdir, "ter_emu.cpp", "libhsddp_ter_emu.so")
     assert [lib.ter_emu_park_doubles(m) for m in (0, 1)] == [45, 47]      # the parked column of the three kernels, doubles per lane: 24 064 B at most
     return lib
 
 
 def emu_args(pkg, so, b, x0, smap):
-    """The leading arguments of ter_emu_run for problem b of a solved handle (kept alive by the caller through the returned list)."""
-    nph = len(so.phases)
-    D = [p["desc"] for p in so.phases]
-    hor = np.array([q.horizon for q in D], dtype=np.int32); dt = np.array([q.dt for q in D]); al = np.array([q.BG_alpha for q in D])
-    ct = np.array([[q.contact[l] for l in range(4)] for q in D], dtype=np.int32)
-    td = np.array([[1 if (q.contact[l] == 0 and q.next_contact[l] == 1) else 0 for l in range(4)] for q in D], dtype=np.int32)
-    xb = [np.ascontiguousarray(so.field(i, "XBAR", b, 1)[0]) for i in range(nph)]
-    ub = [np.ascontiguousarray(so.field(i, "UBAR", b, 1)[0]) for i in range(nph)]
-    kk = [np.ascontiguousarray(so.field(i, "K", b, 1)[0].transpose(0, 2, 1)) for i in range(nph)]
-    return nph, hor, dt, al, ct, td, xb, ub, kk
+    """The policy arguments of the host builds for problem b of a solved handle: walk_ref.policy_arrays."""
+    return wr.policy_arrays(so, b)
 
 
 def emu_run(lib, pkg, so, b, x0, smap, S, fz_rel, z_ground, ter, map_of=None, dist=None, kick=None, mu=0.0, fz_min=0.0, F=None, E=None, hold=None, expect=0):
     """The host build on problem b of a solved handle; x0, kick: [R, 36]; map_of: None or int [R]; F, E: None or float [R, 4], updated in place.
     Returns raw arrays (expect != 0: the return code the call must give, and None)."""
-    nph, hor, dt, al, ct, td, xb, ub, kk = emu_args(pkg, so, b, x0, smap)
-    ptrs = lambda arrs: (C.c_void_p * nph)(*[a.ctypes.data for a in arrs])
-    n, R = smap.shape[1], x0.shape[0]
-    x0 = np.ascontiguousarray(x0); smap = np.ascontiguousarray(smap, dtype=np.int32)
-    xf = np.zeros((R, 36)); rows = np.zeros((R, 5)); X = np.zeros((R, n + 1, 36)); U = np.zeros((R, n, 12)); extra = np.full((R, 2), np.nan)
-    g = np.full((R, 5), np.nan); Y = np.full((R, n, 12), np.nan); c = np.full((R, 6), np.nan); tr = np.full((R, 6), np.nan)
-    use_mc = dist is not None or kick is not None
-    d = dist if dist is not None else pkg.sim.Disturbance()
-    sw = np.array([d.sigma_u, d.sigma_q, d.sigma_v, d.u_max, d.fall_height])
-    kick = None if kick is None else np.ascontiguousarray(kick)
-    hold = None if hold is None else np.ascontiguousarray(hold, dtype=np.int32)
-    mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
-    for a in (F, E):
-        assert a is None or (a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (R, 4))
-    H = ter.grid(); t = ter.to_c()
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    rc = lib.ter_emu_run(nph, vp(hor), vp(dt), vp(al), vp(ct), vp(td), ptrs(xb), ptrs(ub), ptrs(kk), C.c_double(mc.PSI_DYN), vp(smap), n, R, vp(x0), vp(xf), vp(rows),
-                         vp(X), vp(U), int(S), 1 if use_mc else 0, C.c_ulonglong(d.seed), d.first_problem + b, vp(sw), d.kick_step, vp(kick), vp(extra),
-                         C.c_double(mu), C.c_double(fz_min), vp(g), vp(Y), C.c_double(fz_rel), C.c_double(z_ground), vp(c), vp(F), vp(hold),
-                         C.byref(t), vp(H), vp(mo), vp(tr), vp(E))
+    R = x0.shape[0]
+    args, out, keep = wr.emu_prefix(pkg, so, b, x0, smap, S, dist, kick, mu, fz_min)
+    ctail, out["c"] = wr.emu_contact_args(R, fz_rel, z_ground, F, hold, E)
+    ttail, out["t"] = wr.emu_terrain_args(R, ter, map_of, E)
+    rc = lib.ter_emu_run(*args, *ctail, *ttail)
     assert rc == expect, (rc, expect)
-    return None if expect else dict(xf=xf, rows=rows, X=X, U=U, extra=extra, g=g, Y=Y, c=c, t=tr)
+    return None if expect else out
 
 
 def terrain_rows_of(pkg, raw):
-    assert np.array_equal(raw[..., :5], np.round(raw[..., :5]))      # the counters are whole numbers in doubles
-    out = np.zeros(raw.shape[:-1], dtype=pkg._abi.TERRAIN_ROW_DTYPE)
-    for i, f in enumerate(INTS_T):
-        out[f] = raw[..., i]
-    out["max_pen"] = raw[..., 5]
-    return out
+    return wr.struct_rows(raw, pkg._abi.TERRAIN_ROW_DTYPE)
 
 
 def host_run(lib, pkg, so, xs, smap, S, fz_rel, z_ground, ter, d=None, k=None, mu=0.0):

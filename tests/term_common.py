@@ -1,22 +1,18 @@
 """Shared by tests/test_quad_terminal_host.py: the host build of the lane-quad terminal knot (tests/_emu/term_emu.cpp: the lane emulator plus the two
 terminal programs as entry points) behind numpy arguments."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT, pkg
+import walk_ref as wr
+from conftest import pkg
 
 DP = C.POINTER(C.c_double)
 WAVE, QUAD = 0, 1      # program of term_emu_terminal
 
 
 def build_emu(tmpdir):
-    out = os.path.join(str(tmpdir), "libhsddp_term_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cafe-mpc_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "_emu", "term_emu.cpp"), "-o", out])
-    raw = C.CDLL(out)
+    raw = wr.build_so(tmpdir, "term_emu.cpp", "libhsddp_term_emu.so")
     raw.term_emu_terminal.argtypes = [C.c_void_p, C.c_int, DP, C.c_void_p, C.c_int, DP]
     raw.term_emu_records.argtypes = [C.c_void_p, C.c_int, DP]
     raw.term_emu_set_al.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]

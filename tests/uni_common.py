@@ -1,10 +1,9 @@
 """Shared by tests/test_contact_host.py and tests/test_contact_gpu.py: the reference of a closed-loop window with UNILATERAL GROUND CONTACT
 (include/hsddp_contact.h), the host build of the program (tests/_emu/uni_emu.cpp) behind numpy arguments, and the comparison against the reference.
 
-Reference: sub_common.oracle_walk_sub with the four rules of the header, in numpy on the oracle's existing probes only - oracle_wb_foot_kin gives the
-foot positions and velocities of a landing test, oracle_wb_dynamics(x, u, A, ..., dt / S) every solve with the contact array set to the attached feet
-A, oracle_wb_impact(x, cur = 0, nxt = T, ..., 1) a landing.  The walk takes an initial F (episode ticks) and returns the forces and attached sets of
-every substep's LAST solve, the contact rows and, per sample, the MARGIN of its decisions.
+Reference: walk_ref.reference_walk with the contact rule on - the four rules of the header, in numpy on the oracle's existing probes only.  The walk
+takes an initial F (episode ticks) and returns the forces and attached sets of every substep's LAST solve, the contact rows and, per sample, the MARGIN
+of its decisions.
 
 Tolerances.  X, U, x_final, the summaries, the forces and max_lift: sim_common.compare_window / grf_common.force_bound, 1e-8 x scale.  The integers
 and free_final EXACTLY, but for a sample whose reference comes within grf_common.MARGIN_FACTOR x the bound of a decision; at most ONE such sample per
@@ -14,144 +13,22 @@ case is left out (its floats are left out with it: behind a flipped decision the
   - a landing test (p_z <= z_ground and w_z < 0): true - the smaller of |p_z - z_ground| and |w_z|; false - the larger over the conditions that
     fail; against the trajectory bound 1e-8 (metres, metres per second).
 The amplification of a 1e-12 change of x0 through the event-carrying windows is measured by test_contact_host.py and printed."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
 import sim_common as sc
 import mc_common as mc
 import grf_common as gc
-from conftest import ROOT
+import walk_ref as wr
 
-DP = C.POINTER(C.c_double)
-IP = C.POINTER(C.c_int)
 TRAJ_BOUND = sc.RTOL      # positions and velocities of order one
-
-
-def _dp(a):
-    return a.ctypes.data_as(DP)
 
 
 def oracle_walk_uni(pkg, oracle_lib, phases, policy, smap, x0, S, fz_rel, z_ground, dist=None, kick=None, F0=None):
     """x0: [B, R, 36]; F0: None or bool [B, R, 4].  Returns what sub_common.oracle_walk_sub returns - Y [B, R, n, S, 12] of the LAST solve of every
     substep - and att [B, R, n, S, 4] (the set that solve ran on), rows (CONTACT_ROW_DTYPE [B, R]), F [B, R, 4] at the end, solves [B, R] (contact
     solves made), force_margin and kin_margin [B, R] (see the head of the file), raw_kin (smallest |p_z - z_ground|, |w_z| over all tests)."""
-    d = dist if dist is not None else pkg.sim.Disturbance()
-    B, R = x0.shape[:2]
-    n = smap.shape[1]
-    X = np.zeros((B, R, n + 1, 36)); U = np.zeros((B, R, n, 12)); Y = np.zeros((B, R, n, S, 12)); counted = np.zeros((B, R, n, S), dtype=bool)
-    att = np.zeros((B, R, n, S, 4), dtype=bool)
-    first_bad = -np.ones((B, R), dtype=np.int32); first_fall = -np.ones((B, R), dtype=np.int32); n_sat = np.zeros((B, R), dtype=np.int32)
-    sat_margin = np.full((B, R), np.inf); fall_margin = np.full((B, R), np.inf)
-    rows = np.zeros((B, R), dtype=pkg._abi.CONTACT_ROW_DTYPE); rows["first_release"] = -1
-    Fend = np.zeros((B, R, 4), dtype=bool); solves = np.zeros((B, R), dtype=np.int64)
-    force_margin = np.full((B, R), np.inf); kin_margin = np.full((B, R), np.inf); raw_kin = [np.inf, np.inf]
-    D = [p["desc"] for p in phases]
-    contact = [np.array([dd.contact[l] for l in range(4)], dtype=np.int32) for dd in D]
-    nxt = [np.array([dd.next_contact[l] for l in range(4)], dtype=np.int32) for dd in D]
-    noisy = d.sigma_u > 0 or d.sigma_q > 0 or d.sigma_v > 0
-    zero4 = np.zeros(4, dtype=np.int32)
-    for b in range(B):
-        for r in range(R):
-            x = x0[b, r].astype(np.float64).copy(); alive = True
-            F = np.zeros(4, dtype=bool) if F0 is None else np.array(F0[b, r], dtype=bool)
-            lift = -np.inf
-
-            def fall_test(idx):
-                if d.fall_height > 0:
-                    fall_margin[b, r] = min(fall_margin[b, r], abs(x[2] - d.fall_height))
-                    if x[2] < d.fall_height and first_fall[b, r] < 0:
-                        first_fall[b, r] = idx
-            for s in range(n):
-                p, k, reset = (int(v) for v in smap[:, s])
-                if alive and kick is not None and s == d.kick_step:
-                    x = x + kick[b, r]
-                X[b, r, s] = x
-                if alive:
-                    fall_test(s)
-                z = pkg.sim.mc_normals(d.seed, d.first_problem + b, r, s) if noisy else np.zeros(48)
-                e = np.zeros(36)
-                if d.sigma_q > 0:
-                    e[:18] = d.sigma_q * z[12:30]
-                if d.sigma_v > 0:
-                    e[18:] = d.sigma_v * z[30:48]
-                u = policy["UBAR"][p][b, k] + policy["K"][p][b, k] @ ((x + e) - policy["XBAR"][p][b, k])
-                if d.sigma_u > 0:
-                    u = u + d.sigma_u * z[:12]
-                if d.u_max > 0:
-                    if alive:
-                        sat_margin[b, r] = min(sat_margin[b, r], float(np.abs(np.abs(u) - d.u_max).min()))
-                        n_sat[b, r] += int((np.abs(u) > d.u_max).sum())
-                    u = np.clip(u, -d.u_max, d.u_max)
-                U[b, r, s] = u
-                if not alive:
-                    continue
-                u = np.ascontiguousarray(u)
-                Cs = contact[p] > 0
-                F = F & Cs                                   # rule 4: F <- F n C at a phase change
-                h = D[p].dt / S
-
-                def solve(A):
-                    xn = np.zeros(36); y = np.zeros(12)
-                    oracle_lib.oracle_wb_dynamics(_dp(x), _dp(u), np.ascontiguousarray(A, dtype=np.int32).ctypes.data_as(IP), C.c_double(mc.PSI_DYN), C.c_double(np.pi),
-                                                  C.c_double(D[p].BG_alpha), C.c_double(h), _dp(xn), _dp(y))
-                    solves[b, r] += 1
-                    return xn, y
-                for j in range(S):
-                    counted[b, r, s, j] = True
-                    if F.any():                              # rule 1: landing
-                        pos = np.zeros((4, 3)); vel = np.zeros((4, 3)); J = np.zeros((4, 3, 18)); Jv = np.zeros((4, 3, 18))
-                        oracle_lib.oracle_wb_foot_kin(_dp(x), C.c_double(mc.PSI_DYN), C.c_double(np.pi), _dp(pos), _dp(vel), _dp(J), _dp(Jv))
-                        dz = pos[:, 2] - z_ground; wz = vel[:, 2]
-                        lift = max(lift, float(dz[F].max()))
-                        T = F & (dz <= 0.0) & (wz < 0.0)
-                        for f in np.flatnonzero(F):
-                            raw_kin[0] = min(raw_kin[0], abs(dz[f])); raw_kin[1] = min(raw_kin[1], abs(wz[f]))
-                            m = min(abs(dz[f]), abs(wz[f])) if T[f] else max(abs(dz[f]) if dz[f] > 0.0 else 0.0, abs(wz[f]) if wz[f] >= 0.0 else 0.0)
-                            kin_margin[b, r] = min(kin_margin[b, r], m)
-                        if T.any():
-                            xi = np.zeros(36)
-                            oracle_lib.oracle_wb_impact(_dp(x), zero4.ctypes.data_as(IP), T.astype(np.int32).ctypes.data_as(IP), C.c_double(mc.PSI_DYN), C.c_double(np.pi), 1, _dp(xi), None)
-                            x = xi; F = F & ~T; rows["n_land"][b, r] += int(T.sum())
-                    while True:                              # rule 2: lift-off
-                        A = Cs & ~F
-                        xn, y = solve(A)
-                        lz = y.reshape(4, 3)[:, 2]
-                        if A.any():
-                            force_margin[b, r] = min(force_margin[b, r], float(np.abs(lz[A] - fz_rel).min()))
-                        if not A.any() or not (lz[A].min() < fz_rel):
-                            break
-                        cand = np.where(A, lz, np.inf)
-                        f = int(np.argmin(cand))                 # (the lowest leg index on a tie)
-                        if A.sum() > 1:
-                            force_margin[b, r] = min(force_margin[b, r], float(np.sort(cand)[1] - cand[f]))
-                        F = F.copy(); F[f] = True
-                        rows["n_release"][b, r] += 1
-                        if rows["first_release"][b, r] < 0:
-                            rows["first_release"][b, r] = s
-                    Y[b, r, s, j] = y; att[b, r, s, j] = A
-                    rows["n_free"][b, r] += int((F & Cs).sum())
-                    nsq = float(xn @ xn)
-                    if not (nsq <= 1e12):      # rule 3: the state the failing step was taken from is kept, nothing further is counted
-                        first_bad[b, r] = s; alive = False
-                        break
-                    x = xn
-                if alive and reset:
-                    xi = np.zeros(36)
-                    oracle_lib.oracle_wb_impact(_dp(x), contact[p].ctypes.data_as(IP), nxt[p].ctypes.data_as(IP), C.c_double(mc.PSI_DYN), C.c_double(np.pi), 1, _dp(xi), None)
-                    x = xi
-            X[b, r, n] = x
-            if alive:
-                fall_test(n)
-            Fend[b, r] = F
-            rows["free_final"][b, r] = int(sum(1 << l for l in range(4) if F[l]))
-            rows["max_lift"][b, r] = lift if np.isfinite(lift) else 0.0
-    for a in (X, U, Y, counted, att):
-        a.setflags(write=False)
-    return dict(X=X, U=U, Y=Y, counted=counted, att=att, first_bad=first_bad, first_fall=first_fall, n_sat=n_sat, sat_margin=sat_margin, fall_margin=fall_margin,
-                rows=rows, F=Fend, solves=solves, force_margin=force_margin, kin_margin=kin_margin, raw_kin=tuple(raw_kin))
+    w = wr.reference_walk(pkg, oracle_lib, phases, policy, smap, x0, S, contact=(fz_rel, z_ground), dist=dist, kick=kick, F0=F0)
+    return wr.pick(w, wr.KEYS_UNI)
 
 
 def grf_rows_uni(pkg, ref, mu, fz_min):
@@ -251,50 +128,21 @@ def invariants(tag, res, fz_rel, bound):
 # ---- the host build of the program
 
 def build_emu(tmpdir):
-    out = os.path.join(str(tmpdir), "libhsddp_uni_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cafe-mpc_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "_emu", "uni_emu.cpp"), "-o", out])
-    lib = C.CDLL(out)
+    lib = wr.build_so(tmpdir, "uni_emu.cpp", "libhsddp_uni_emu.so")
     assert [lib.uni_emu_park_doubles(m) for m in (0, 1)] == [39, 41]      # the parked column of the three kernels, doubles per lane
     return lib
 
 
 def emu_run(lib, pkg, so, b, x0, smap, S, fz_rel, z_ground, dist=None, kick=None, mu=0.0, fz_min=0.0, F=None, hold=None):
     """The host build on problem b of a solved handle; x0, kick: [R, 36]; F: None or float [R, 4], updated in place.  Returns raw arrays."""
-    nph = len(so.phases)
-    D = [p["desc"] for p in so.phases]
-    hor = np.array([q.horizon for q in D], dtype=np.int32); dt = np.array([q.dt for q in D]); al = np.array([q.BG_alpha for q in D])
-    ct = np.array([[q.contact[l] for l in range(4)] for q in D], dtype=np.int32)
-    td = np.array([[1 if (q.contact[l] == 0 and q.next_contact[l] == 1) else 0 for l in range(4)] for q in D], dtype=np.int32)
-    xb = [np.ascontiguousarray(so.field(i, "XBAR", b, 1)[0]) for i in range(nph)]
-    ub = [np.ascontiguousarray(so.field(i, "UBAR", b, 1)[0]) for i in range(nph)]
-    kk = [np.ascontiguousarray(so.field(i, "K", b, 1)[0].transpose(0, 2, 1)) for i in range(nph)]
-    ptrs = lambda arrs: (C.c_void_p * nph)(*[a.ctypes.data for a in arrs])
-    n, R = smap.shape[1], x0.shape[0]
-    x0 = np.ascontiguousarray(x0); smap = np.ascontiguousarray(smap, dtype=np.int32)
-    xf = np.zeros((R, 36)); rows = np.zeros((R, 5)); X = np.zeros((R, n + 1, 36)); U = np.zeros((R, n, 12)); extra = np.full((R, 2), np.nan)
-    g = np.full((R, 5), np.nan); Y = np.full((R, n, 12), np.nan); c = np.full((R, 6), np.nan)
-    use_mc = dist is not None or kick is not None
-    d = dist if dist is not None else pkg.sim.Disturbance()
-    sw = np.array([d.sigma_u, d.sigma_q, d.sigma_v, d.u_max, d.fall_height])
-    kick = None if kick is None else np.ascontiguousarray(kick)
-    hold = None if hold is None else np.ascontiguousarray(hold, dtype=np.int32)
-    assert F is None or (F.dtype == np.float64 and F.flags.c_contiguous and F.shape == (R, 4))
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    rc = lib.uni_emu_run(nph, vp(hor), vp(dt), vp(al), vp(ct), vp(td), ptrs(xb), ptrs(ub), ptrs(kk), C.c_double(mc.PSI_DYN), vp(smap), n, R, vp(x0), vp(xf), vp(rows),
-                         vp(X), vp(U), int(S), 1 if use_mc else 0, C.c_ulonglong(d.seed), d.first_problem + b, vp(sw), d.kick_step, vp(kick), vp(extra),
-                         C.c_double(mu), C.c_double(fz_min), vp(g), vp(Y), C.c_double(fz_rel), C.c_double(z_ground), vp(c), vp(F), vp(hold))
-    assert rc == 0
-    return dict(xf=xf, rows=rows, X=X, U=U, extra=extra, g=g, Y=Y, c=c)
+    args, out, keep = wr.emu_prefix(pkg, so, b, x0, smap, S, dist, kick, mu, fz_min)
+    tail, out["c"] = wr.emu_contact_args(x0.shape[0], fz_rel, z_ground, F, hold)
+    assert lib.uni_emu_run(*args, *tail) == 0
+    return out
 
 
 def contact_rows_of(pkg, raw):
-    assert np.array_equal(raw[..., :5], np.round(raw[..., :5]))      # the counters are whole numbers in doubles
-    out = np.zeros(raw.shape[:-1], dtype=pkg._abi.CONTACT_ROW_DTYPE)
-    for i, f in enumerate(("first_release", "n_release", "n_land", "n_free", "free_final")):
-        out[f] = raw[..., i]
-    out["max_lift"] = raw[..., 5]
-    return out
+    return wr.struct_rows(raw, pkg._abi.CONTACT_ROW_DTYPE)
 
 
 def emu_result(pkg, outs, disturbed, records):
