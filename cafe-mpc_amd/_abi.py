@@ -459,6 +459,28 @@ def bind_latency(lib):
     return lib
 
 
+# include/hsddp_touchdown.h: per-problem, per-foot touchdown heights and terrain-aware planning (libhsddp_hip.so only)
+TOUCHDOWN_EXPORTS = ["hsddp_touchdown_set", "hsddp_touchdown_get", "hsddp_touchdown_clear", "hsddp_touchdown_from_terrain", "hsddp_episode_plan_terrain"]
+
+
+def bind_touchdown(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_touchdown.h (and of hsddp_terrain.h and hsddp_episode.h, which it includes).
+    Raises if the library lacks any."""
+    missing = [s for s in TOUCHDOWN_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the touchdown-height entry points {missing}")
+    bind_terrain(lib); bind_episode(lib)
+    H = C.c_void_p
+    lib.hsddp_touchdown_set.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.hsddp_touchdown_get.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.hsddp_touchdown_clear.argtypes = [H, C.c_int]
+    lib.hsddp_touchdown_from_terrain.argtypes = [H, C.POINTER(TerrainParams), C.c_void_p, C.c_void_p, C.c_double, C.c_int]
+    lib.hsddp_episode_plan_terrain.argtypes = [H]
+    for s in TOUCHDOWN_EXPORTS:
+        getattr(lib, s).restype = C.c_int
+    return lib
+
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -713,6 +735,62 @@ class Solver:
         self._ck(self.lib.hsddp_get_references(self.h, phase, b0, nb, *[out[n].ctypes.data if n in out else None for n in REF_FIELDS]),
                  "get_references")
         return out
+
+    def set_touchdown_heights(self, phase, heights, b0=0):
+        """Touchdown heights of problems b0 .. b0+nb-1 of a whole-body phase (include/hsddp_touchdown.h): heights [nb, 4] by leg FL FR HL HR - a
+        numpy array (copied) or a float64 torch tensor on the handle's device (read in place).  The touchdown constraint of leg l of problem b
+        becomes foot_z - heights[b, l]."""
+        lib = bind_touchdown(self.lib)
+        if type(heights).__module__.startswith("torch"):
+            import torch
+            if heights.dtype != torch.float64 or not heights.is_contiguous() or heights.device.type != "cuda" or heights.dim() != 2 or heights.shape[1] != 4:
+                raise ValueError(f"heights: need a contiguous float64 tensor [nb, 4] on the handle's device, got {heights.dtype} {tuple(heights.shape)} on {heights.device}")
+            self._ck(lib.hsddp_touchdown_set(self.h, phase, b0, heights.shape[0], heights.data_ptr(), 1), "touchdown_set")
+            return
+        a = np.ascontiguousarray(heights, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError(f"heights: shape {a.shape}, need [nb, 4]")
+        self._ck(lib.hsddp_touchdown_set(self.h, phase, b0, a.shape[0], a.ctypes.data, 0), "touchdown_set")
+
+    def touchdown(self, phase, b0=0, nb=None):
+        """(heights, values) of problems b0 .. b0+nb-1 of a phase, each [nb, 4] by leg: the touchdown heights in use (the descriptor's ground_height
+        when the phase has none of its own) and the constraint values the last writing rollout stored (NaN for legs without a touchdown)."""
+        lib = bind_touchdown(self.lib)
+        nb = self.batch - b0 if nb is None else nb
+        hts, val = np.zeros((max(nb, 0), 4)), np.zeros((max(nb, 0), 4))
+        self._ck(lib.hsddp_touchdown_get(self.h, phase, b0, nb, hts.ctypes.data, val.ctypes.data), "touchdown_get")
+        return hts, val
+
+    def clear_touchdown_heights(self, phase=-1):
+        """Return a phase (-1: every phase) to the shared ground_height of its descriptor."""
+        self._ck(bind_touchdown(self.lib).hsddp_touchdown_clear(self.h, phase), "touchdown_clear")
+
+    def plan_terrain(self, terrain, map_of=None, z_ground=0.0):
+        """Touchdown heights of every whole-body phase with a touchdown constraint from a sim.Terrain: z_ground + the grid's height at the phase's
+        terminal reference foothold of each leg (hsddp_touchdown_from_terrain; problems.touchdown_heights_from_terrain is the definition).
+        terrain.H and map_of (int [batch] or None: map 0; default terrain.map_of[:, 0]) are numpy arrays, or both torch tensors on the handle's
+        device."""
+        lib = bind_touchdown(self.lib)
+        if map_of is None and terrain.map_of is not None:
+            map_of = np.asarray(terrain.map_of).reshape(self.batch, -1)[:, 0]
+        if type(terrain.H).__module__.startswith("torch"):
+            import torch
+            H = terrain.H if terrain.H.dim() == 3 else terrain.H[None]
+            if H.dtype != torch.float64 or not H.is_contiguous() or H.device.type != "cuda":
+                raise ValueError("plan_terrain: a device grid is a contiguous float64 tensor on the handle's device")
+            if map_of is not None and (not type(map_of).__module__.startswith("torch") or map_of.dtype != torch.int32 or not map_of.is_contiguous()
+                                       or map_of.device.type != "cuda" or tuple(map_of.shape) != (self.batch,)):
+                raise ValueError("plan_terrain: with a device grid map_of is a contiguous int32 tensor [batch] on the handle's device")
+            t = TerrainParams(H.shape[2], H.shape[1], H.shape[0], 1 if terrain.early else 0, terrain.x0, terrain.y0, terrain.cx, terrain.cy, terrain.w_td)
+            self._ck(lib.hsddp_touchdown_from_terrain(self.h, C.byref(t), H.data_ptr(), None if map_of is None else map_of.data_ptr(), float(z_ground), 1), "touchdown_from_terrain")
+            return
+        H, t = terrain.grid(), terrain.to_c()
+        mo = None
+        if map_of is not None:
+            mo = np.ascontiguousarray(map_of, dtype=np.int32)
+            if mo.shape != (self.batch,):
+                raise ValueError(f"plan_terrain: map_of has shape {mo.shape}, need ({self.batch},)")
+        self._ck(lib.hsddp_touchdown_from_terrain(self.h, C.byref(t), H.ctypes.data, None if mo is None else mo.ctypes.data, float(z_ground), 0), "touchdown_from_terrain")
 
     def simulate(self, x0, n_steps, keep_traj=False, dist=None, kick=None, grf=None, substeps=1, contact=None, terrain=None, plant=None, friction=None):
         """Closed-loop rollouts of the current policy from the initial states x0 [batch, R, 36] (numpy, or a torch tensor on the handle's device)

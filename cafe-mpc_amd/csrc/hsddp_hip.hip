@@ -28,6 +28,7 @@
 #include "hsddp_mc.h"
 #include "hsddp_episode.h"
 #include "hsddp_latency.h"
+#include "hsddp_touchdown.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -68,103 +69,7 @@ static std::atomic<long long> g_dev_allocs{0};
 #define LQ_ATTR __attribute__((amdgpu_waves_per_eu(LQ_WPE, LQ_WPE)))
 
 // ------------------------------------------------------------------------------------------------ kernels
-// Single shooting from phase `first` on, by ONE wave: every knot takes the state its predecessor simulated (SinglePhase.cpp:187,211-220).
-// Used for the young phases the receding-horizon update creates (SS_set empty, MHPCProblem.cpp:340-351; first > 0, stops at the next
-// phase with shooting nodes) and for the whole horizon when option.MS is false (MultiPhaseDDP.cpp:65-68; first = 0, descriptors with
-// every shooting flag cleared).  On entry the state to start from is in L.xnext (whole-body phase) / in Xsim[0] of the phase (SRB, HKD).
-template <bool WBM, class LDS> __device__ __forceinline__ void rollout_chain(LDS& L, PhaseC* ph, int nph, int first, const ModelDev& md, int b, int nslots, double eps, const OptDev& opt, SlotOut so,
-                                              size_t slot_base, int* fail, bool wr) {
-    for (int pj = first; pj < nph && !ph[pj].shooting; pj++) {
-        PhaseC& Q = ph[pj]; PhaseC* Qn = pj + 1 < nph ? &ph[pj + 1] : nullptr; const size_t s0 = slot_base + Q.slot0;
-        if (WBM && Q.model == HSDDP_MODEL_WB) {
-            if constexpr (WBM) {
-            for (int kq = 0; kq < Q.h; kq++) wb_rollout_knot<64>(L, Q, md, b, kq, eps, opt.ReB_active, nullptr, so, s0 + kq, fail, true, wr);
-            wb_rollout_terminal<64>(L, Q, Qn, md, b, eps, opt.AL_active, so, s0 + Q.h, true, wr);
-            }
-        } else if (Q.model == HSDDP_MODEL_SRB) {      // (reads the simulated state back from Xsim: not available to probes, see hsddp_solve)
-            SrbLds& Ls = *reinterpret_cast<SrbLds*>(&L);
-            for (int kq = 0; kq < Q.h; kq++) srb_rollout_knot<64>(Ls, Q, b, kq, eps, opt.ReB_active, nullptr, so, s0 + kq, fail, true, wr);
-            srb_rollout_terminal<64>(Ls, Q, Qn, b, eps, so, s0 + Q.h, true, wr);
-        } else {
-            HkdLds& Lh = *reinterpret_cast<HkdLds*>(&L);
-            for (int kq = 0; kq < Q.h; kq++) hkd_rollout_knot<64>(Lh, Q, b, kq, eps, opt.ReB_active, nullptr, so, s0 + kq, fail, true, wr);
-            hkd_rollout_terminal<64>(Lh, Q, Qn, md, b, eps, opt.AL_active, so, s0 + Q.h, true, wr);
-        }
-    }
-}
-
-// Probe launches of the ONE-WAVE kernels (k_rollout, k_rollout_hkd; the quad kernel loops over the candidates inside a unit's wave instead):
-// grid = candidates x units.  Workgroups go round-robin over the 8 XCDs (one L2 each); the candidates of a unit read the same
-// trajectories and differ in eps only.  Unit u lives on XCD u % 8 and its candidates occupy consecutive dispatch slots of that XCD, so one of them
-// brings the lines into that L2 and the others find them there (candidate-major order streamed the whole ensemble from HBM once per candidate:
-// probe launch of the quad kernel 11.4 -> 9.8 ms).  QUAD_CAND_MAJOR 1 = the old order.
-#ifndef QUAD_CAND_MAJOR
-#define QUAD_CAND_MAJOR 0
-#endif
-__device__ __forceinline__ void cand_unit(int per, int g, int& c, int& r) {
-#if QUAD_CAND_MAJOR
-    c = g / per; r = g - c * per;
-#else
-    const int ncand = gridDim.x / per;
-    const int full = (per >> 3) << 3;
-    if (g < full * ncand) { const int G = g / (8 * ncand), rem = g - G * 8 * ncand; c = rem >> 3; r = G * 8 + (rem & 7); }
-    else { const int nt = per - full, g2 = g - full * ncand; c = g2 / nt; r = full + (g2 - c * nt); }
-#endif
-}
-
-// LDS of the kernels instantiated WITHOUT the whole-body model (kinodynamic / single-rigid-body handles): 8 KB instead of 16 / 40 KB, so that
-// their small knots are not held to the whole-body kernels' two waves per SIMD
-union RedLds { HkdLds h; SrbLds s; };
-// slot_list / nlist: the slots this launch covers (null: all nslots) - when the lane-quad kernel takes the whole-body running knots of a launch,
-// the one-wave programs only see the rest (the terminal knots it leaves with their reset maps, single-rigid-body knots); unit_knots: running knots
-// among them; plist / nprob: the problems this launch is for (null: all nprob = batch of them, `mask` picks)
-#define ROLL_ARGS const PhaseDev* ph_, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, ModelDev md, EpsList el, OptDev opt, const double* x0, SlotArrays sa, \
-                  const ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist, int unit_knots, const int* plist, int nprob
-template <bool WBM, class LDS> __device__ __forceinline__ void rollout_body(LDS& L, ROLL_ARGS) {
-    PhaseC* ph = (PhaseC*)ph_;   // descriptors: constant memory, scalar loads
-    const int per = nprob * nlist;
-    int c, r; cand_unit(per, blockIdx.x, c, r);
-    const int ip = r / nlist, si = r - ip * nlist;
-    const int b = plist != nullptr ? plist[ip] : ip;
-    if (masked_out(st[b], mask)) return;
-    if (si == 0 && threadIdx.x == 0) atomicAdd(units, (unsigned long long)unit_knots);     // knots this launch rolls out (measurement only)
-    const int s = slot_list != nullptr ? slot_list[si] : si;
-    const int pi = slot_phase[s], k = slot_k[s];
-    PhaseC& P = ph[pi];
-    const size_t cbase = (size_t)c * batch * nslots;            // slice of candidate c in the slot arrays
-    SlotOut so{sa.cost, sa.dsq, sa.ming, sa.maxh};
-    const size_t slot_base = cbase + (size_t)b * nslots, slot = slot_base + s;
-    const double eps = el.from_state ? st[b].ls_eps : el.e[c];
-    const bool wr = (c == el.writer);
-    fail += (size_t)c * batch;
-    int chain_first = -1;
-    if (!ph[0].shooting) {       // single shooting over the whole horizon (option.MS = false): the wave of slot 0 walks every phase
-        if (s != 0) return;
-        const int n0 = ph[0].n;
-        if (WBM && ph[0].model == HSDDP_MODEL_WB) { if constexpr (WBM) { HS_PHASE(64, if (tid < 36) L.xnext[tid] = x0[(size_t)b * 36 + tid];) } }
-        else { HS_PHASE(64, if (tid < n0) ph[0].Xsim[(size_t)b * (ph[0].h + 1) * n0 + tid] = x0[(size_t)b * n0 + tid];) }
-        chain_first = 0;
-    } else {
-        if (!P.shooting) return;     // a phase without shooting nodes is rolled sequentially by the wave of its predecessor's terminal knot
-        PhaseC* Pn = pi + 1 < nph ? &ph[pi + 1] : nullptr;
-        if (k == P.h) chain_first = pi + 1;
-        if (P.model == HSDDP_MODEL_HKD) {
-            HkdLds& Lh = *reinterpret_cast<HkdLds*>(&L);
-            if (k < P.h) hkd_rollout_knot<64>(Lh, P, b, k, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, so, slot, fail, false, wr);
-            else hkd_rollout_terminal<64>(Lh, P, Pn, md, b, eps, opt.AL_active, so, slot, false, wr);
-        } else if (P.model == HSDDP_MODEL_SRB) {   // reduced-model tail of the MHPC horizon: a few hundred flops per knot, reuses the whole-body LDS block
-            SrbLds& Ls = *reinterpret_cast<SrbLds*>(&L);
-            if (k < P.h) srb_rollout_knot<64>(Ls, P, b, k, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, so, slot, fail, false, wr);
-            else srb_rollout_terminal<64>(Ls, P, Pn, b, eps, so, slot, false, wr);
-        } else if constexpr (WBM) {
-            if (k < P.h) wb_rollout_knot<64>(L, P, md, b, k, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, so, slot, fail, false, wr);
-            else wb_rollout_terminal<64>(L, P, Pn, md, b, eps, opt.AL_active, so, slot, false, wr);
-        }
-    }
-    // single-shooting phases from here on (young phases behind a terminal knot, or the whole horizon): ONE call site, one copy of the code
-    if (chain_first >= 0 && chain_first < nph && !ph[chain_first].shooting) rollout_chain<WBM>(L, ph, nph, chain_first, md, b, nslots, eps, opt, so, slot_base, fail, wr);
-}
-#define ROLL_PASS ph_, nph, slot_phase, slot_k, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, slot_list, nlist, unit_knots, plist, nprob
+#include "rollout_body.hpp"      // rollout_chain, cand_unit, RedLds, ROLL_ARGS, rollout_body, ROLL_PASS
 __global__ void __launch_bounds__(64) ROLL_ATTR k_rollout(ROLL_ARGS) { __shared__ WbCore L; rollout_body<true>(L, ROLL_PASS); }
 // handles without whole-body phases (has_hkd): no whole-body code, 8 KB of LDS, no register cap
 // (measured on config 5, waves per SIMD rollout / LQ: none/none 111.6 k it/s, 3/- 117.7 k, 4/- 121.9 k, 4/5 122.1 k, 5/5 122.5 k; 8 KB of LDS allow five)
@@ -207,6 +112,11 @@ __global__ void __launch_bounds__(64) ROLL_HKD_ATTR k_rollout_hkd(ROLL_ARGS) { _
 // k_episode_latency (hsddp_latency.h) and its launcher, likewise (-DHS_LAT_SEPARATE here); the prototype is in episode.hpp either way.
 #ifndef HS_LAT_SEPARATE
 #include "hsddp_lat.hip"
+#endif
+// k_rollout_tdh, k_rollout_quad_term_tdh and k_td_terrain (hsddp_touchdown.h) and their launchers, likewise (-DHS_TDH_SEPARATE here); the prototypes
+// are in rollout_args.hpp either way.
+#ifndef HS_TDH_SEPARATE
+#include "hsddp_tdh.hip"
 #endif
 
 // Batched line search, decision step (MultiPhaseDDP::line_search, MultiPhaseDDP.cpp:108-131, for the candidates of one probe launch): per
@@ -634,6 +544,10 @@ struct hsddp_handle {
     // hsddp_reconfigure (the new window's phases are shared again); staging for host sources.  Both grow on demand, freed by hsddp_destroy.
     char* d_refs = nullptr; size_t refs_cap = 0, refs_used = 0;
     char* d_refs_stage = nullptr; size_t refs_stage_cap = 0;
+    // per-problem touchdown heights (hsddp_touchdown.h, touchdown_host.hpp): the table [nph_cap][batch][4], the phases with heights of their own and
+    // their count (0: the table is not read), staging of a fill, staging of a host grid / map of hsddp_touchdown_from_terrain.  Freed by hsddp_destroy.
+    double* d_tdh = nullptr; std::vector<char> td_own; int td_n = 0; std::vector<double> td_stage;
+    double* d_td_H = nullptr; size_t td_H_cap = 0; int* d_td_map = nullptr;
     ProbState* d_st = nullptr;
     double* d_x0 = nullptr;
     SlotArrays sa{};
@@ -732,7 +646,7 @@ void hsddp_destroy(hsddp_handle_t* h) {
     if (h->d_cmd) hipFree(h->d_cmd);
     if (h->d_cmd_map) hipFree(h->d_cmd_map);
     if (h->d_cmd_status) hipFree(h->d_cmd_status);
-    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out, h->d_refs, h->d_refs_stage}; for (void* q : p) if (q) hipFree(q); }
+    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out, h->d_refs, h->d_refs_stage, h->d_tdh, h->d_td_H, h->d_td_map}; for (void* q : p) if (q) hipFree(q); }
     for (auto e : h->pool) hipEventDestroy(e);
     if (h->h_counters) hipHostFree(h->h_counters);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -910,6 +824,7 @@ int hsddp_reconfigure(hsddp_handle_t* h, int n_phases, const hsddp_phase_desc_t*
     h->has_hkd = false; for (int i = 0; i < n_phases; i++) if (phases[i].model == HSDDP_MODEL_HKD) h->has_hkd = true;
     h->cache_valid = false;
     h->refs_used = 0;                                                                   // every phase of the new window reads its descriptor's references
+    h->td_own.assign(n_phases, 0); h->td_n = 0;                                         // ... and its descriptor's ground_height (hsddp_touchdown.h)
     if (h->d_cmd_status) { hipFree(h->d_cmd_status); h->d_cmd_status = nullptr; }      // sized by the phase count
     HIPCK(hipGetLastError());
     return HSDDP_OK;
@@ -964,12 +879,24 @@ static void launch_rollout_list(hsddp_handle* h, const EpsList& el, const SlotAr
         const int nprob = plist ? nlist : h->batch, nbg = (nprob + 15) / 16;
         launch_k_rollout_quad((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
                               h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist);
-        if (h->n_term > 0)
+        const bool tdh = h->td_n > 0;      // a phase of the window has touchdown heights of its own (hsddp_touchdown.h): the terminal knots read the table
+        if (h->n_term > 0 && tdh)
+            launch_k_rollout_quad_term_tdh((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
+                                           plist, nlist, h->d_tdh);
+        else if (h->n_term > 0)
             launch_k_rollout_quad_term((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
                                        plist, nlist);
-        if (h->n_other > 0 && nprob > 0)      // (a window whose every slot is on lane quads launches no one-wave kernel at all)
+        if (h->n_other > 0 && nprob > 0 && tdh)
+            launch_k_rollout_tdh((unsigned)((size_t)el.n * nprob * h->n_other), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
+                                 h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob, h->d_tdh);
+        else if (h->n_other > 0 && nprob > 0)      // (a window whose every slot is on lane quads launches no one-wave kernel at all)
             hipLaunchKernelGGL(k_rollout, dim3((unsigned)((size_t)el.n * nprob * h->n_other)), dim3(64), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
                                h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob);
+        return;
+    }
+    if (h->td_n > 0 && !h->has_hkd) {      // (heights exist for whole-body phases only, and a window with a kinodynamic phase has none)
+        launch_k_rollout_tdh((unsigned)((size_t)el.n * h->batch * h->nslots), h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
+                             h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph, (const int*)nullptr, h->batch, h->d_tdh);
         return;
     }
     hipLaunchKernelGGL(h->has_hkd ? k_rollout_hkd : k_rollout, dim3((unsigned)((size_t)el.n * h->batch * h->nslots)), dim3(64), 0, h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
@@ -1693,4 +1620,6 @@ int hsddp_get_references(hsddp_handle_t* h, int phase, int b0, int nb, double* x
 
 // ------------------------------------------------------------------------------------------------ closed-loop policy simulation (hsddp_sim.h) and MPC episodes (hsddp_episode.h)
 #include "sim_host.hpp"
+// ------------------------------------------------------------------------------------------------ per-problem touchdown heights (hsddp_touchdown.h)
+#include "touchdown_host.hpp"
 #endif

@@ -29,3 +29,13 @@ void launch_k_rollout_quad(unsigned grid, hipStream_t stream, const hs::PhaseDev
 // k_rollout_quad_term (hsddp_quad.hip): the terminal knots the quad path owns, one workgroup per unit (terminal slot of the list x group of sixteen problems)
 void launch_k_rollout_quad_term(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* tslots, int nslots, int batch,
                                 hs::ModelDev md, EpsList el, hs::OptDev opt, SlotArrays sa, const hs::ProbState* st, int mask, const int* plist, int nlist);
+
+// The rollout kernels with per-problem touchdown heights and the kernel that fills the heights from a terrain grid (hsddp_tdh.hip, hsddp_touchdown.h);
+// tdh: the window's table [phase][batch][4].  Arguments otherwise those of k_rollout / k_rollout_quad_term.
+namespace hs { struct TdGrid; }
+void launch_k_rollout_tdh(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, hs::ModelDev md, EpsList el,
+                          hs::OptDev opt, const double* x0, SlotArrays sa, const hs::ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist,
+                          int unit_knots, const int* plist, int nprob, const double* tdh);
+void launch_k_rollout_quad_term_tdh(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* tslots, int nslots, int batch,
+                                    hs::ModelDev md, EpsList el, hs::OptDev opt, SlotArrays sa, const hs::ProbState* st, int mask, const int* plist, int nlist, const double* tdh);
+void launch_k_td_terrain(hipStream_t stream, const hs::PhaseDev* ph, int nph, int batch, const hs::TdGrid& g, double* out);

@@ -725,9 +725,10 @@ HD double wb_terminal_cost_base(PhaseC& P, const WbCore& L, int b) {
 }
 
 // Terminal knot (k = h) of a phase: terminal constraint + cost, then the reset map into the next phase.
-template <int NT>
+// TDH: the touchdown feet are held to the problem's own heights tdh[0..4) (by leg, hsddp_touchdown.h) instead of the phase's ground_height.
+template <int NT, bool TDH = false>
 HD void wb_rollout_terminal(WbCore& L, PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active,
-                            SlotOut so, size_t slot, bool ss = false, bool wr = true) {
+                            SlotOut so, size_t slot, bool ss = false, bool wr = true, const double* tdh = nullptr) {
     const int h = P.h;
     const size_t kx = ((size_t)b * (h + 1) + h) * 36;
     HS_PHASE(NT, if (tid < 36) { double x = ss ? L.xnext[tid] : P.Xbar[kx + tid] + eps * P.dX[kx + tid]; L.x[tid] = x; if (wr) P.X[kx + tid] = x; }
@@ -738,7 +739,8 @@ HD void wb_rollout_terminal(WbCore& L, PhaseC& P, PhaseC* Pn, const ModelDev& md
         double pb = wb_terminal_cost_base(P, L, b); if (wr) P.Phibase[b] = pb;
         double maxh = 0, c = 0; int i = 0;
         for (int f = 0; f < 4; f++) if (P.td[f] && P.nt > 0) {
-            double hh = L.fpos[3 * f + 2] - P.ground_height; if (wr) P.th[(size_t)b * P.nt + i] = hh; maxh = fmax(maxh, fabs(hh));
+            double hh; if constexpr (TDH) hh = L.fpos[3 * f + 2] - tdh[f]; else hh = L.fpos[3 * f + 2] - P.ground_height;
+            if (wr) P.th[(size_t)b * P.nt + i] = hh; maxh = fmax(maxh, fabs(hh));
             double sg = P.sigma[(size_t)b * P.nt + i], lm = P.lambda[(size_t)b * P.nt + i];
             c += 0.5 * sg * hh * hh; c += lm * hh; i++;
         }

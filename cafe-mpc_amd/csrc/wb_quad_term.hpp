@@ -29,8 +29,9 @@ struct QuadTermOut { double cost, dsq, maxh; };
 //   wr = false: a probe - only (Phi, defect^2 of the successor's knot 0, max |h|) come back;  wr = true additionally stores what wb_rollout_terminal
 //   stores: X[h], Phibase, Phi, th and the successor's Xsim[0], Defect[0].  wr must be uniform over the wave.
 //   in: xbar / dx rows of 72 (knot h, then knot 0 of the successor - unread without one), rr: row h of the packed references.
-template <class Q, class PT>
-HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active, bool wr, const QuadIn<PT>& in) {
+//   TDH: the lane's foot is held to the problem's own height tdh[leg] (hsddp_touchdown.h: tdh points at the problem's four) instead of ground_height.
+template <class Q, bool TDH = false, class PT>
+HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active, bool wr, const QuadIn<PT>& in, const double* tdh = nullptr) {
     using S = typename Q::S;
     const bool WR = wr;
     const int h = P.h;
@@ -136,7 +137,8 @@ HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, i
         const size_t tb = (size_t)b * P.nt;
         const S ti = Q::sel(on, before, S(0.0));      // (a lane without a touchdown reads a valid dummy and contributes nothing)
         const S sg = Q::ldv(P.sigma, tb, ti), lm = Q::ldv(P.lambda, tb, ti);
-        const S hh = fpos.z - P.ground_height;
+        S hh;
+        if constexpr (TDH) hh = fpos.z - Q::ld(tdh, 0, 1); else hh = fpos.z - P.ground_height;
         if (WR) Q::stv(P.th, tb, ti, on, hh);
         maxh = -Q::vmin(Q::sel(on, Q::sel(Q::gt(zero, hh), hh, -hh), zero));      // max |h| over the touchdown feet
         S c = zero;
@@ -366,14 +368,14 @@ HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, i
 
 #ifdef HS_HOST_EMU
 // host form that gathers the rows from the phases' arrays (tests/_emu, one evaluation per knot)
-template <class Q>
-inline QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active, bool wr) {
+template <class Q, bool TDH = false>
+inline QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active, bool wr, const double* tdh = nullptr) {
     double xb[72] = {0}, dx[72] = {0};
     const size_t kx = ((size_t)b * (P.h + 1) + P.h) * 36;
     for (int i = 0; i < 36; i++) { xb[i] = P.Xbar[kx + i]; dx[i] = P.dX[kx + i]; }
     if (Pn != nullptr) { const size_t nx = (size_t)b * (Pn->h + 1) * 36; for (int i = 0; i < 36; i++) { xb[36 + i] = Pn->Xbar[nx + i]; dx[36 + i] = Pn->dX[nx + i]; } }
     const QuadIn<const double*> in = {xb, dx, nullptr, nullptr, nullptr, P.rref + ref_row(P, b, P.h) * 80};
-    return wbq_rollout_terminal<Q>(P, Pn, md, b, eps, al_active, wr, in);
+    return wbq_rollout_terminal<Q, TDH>(P, Pn, md, b, eps, al_active, wr, in, tdh);
 }
 #endif
 

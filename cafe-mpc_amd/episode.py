@@ -235,6 +235,14 @@ class Episode:
         if rc != 0:
             raise RuntimeError(f"hsddp_terrain_set failed rc={rc}")
 
+    def plan_terrain(self):
+        """Terrain-aware planning (include/hsddp_touchdown.h): the touchdown heights of the solver's current window from the terrain this episode
+        simulates on - its grid, z_ground and the map of each robot, as they are on the device.  Call it after the window moved (reconfigure, any
+        set_references) and before the solve.  Raises if the episode has no terrain set."""
+        rc = _abi.bind_touchdown(self.lib).hsddp_episode_plan_terrain(self.e)
+        if rc != 0:
+            raise RuntimeError(f"hsddp_episode_plan_terrain failed rc={rc}")
+
     def set_friction(self, friction, on=True):
         """Coulomb friction (include/hsddp_friction.h) for every later tick with the contact rule on; `friction`: a sim.Friction whose mu_of, if
         given, is int [batch] or [batch, 1].  The sliding feet of a robot and their lagged normal forces are carried from tick to tick and cleared by
@@ -377,13 +385,15 @@ class Episode:
         return t.value, a.value, i.value
 
 
-def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None, friction=None):
+def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None, friction=None, plan_terrain=False, post_hook=None):
     """The receding-horizon loop of MHPCLocomotion::update with the SIMULATED state fed back, for the whole batch.  solver: solved for the window
     `phases` of pd (builder.MHPCProblemData).  Per tick: episode.advance, pd.update(), builder.shift_solver_in_place, hook(tick, phases) - the
     place for solver.set_references - and solver.solve(opt_rt).  kicks: {tick: (kick_step, [B, 36])}.  episode: an Episode already reset; None
     creates one (n_exec = dt_mpc / dt_wb, max_ticks = n_ticks) and resets it to the solver's Xbar[0].  delay: None leaves the episode as it is; an int
     or int [B] is Episode.set_latency before the first tick (include/hsddp_latency.h: the loop moves the window by n_exec knots a tick, as that needs).
-    friction: None leaves the episode as it is; a sim.Friction is Episode.set_friction before the first tick (it acts while the contact rule is on).  Returns a dict: episode, phases (the last
+    friction: None leaves the episode as it is; a sim.Friction is Episode.set_friction before the first tick (it acts while the contact rule is on).
+    plan_terrain: every tick, after the hook and before the solve, episode.plan_terrain() gives the new window the touchdown heights of the episode's
+    terrain (include/hsddp_touchdown.h); False plans onto the descriptors' ground_height.  post_hook(tick, phases) is called after the tick's solve.  Returns a dict: episode, phases (the last
     window), n_iters / n_ls_iters / n_reg_iters / cost [n_ticks, B], alive [n_ticks]."""
     from . import builder
     if episode is None:
@@ -404,7 +414,11 @@ def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=No
         phases, _ = builder.shift_solver_in_place(solver, phases, pd, m, ubar_mode="zero")
         if hook is not None:
             hook(t, phases)
+        if plan_terrain:
+            episode.plan_terrain()
         solver.solve(opt_rt)
+        if post_hook is not None:
+            post_hook(t, phases)
         ia = solver.info_arrays()
         out["n_iters"].append(ia["n_iters"]); out["n_ls_iters"].append(ia["n_ls_iters"]); out["n_reg_iters"].append(ia["n_reg_iters"]); out["cost"].append(ia["actual_cost"])
         out["alive"].append(episode.status()[1])

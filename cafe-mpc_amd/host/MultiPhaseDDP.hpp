@@ -28,6 +28,7 @@
 #include "hsddp_plant.h"
 #include "hsddp_episode.h"
 #include "hsddp_latency.h"
+#include "hsddp_touchdown.h"
 
 namespace hsddp {
 
@@ -160,6 +161,9 @@ public:
     }
     // terrain and early touchdown for every later tick; the swing feet a robot holds are carried from tick to tick (include/hsddp_terrain.h)
     bool set_terrain(bool on, const hsddp_terrain_t* t = nullptr, const double* H = nullptr, const int* map_of = nullptr) { rc_ = e_ ? hsddp_terrain_set(hsddp_episode_sim(e_), on ? 1 : 0, t, H, map_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // terrain-aware planning (include/hsddp_touchdown.h): the touchdown heights of the handle's current window from the terrain this episode simulates
+    // on; after the window moved (reconfigure, set_references) and before the solve
+    bool plan_terrain() { rc_ = e_ ? hsddp_episode_plan_terrain(e_) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // a plant row per robot for the whole episode (include/hsddp_plant.h): plant_of [batch] or null
     bool set_plant(bool on, int n_plants = 0, const double* P = nullptr, const int* plant_of = nullptr) { rc_ = e_ ? hsddp_plant_set(hsddp_episode_sim(e_), on ? 1 : 0, n_plants, P, plant_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // per-robot policy latency for every later tick (include/hsddp_latency.h): delay_of [batch] in control steps, or null and one delay for all
@@ -278,6 +282,18 @@ public:
     void get_references(int phase, int b0, int nb, double* xr, double* ur, double* yr, double* foot_pos, double* foot_vel, double* body_pos,
                         int* ref_contact) {
         rc_ = hsddp_get_references(h_, phase, b0, nb, xr, ur, yr, foot_pos, foot_vel, body_pos, ref_contact);
+    }
+    // per-problem, per-foot touchdown heights (include/hsddp_touchdown.h): heights [nb][4] by leg FL FR HL HR for problems [b0, b0+nb) of a whole-body
+    // phase (host memory, or device memory with src_device); touchdown: the heights in use and the stored constraint values (NaN for legs without a
+    // touchdown), NULL skips; clear: back to the descriptor's ground_height (-1: every phase); plan_terrain: the heights of the whole window from a
+    // terrain grid H [n_maps][ny][nx] at the reference footholds, map_of [batch] or null.
+    bool set_touchdown_heights(int phase, const double* heights, int nb, int b0 = 0, bool src_device = false) {
+        rc_ = hsddp_touchdown_set(h_, phase, b0, nb, heights, src_device ? 1 : 0); return rc_ == HSDDP_OK;
+    }
+    bool touchdown(int phase, double* heights, double* values, int b0, int nb) { rc_ = hsddp_touchdown_get(h_, phase, b0, nb, heights, values); return rc_ == HSDDP_OK; }
+    bool clear_touchdown_heights(int phase = -1) { rc_ = hsddp_touchdown_clear(h_, phase); return rc_ == HSDDP_OK; }
+    bool plan_terrain(const hsddp_terrain_t& t, const double* H, const int* map_of = nullptr, double z_ground = 0.0, bool src_device = false) {
+        rc_ = hsddp_touchdown_from_terrain(h_, &t, H, map_of, z_ground, src_device ? 1 : 0); return rc_ == HSDDP_OK;
     }
     // one-off closed-loop rollouts of the current policy, u = Ubar + K (x - Xbar), from n_samples initial states per problem over the first
     // n_steps whole-body control knots (x0: batch x n_samples x 36) - what the controller side of the reference does one state at a time

@@ -588,3 +588,34 @@ def translate_references(phases, dx, dy):
         q = dict(p); q.update(desc=d, bufs=bufs, Xbar=xbar)
         out.append(q)
     return out
+
+
+def touchdown_legs(desc):
+    """The legs [4] (bool) whose touchdown a whole-body phase constrains: in the air during the phase and in contact in the next one, with the
+    touchdown constraint switched on; all False for the other models."""
+    if desc.model != MODEL_WB or not desc.c_touchdown:
+        return np.zeros(4, dtype=bool)
+    return np.array([desc.contact[l] == 0 and desc.next_contact[l] == 1 for l in range(4)])
+
+
+def touchdown_heights_from_terrain(solver_or_phases, terrain, map_of=None, z_ground=0.0, batch=None):
+    """The definition of hsddp_touchdown_from_terrain (include/hsddp_touchdown.h) in numpy.  solver_or_phases: an _abi.Solver - the references its
+    problems track, per problem where hsddp_set_references gave them - or a list of phase dicts with `batch` (the shared references of the
+    descriptors).  terrain: sim.Terrain; map_of: int [batch] or None (map 0).  Returns {phase index: heights [batch, 4]} for every whole-body phase
+    with a touchdown constraint: z_ground + the height of the problem's map (sim.terrain_height) at the x, y of each leg's reference foothold at
+    the phase's terminal knot."""
+    from . import sim
+    if isinstance(solver_or_phases, (list, tuple)):
+        phases, B = solver_or_phases, int(batch)
+        feet = [np.broadcast_to(p["bufs"]["foot_pos"][-1], (B, 12)) for p in phases]
+    else:
+        phases, B = solver_or_phases.phases, solver_or_phases.batch
+        feet = [solver_or_phases.get_references(i)["foot_pos"][:, -1] if touchdown_legs(p["desc"]).any() else None for i, p in enumerate(phases)]
+    m = np.zeros(B, dtype=np.int64) if map_of is None else np.asarray(map_of, dtype=np.int64).reshape(B)
+    out = {}
+    for i, p in enumerate(phases):
+        if not touchdown_legs(p["desc"]).any():
+            continue
+        xy = np.asarray(feet[i], dtype=np.float64).reshape(B, 4, 3)[:, :, :2]
+        out[i] = float(z_ground) + sim.terrain_height(terrain, xy, m[:, None])
+    return out

@@ -49,8 +49,9 @@
  *   - hsddp_terrain_get returns the rows of the LAST run; HSDDP_EINVAL if that run had the terrain dormant, for a bad range or a NULL argument.
  *   - hsddp_episode_sim(e) is accepted, as by hsddp_contact_set.  Its rows are those of the last tick.
  *
- * Out of scope: sloped contact normals and risers that stop a foot sideways; sliding friction; the sign of landing impulses; terrain-aware planning
- * (the solver does not see the grid); fp32 handles; grids that already live in device memory.
+ * Out of scope: sloped contact normals and risers that stop a foot sideways; sliding friction; the sign of landing impulses; fp32 handles; grids that
+ * already live in device memory.  Terrain-aware planning is include/hsddp_touchdown.h: it gives the solver the grid's height at each reference foothold
+ * as the touchdown height of that problem and leg (hsddp_episode_plan_terrain for an episode's own terrain).
  */
 #ifndef HSDDP_TERRAIN_H
 #define HSDDP_TERRAIN_H
