@@ -481,6 +481,38 @@ def bind_touchdown(lib):
     return lib
 
 
+# include/hsddp_weights.h: per-problem cost-weight scales of whole-body phases (libhsddp_hip.so only)
+WEIGHTS_EXPORTS = ["hsddp_weights_set", "hsddp_weights_get", "hsddp_weights_clear"]
+WEIGHTS_ROW = 84      # sq[36] | sr[12] | sqf[36]
+
+
+def bind_weights(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_weights.h.  Raises if the library lacks any."""
+    missing = [s for s in WEIGHTS_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the weight-scale entry points {missing}")
+    H = C.c_void_p
+    lib.hsddp_weights_set.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.hsddp_weights_get.argtypes = [H, C.c_int, C.c_int, C.c_void_p]
+    lib.hsddp_weights_clear.argtypes = [H]
+    for s in WEIGHTS_EXPORTS:
+        getattr(lib, s).restype = C.c_int
+    return lib
+
+
+def pack_weight_scales(sq, sr, sqf, nb=None):
+    """Rows [nb, 84] = sq[36] | sr[12] | sqf[36] from three arrays, each one row ([36] / [12] / [36], broadcast to nb problems) or [nb, width]."""
+    parts = [np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (sq, sr, sqf)]
+    for a, w, n in zip(parts, (36, 12, 36), ("sq", "sr", "sqf")):
+        if a.ndim != 2 or a.shape[1] != w:
+            raise ValueError(f"{n}: shape {a.shape}, need [{w}] or [nb, {w}]")
+    rows = max(a.shape[0] for a in parts) if nb is None else nb
+    for a, n in zip(parts, ("sq", "sr", "sqf")):
+        if a.shape[0] not in (1, rows):
+            raise ValueError(f"{n}: {a.shape[0]} rows, need 1 or {rows}")
+    return np.ascontiguousarray(np.concatenate([np.broadcast_to(a, (rows, a.shape[1])) for a in parts], axis=1))
+
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -764,6 +796,33 @@ class Solver:
     def clear_touchdown_heights(self, phase=-1):
         """Return a phase (-1: every phase) to the shared ground_height of its descriptor."""
         self._ck(bind_touchdown(self.lib).hsddp_touchdown_clear(self.h, phase), "touchdown_clear")
+
+    def set_weight_scales(self, sq, sr, sqf, b0=0, nb=None):
+        """Cost-weight scales of problems b0 .. b0+nb-1 (include/hsddp_weights.h): in every whole-body phase problem b plans with q * sq[b], r * sr[b]
+        and qf * sqf[b].  sq [nb, 36], sr [nb, 12], sqf [nb, 36], or one row each that is broadcast to nb problems (default: b0 to the end of the
+        batch when every argument is one row).  A float64 torch tensor [nb, 84] on the handle's device passed as sq (sr = sqf = None) is read in place.
+        The scales stay across reconfigure; the foot costs, constraints, reduced-model phases and the episodes' track_cost are not scaled."""
+        lib = bind_weights(self.lib)
+        if type(sq).__module__.startswith("torch"):
+            import torch
+            if sr is not None or sqf is not None or sq.dtype != torch.float64 or not sq.is_contiguous() or sq.device.type != "cuda" or sq.dim() != 2 or sq.shape[1] != WEIGHTS_ROW:
+                raise ValueError("set_weight_scales: a device source is one contiguous float64 tensor [nb, 84] on the handle's device (sr = sqf = None)")
+            self._ck(lib.hsddp_weights_set(self.h, b0, sq.shape[0], sq.data_ptr(), 1), "weights_set")
+            return
+        one = all(np.asarray(a).ndim == 1 for a in (sq, sr, sqf))
+        rows = pack_weight_scales(sq, sr, sqf, nb=(self.batch - b0) if (one and nb is None) else nb)
+        self._ck(lib.hsddp_weights_set(self.h, b0, rows.shape[0], rows.ctypes.data, 0), "weights_set")
+
+    def weight_scales(self, b0=0, nb=None):
+        """(sq [nb, 36], sr [nb, 12], sqf [nb, 36]) in use for problems b0 .. b0+nb-1: ones when none are set."""
+        nb = self.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0), WEIGHTS_ROW))
+        self._ck(bind_weights(self.lib).hsddp_weights_get(self.h, b0, nb, rows.ctypes.data), "weights_get")
+        return rows[:, :36].copy(), rows[:, 36:48].copy(), rows[:, 48:].copy()
+
+    def clear_weight_scales(self):
+        """Back to the descriptors' weights for every problem: the kernels of a handle that never had scales."""
+        self._ck(bind_weights(self.lib).hsddp_weights_clear(self.h), "weights_clear")
 
     def plan_terrain(self, terrain, map_of=None, z_ground=0.0):
         """Touchdown heights of every whole-body phase with a touchdown constraint from a sim.Terrain: z_ground + the grid's height at the phase's

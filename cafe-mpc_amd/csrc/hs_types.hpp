@@ -85,6 +85,11 @@ template <class PD> HD size_t ref_row(PD& P, int b, int k) { return (unsigned)(b
 // how device code sees a descriptor: constant memory (scalar loads, values survive memory clobbers)
 using PhaseC = const HS_CONST PhaseDev;
 
+// Per-problem cost-weight scales (hsddp_weights.h): one row of WS_ROW doubles per problem, sq[36] | sr[12] | sqf[36].  A kernel only reads the
+// table, so its rows are seen like the descriptors: a row pointer that is uniform over the wave and a uniform index make a scalar load.
+constexpr int WS_R = 36, WS_QF = 48, WS_ROW = 84;
+using WsRow = const HS_CONST double*;
+
 // ReB parameter group of path constraint c (index into reb_init)
 HDH int constraint_group(const PhaseDev& P, int c) {
     if (P.go_torque >= 0 && c >= P.go_torque && c < P.go_torque + 24) return 0;

@@ -29,6 +29,7 @@
 #include "hsddp_episode.h"
 #include "hsddp_latency.h"
 #include "hsddp_touchdown.h"
+#include "hsddp_weights.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -58,16 +59,6 @@ static std::atomic<long long> g_dev_allocs{0};
 #else
 #define ROLL_ATTR
 #endif
-// LQ workgroup: 128 threads = two waves per knot (tangent rounds side by side, then column solves || cost partials), capped at 256
-// registers so that the four knots a CU holds in LDS make two waves per SIMD.  LQ_NT=64 is the one-wave variant.
-#ifndef LQ_NT
-#define LQ_NT 128
-#endif
-#ifndef LQ_WPE
-#define LQ_WPE 2
-#endif
-#define LQ_ATTR __attribute__((amdgpu_waves_per_eu(LQ_WPE, LQ_WPE)))
-
 // ------------------------------------------------------------------------------------------------ kernels
 #include "rollout_body.hpp"      // rollout_chain, cand_unit, RedLds, ROLL_ARGS, rollout_body, ROLL_PASS
 __global__ void __launch_bounds__(64) ROLL_ATTR k_rollout(ROLL_ARGS) { __shared__ WbCore L; rollout_body<true>(L, ROLL_PASS); }
@@ -117,6 +108,11 @@ __global__ void __launch_bounds__(64) ROLL_HKD_ATTR k_rollout_hkd(ROLL_ARGS) { _
 // are in rollout_args.hpp either way.
 #ifndef HS_TDH_SEPARATE
 #include "hsddp_tdh.hip"
+#endif
+// k_rollout_pw, k_rollout_quad_pw, k_rollout_quad_term_pw, k_lq_pw and k_pack_weights (hsddp_weights.h) and their launchers, likewise (-DHS_PW_SEPARATE
+// here); the prototypes are in rollout_args.hpp either way.
+#ifndef HS_PW_SEPARATE
+#include "hsddp_pw.hip"
 #endif
 
 // Batched line search, decision step (MultiPhaseDDP::line_search, MultiPhaseDDP.cpp:108-131, for the candidates of one probe launch): per
@@ -173,30 +169,7 @@ __global__ void __launch_bounds__(64) k_ls_pick(int nslots, int batch, SlotArray
     }
 }
 
-#define LQ_ARGS const PhaseDev* ph_, int nph, const int* slot_phase, const int* slot_k, int nslots, ModelDev md, OptDev opt, const ProbState* st, int mask, int use_cache, unsigned long long* units
-template <bool WBM, int NT, class LDS> __device__ __forceinline__ void lq_body(LDS& L, LQ_ARGS) {
-    PhaseC* ph = (PhaseC*)ph_;   // descriptors: constant memory, scalar loads
-    const int b = blockIdx.x / nslots, s = blockIdx.x % nslots;
-    if (masked_out(st[b], mask)) return;
-    if (s == 0 && threadIdx.x == 0) atomicAdd(units, (unsigned long long)nslots - nph);
-    const int pi = slot_phase[s], k = slot_k[s];
-    PhaseC& P = ph[pi];
-    if (P.model == HSDDP_MODEL_HKD) {
-        HkdLds& Lh = *reinterpret_cast<HkdLds*>(&L);
-        if (k < P.h) hkd_lq_knot<NT>(Lh, P, b, k, opt.ReB_active); else hkd_lq_terminal<NT>(Lh, P, pi + 1 < nph ? &ph[pi + 1] : nullptr, md, b, opt.AL_active);
-        return;
-    }
-    if (P.model == HSDDP_MODEL_SRB) {
-        SrbLds& Ls = *reinterpret_cast<SrbLds*>(&L);
-        if (k < P.h) srb_lq_knot<NT>(Ls, P, b, k, opt.ReB_active); else srb_lq_terminal<NT>(Ls, P, pi + 1 < nph ? &ph[pi + 1] : nullptr, b);
-        return;
-    }
-    if constexpr (WBM) {
-        if (k < P.h) wb_lq_knot<NT>(L, P, md, b, k, opt.ReB_active, use_cache != 0);
-        else wb_lq_terminal<NT>(L, P, pi + 1 < nph ? &ph[pi + 1] : nullptr, md, b, opt.AL_active);
-    }
-}
-#define LQ_PASS ph_, nph, slot_phase, slot_k, nslots, md, opt, st, mask, use_cache, units
+#include "lq_body.hpp"      // LQ_NT, LQ_WPE, LQ_ATTR, LQ_ARGS, lq_body, LQ_PASS
 __global__ void __launch_bounds__(LQ_NT) LQ_ATTR k_lq(LQ_ARGS) { __shared__ WbLqLds L; lq_body<true, LQ_NT>(L, LQ_PASS); }
 // handles without whole-body phases: one wave per knot, 8 KB of LDS, no register cap
 #ifndef LQ_HKD_WPE
@@ -548,6 +521,9 @@ struct hsddp_handle {
     // their count (0: the table is not read), staging of a fill, staging of a host grid / map of hsddp_touchdown_from_terrain.  Freed by hsddp_destroy.
     double* d_tdh = nullptr; std::vector<char> td_own; int td_n = 0; std::vector<double> td_stage;
     double* d_td_H = nullptr; size_t td_H_cap = 0; int* d_td_map = nullptr;
+    // per-problem cost-weight scales (hsddp_weights.h, weights_host.hpp): the block [2][batch][84] (table | staging of a host source), whether the
+    // table is in use, and the window (window_gen) for which d_tdh holds every phase's ground_height for the scaled terminal programs (-1: none)
+    double* d_ws = nullptr; bool ws_on = false; int td_shared_gen = -1;
     ProbState* d_st = nullptr;
     double* d_x0 = nullptr;
     SlotArrays sa{};
@@ -570,6 +546,7 @@ struct hsddp_handle {
     bool timing = true;
 };
 
+static int td_ensure(hsddp_handle* h); static int td_fill(hsddp_handle* h, int p0, int p1); static int ws_tdh_ready(hsddp_handle* h);      // touchdown_host.hpp, weights_host.hpp
 static int kid(hsddp_handle* h, const char* n) {
     for (size_t i = 0; i < h->kname.size(); i++) if (h->kname[i] == n) return (int)i;
     h->kname.push_back(n); h->kms.push_back(0); h->kcnt.push_back(0); return (int)h->kname.size() - 1;
@@ -646,7 +623,7 @@ void hsddp_destroy(hsddp_handle_t* h) {
     if (h->d_cmd) hipFree(h->d_cmd);
     if (h->d_cmd_map) hipFree(h->d_cmd_map);
     if (h->d_cmd_status) hipFree(h->d_cmd_status);
-    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out, h->d_refs, h->d_refs_stage, h->d_tdh, h->d_td_H, h->d_td_map}; for (void* q : p) if (q) hipFree(q); }
+    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out, h->d_refs, h->d_refs_stage, h->d_tdh, h->d_td_H, h->d_td_map, h->d_ws}; for (void* q : p) if (q) hipFree(q); }
     for (auto e : h->pool) hipEventDestroy(e);
     if (h->h_counters) hipHostFree(h->h_counters);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -827,7 +804,7 @@ int hsddp_reconfigure(hsddp_handle_t* h, int n_phases, const hsddp_phase_desc_t*
     h->td_own.assign(n_phases, 0); h->td_n = 0;                                         // ... and its descriptor's ground_height (hsddp_touchdown.h)
     if (h->d_cmd_status) { hipFree(h->d_cmd_status); h->d_cmd_status = nullptr; }      // sized by the phase count
     HIPCK(hipGetLastError());
-    return HSDDP_OK;
+    return ws_tdh_ready(h);      // the scales (hsddp_weights.h) stay: their terminal programs read the new window's ground heights from the table
 }
 
 int hsddp_set_initial_condition(hsddp_handle_t* h, const double* x0) {
@@ -872,11 +849,32 @@ int hsddp_set_control_knot(hsddp_handle_t* h, int phase, int k, const double* u)
 // ---- launch helpers
 enum { UNIT_ROLLOUT = 0, UNIT_LQ = 1, UNIT_SWEEP = 2, UNIT_PROBE = 3 };
 static HistDev hist_of(hsddp_handle* h) { return HistDev{h->d_hist, h->hist_cap}; }
+// the table of per-problem cost-weight scales (hsddp_weights.h) if the launches of this window read it: one is set and a whole-body phase is there
+// to use it.  Null: the kernels of before, with the arguments of before.
+static const double* ws_table(hsddp_handle* h) {
+    if (!h->ws_on || h->f32 || h->has_hkd) return nullptr;
+    for (const PhaseDev& P : h->ph) if (P.model == HSDDP_MODEL_WB) return h->d_ws;
+    return nullptr;
+}
 static void launch_rollout_list(hsddp_handle* h, const EpsList& el, const SlotArrays& sa, const OptDev& o, int mask, const char* name, int unit = UNIT_ROLLOUT, const int* plist = nullptr, int nlist = 0) {
-    Timed t(h, name);
+    const double* wtab = ws_table(h);
+    if (wtab && ws_tdh_ready(h) != HSDDP_OK) { fprintf(stderr, "[hsddp_hip] %s: the touchdown-height table of the scaled kernels is not available, launch skipped\n", name); return; }
+    const std::string pw_name = wtab ? std::string(name) + "_pw" : std::string();      // (launches with scales are timed under their own names: k_rollout_pw, k_ls_probe_pw)
+    Timed t(h, wtab ? pw_name.c_str() : name);
     hipMemsetAsync(h->d_fail, 0, (size_t)h->batch * el.n * sizeof(int), h->stream);
     if (h->quad && o.MS && h->nq > 0) {      // whole-body running knots and the terminal knots behind them on lane quads, the rest on the one-wave programs
         const int nprob = plist ? nlist : h->batch, nbg = (nprob + 15) / 16;
+        if (wtab) {      // per-problem cost-weight scales: the three kernels' twins, the terminal programs with the heights compiled in (ws_tdh_ready)
+            launch_k_rollout_quad_pw((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
+                                     h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist, wtab);
+            if (h->n_term > 0)
+                launch_k_rollout_quad_term_pw((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
+                                              plist, nlist, h->d_tdh, wtab);
+            if (h->n_other > 0 && nprob > 0)
+                launch_k_rollout_pw((unsigned)((size_t)el.n * nprob * h->n_other), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
+                                    h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob, h->d_tdh, wtab);
+            return;
+        }
         launch_k_rollout_quad((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
                               h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist);
         const bool tdh = h->td_n > 0;      // a phase of the window has touchdown heights of its own (hsddp_touchdown.h): the terminal knots read the table
@@ -892,6 +890,11 @@ static void launch_rollout_list(hsddp_handle* h, const EpsList& el, const SlotAr
         else if (h->n_other > 0 && nprob > 0)      // (a window whose every slot is on lane quads launches no one-wave kernel at all)
             hipLaunchKernelGGL(k_rollout, dim3((unsigned)((size_t)el.n * nprob * h->n_other)), dim3(64), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
                                h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob);
+        return;
+    }
+    if (wtab) {
+        launch_k_rollout_pw((unsigned)((size_t)el.n * h->batch * h->nslots), h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
+                            h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph, (const int*)nullptr, h->batch, h->d_tdh, wtab);
         return;
     }
     if (h->td_n > 0 && !h->has_hkd) {      // (heights exist for whole-body phases only, and a window with a kinodynamic phase has none)
@@ -918,6 +921,11 @@ static int ensure_probe_arrays(hsddp_handle* h, int cands) {
     h->sp_cands = cands; return HSDDP_OK;
 }
 static void launch_lq(hsddp_handle* h, const OptDev& o, int mask) {
+    if (const double* wtab = ws_table(h)) {
+        Timed t(h, "k_lq_pw");
+        launch_k_lq_pw((unsigned)((size_t)h->batch * h->nslots), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask, h->cache_valid ? 1 : 0, h->d_units + UNIT_LQ, wtab);
+        return;
+    }
     Timed t(h, "k_lq");
     if (h->has_hkd) hipLaunchKernelGGL(k_lq_hkd, dim3((unsigned)((size_t)h->batch * h->nslots)), dim3(64), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask,
                                        0, h->d_units + UNIT_LQ);
@@ -1211,7 +1219,8 @@ int hsddp_export_solver_info(hsddp_handle_t* h, int problem, unsigned int* out) 
 // roofline figure of bench.py divides algorithmic bytes by what a launch really processed)
 int hsddp_get_kernel_units(hsddp_handle_t* h, const char* name, long long* units) {
     if (!h || !name || !units) return HSDDP_EINVAL;
-    const int id = !strcmp(name, "k_rollout") ? UNIT_ROLLOUT : !strcmp(name, "k_lq") ? UNIT_LQ : !strcmp(name, "k_sweep") ? UNIT_SWEEP : !strcmp(name, "k_ls_probe") ? UNIT_PROBE : -1;
+    const int id = (!strcmp(name, "k_rollout") || !strcmp(name, "k_rollout_pw")) ? UNIT_ROLLOUT : (!strcmp(name, "k_lq") || !strcmp(name, "k_lq_pw")) ? UNIT_LQ : !strcmp(name, "k_sweep") ? UNIT_SWEEP :
+                   (!strcmp(name, "k_ls_probe") || !strcmp(name, "k_ls_probe_pw")) ? UNIT_PROBE : -1;
     if (id < 0) return HSDDP_EINVAL;
     HIPCK(hipSetDevice(h->device));
     unsigned long long v = 0; HIPCK(hipMemcpy(&v, h->d_units + id, sizeof(v), hipMemcpyDeviceToHost));
@@ -1622,4 +1631,5 @@ int hsddp_get_references(hsddp_handle_t* h, int phase, int b0, int nb, double* x
 #include "sim_host.hpp"
 // ------------------------------------------------------------------------------------------------ per-problem touchdown heights (hsddp_touchdown.h)
 #include "touchdown_host.hpp"
+#include "weights_host.hpp"
 #endif

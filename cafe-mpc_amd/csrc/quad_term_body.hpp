@@ -12,9 +12,11 @@
 #define QUAD_WPE 1      // waves per SIMD the quad kernel is compiled for (1: up to 512 registers, nothing in scratch; 2: 256 registers)
 #endif
 constexpr int QS_DX = 72, QS_U = 144, QS_DU = 156, QS_KDX = 168, QS_RR = 180, QS_ROW = 268;
-template <bool TDH>
+// PW: per-problem cost-weight scales (hsddp_weights.h), wtab = the handle's table [batch][84]; the lane reads the row of its quad's problem (with TDH on).
+template <bool TDH, bool PW = false>
 __device__ __forceinline__ void quad_term_body(double* stage, const hs::PhaseDev* ph_, int nph, const int* slot_phase, const int* tslots, int nslots, int batch, hs::ModelDev md, EpsList el,
-                                               hs::OptDev opt, SlotArrays sa, const hs::ProbState* st, int mask, const int* plist, int nlist, const double* tdh) {
+                                               hs::OptDev opt, SlotArrays sa, const hs::ProbState* st, int mask, const int* plist, int nlist, const double* tdh, const double* wtab = nullptr) {
+    static_assert(!PW || TDH, "the scaled terminal program has the touchdown heights compiled in");
     using namespace hs;
     PhaseC* ph = (PhaseC*)ph_;
     const int nprob = plist != nullptr ? nlist : batch;
@@ -71,7 +73,9 @@ __device__ __forceinline__ void quad_term_body(double* stage, const hs::PhaseDev
         const QuadIn<const HS_LDS double*> in = {row, row + QS_DX, row + QS_U, row + QS_DU, row + QS_KDX, row + QS_RR};
         const double eps = el.from_state ? st[bc].ls_eps : el.e[c];
         QuadTermOut q;
-        if constexpr (TDH) q = wbq_rollout_terminal<QDL, true>(*Pc, hasn ? Nc : nullptr, md, bc, eps, opt.AL_active, c == el.writer, in, tdh + ((size_t)pi * batch + bc) * 4);
+        if constexpr (PW) q = wbq_rollout_terminal<QDL, true, true>(*Pc, hasn ? Nc : nullptr, md, bc, eps, opt.AL_active, c == el.writer, in, tdh + ((size_t)pi * batch + bc) * 4,
+                                                                    (hs::WsRow)wtab + (size_t)bc * hs::WS_ROW);
+        else if constexpr (TDH) q = wbq_rollout_terminal<QDL, true>(*Pc, hasn ? Nc : nullptr, md, bc, eps, opt.AL_active, c == el.writer, in, tdh + ((size_t)pi * batch + bc) * 4);
         else q = wbq_rollout_terminal<QDL>(*Pc, hasn ? Nc : nullptr, md, bc, eps, opt.AL_active, c == el.writer, in);
         if ((t & 3) == 0) {
             const size_t slot = ((size_t)c * batch + bc) * nslots + s;

@@ -39,3 +39,19 @@ void launch_k_rollout_tdh(unsigned grid, hipStream_t stream, const hs::PhaseDev*
 void launch_k_rollout_quad_term_tdh(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* tslots, int nslots, int batch,
                                     hs::ModelDev md, EpsList el, hs::OptDev opt, SlotArrays sa, const hs::ProbState* st, int mask, const int* plist, int nlist, const double* tdh);
 void launch_k_td_terrain(hipStream_t stream, const hs::PhaseDev* ph, int nph, int batch, const hs::TdGrid& g, double* out);
+
+// The kernels with per-problem cost-weight scales and the kernel that writes their table (hsddp_pw.hip, hsddp_weights.h); wtab: the handle's table
+// [batch][84].  Arguments otherwise those of k_rollout_tdh / k_rollout_quad / k_rollout_quad_term_tdh / k_lq.
+namespace hs { struct WsPack; }
+void launch_k_rollout_pw(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, hs::ModelDev md, EpsList el,
+                         hs::OptDev opt, const double* x0, SlotArrays sa, const hs::ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist,
+                         int unit_knots, const int* plist, int nprob, const double* tdh, const double* wtab);
+void launch_k_rollout_quad_pw(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, const int* slot_phase, const int* slot_k, const int* qslots, int nq, int nslots, int batch,
+                              hs::ModelDev md, EpsList el, hs::OptDev opt, const double* x0, SlotArrays sa, const hs::ProbState* st, int mask, int* fail, unsigned long long* units,
+                              const int* plist, int nlist, const double* wtab);
+void launch_k_rollout_quad_term_pw(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* tslots, int nslots, int batch,
+                                   hs::ModelDev md, EpsList el, hs::OptDev opt, SlotArrays sa, const hs::ProbState* st, int mask, const int* plist, int nlist, const double* tdh,
+                                   const double* wtab);
+void launch_k_lq_pw(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, hs::ModelDev md, hs::OptDev opt,
+                    const hs::ProbState* st, int mask, int use_cache, unsigned long long* units, const double* wtab);
+void launch_k_pack_weights(hipStream_t stream, const hs::WsPack& W);

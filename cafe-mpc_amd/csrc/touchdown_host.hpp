@@ -10,6 +10,8 @@
 #include "hsddp_touchdown.h"
 #include "touchdown.hpp"
 
+static int ws_tdh_ready(hsddp_handle* h);      // weights_host.hpp
+
 static hs::TdHandleInfo td_info(const hsddp_handle* h) { return hs::TdHandleInfo{h->nph, h->batch, h->f32 ? 1 : 0}; }
 static std::vector<hs::TdPhaseInfo> td_phases(const hsddp_handle* h) {
     std::vector<hs::TdPhaseInfo> v(h->nph);
@@ -42,7 +44,7 @@ static int td_from_grid(hsddp_handle* h, const hs::TdGrid& g) {
     }
     HIPCK(hipGetLastError());
     for (int i = 0; i < h->nph; i++) h->td_own[i] = (h->ph[i].model == HSDDP_MODEL_WB && h->ph[i].nt > 0) ? 1 : 0;
-    h->td_n = n;
+    h->td_n = n; h->td_shared_gen = -1;
     return HSDDP_OK;
 }
 
@@ -58,6 +60,7 @@ int hsddp_touchdown_set(hsddp_handle_t* h, int phase, int b0, int nb, const doub
     HIPCK(hipMemcpyAsync(dst, heights, (size_t)nb * 4 * sizeof(double), src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));      // the new heights are in place on return; a host source may be reused
     if (!h->td_own[phase]) { h->td_own[phase] = 1; h->td_n++; }
+    h->td_shared_gen = -1;      // (weights_host.hpp: the table no longer holds the shared value in every row)
     return HSDDP_OK;
 }
 
@@ -87,7 +90,7 @@ int hsddp_touchdown_clear(hsddp_handle_t* h, int phase) {
     if ((int)h->td_own.size() != h->nph || h->td_n == 0) return HSDDP_OK;
     if (phase >= 0 && !h->td_own[phase]) return HSDDP_OK;
     HIPCK(hipSetDevice(h->device));
-    if (phase < 0 || h->td_n == 1) { h->td_own.assign(h->nph, 0); h->td_n = 0; return HSDDP_OK; }
+    if (phase < 0 || h->td_n == 1) { h->td_own.assign(h->nph, 0); h->td_n = 0; return ws_tdh_ready(h); }      // (scales in use: their terminal programs go on reading the table)
     { const int rc = td_fill(h, phase, phase + 1); if (rc) return rc; }      // other phases keep theirs: this one reads the shared value from the table
     h->td_own[phase] = 0; h->td_n--;
     return HSDDP_OK;

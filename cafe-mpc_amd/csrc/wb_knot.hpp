@@ -557,9 +557,10 @@ HD void store_image(DST dst, int tid, F f) {
 
 // -------------------------------------------------------------------------------------------------------
 // Rollout of one knot k < h of problem b.   eps: line-search step.
-template <int NT>
+// PW: the problem's own cost-weight scales (hsddp_weights.h), ws = its row sq[36] | sr[12] | sqf[36]: q[j] sq[j] and r[j] sr[j] stand where q[j], r[j] stand.
+template <int NT, bool PW = false>
 HD void wb_rollout_knot(WbCore& L, PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active,
-                        const double* x0, SlotOut so, size_t slot, int* fail_flag, bool ss = false, bool wr = true) {
+                        const double* x0, SlotOut so, size_t slot, int* fail_flag, bool ss = false, bool wr = true, WsRow ws = nullptr) {
     // wr = false: a PROBE of the step length eps (one candidate of a batched line-search launch): only the per-slot partials of the merit
     // function (cost, defect^2, min g, max |h|) and the divergence flag leave the wave, no trajectory / cache store
     // ss: knot of a phase WITHOUT shooting nodes (SS_set empty, a phase the receding-horizon update has just created,
@@ -587,7 +588,8 @@ HD void wb_rollout_knot(WbCore& L, PhaseC& P, const ModelDev& md, int b, int k, 
         const double* pe = g == 0 ? P.dX + kx + (ss ? 0 : 36) + i : g == 1 ? P.dU + ku + i : rr;
         double va = *pa, vb = *pb, vc = *pc, vd = *pd, ve = *pe;
         const double* pw = tid < 36 ? &P.q[tid] : &P.r[tid < 48 ? tid - 36 : 0];      // (one load: two would wait for each other where they merge)
-        const double vw = *pw;
+        double vw = *pw;
+        if constexpr (PW) vw = vw * ws[tid < 48 ? tid : 36];      // (the row is sq | sr: entry tid of it belongs to weight tid of q | r)
         double er[2], dr[2];
         _Pragma("unroll") for (int q = 0; q < 2; q++) { const int c = q * NT + tid; er[q] = (c < P.ng) ? P.eps[kk * P.ng + c] : 0.0; dr[q] = (c < P.ng) ? P.delta[kk * P.ng + c] : 0.0; }
         if (ss) { Late& lt = late[HS_LANE(tid)]; _Pragma("unroll") for (int q = 0; q < 7; q++) { const int e = q * NT + tid; lt.kr[q] = (e < 432) ? P.K[kk * 432 + e] : 0.0; } }
@@ -710,9 +712,12 @@ HD void wb_rollout_knot(WbCore& L, PhaseC& P, const ModelDev& md, int b, int k, 
 }
 
 // terminal cost without AL (tracking + foot-place reg (x1) + touchdown-velocity penalty). MHPCCost.cpp:67-87,255-268
-HD double wb_terminal_cost_base(PhaseC& P, const WbCore& L, int b) {
+template <bool PW = false>
+HD double wb_terminal_cost_base(PhaseC& P, const WbCore& L, int b, WsRow ws = nullptr) {
     const int h = P.h; const size_t rw = ref_row(P, b, h);
-    double s = 0; for (int i = 0; i < 36; i++) { double d = L.x[i] - P.xr[rw * 36 + i]; s += d * P.qf[i] * d; }
+    double s = 0;
+    if constexpr (PW) { for (int i = 0; i < 36; i++) { double d = L.x[i] - P.xr[rw * 36 + i]; const double w = P.qf[i] * ws[WS_QF + i]; s += d * w * d; } }
+    else for (int i = 0; i < 36; i++) { double d = L.x[i] - P.xr[rw * 36 + i]; s += d * P.qf[i] * d; }
     double Phi = 0.5 * s;
     const int* rc = P.ref_contact + rw * 4; const double* fp = P.foot_pos + rw * 12; const double* bp = P.body_pos + rw * 3;
     double l2 = 0, l5 = 0;
@@ -726,9 +731,10 @@ HD double wb_terminal_cost_base(PhaseC& P, const WbCore& L, int b) {
 
 // Terminal knot (k = h) of a phase: terminal constraint + cost, then the reset map into the next phase.
 // TDH: the touchdown feet are held to the problem's own heights tdh[0..4) (by leg, hsddp_touchdown.h) instead of the phase's ground_height.
-template <int NT, bool TDH = false>
+// PW: the tracking weights are qf[j] sqf[j] of the problem's scale row ws (hsddp_weights.h).
+template <int NT, bool TDH = false, bool PW = false>
 HD void wb_rollout_terminal(WbCore& L, PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active,
-                            SlotOut so, size_t slot, bool ss = false, bool wr = true, const double* tdh = nullptr) {
+                            SlotOut so, size_t slot, bool ss = false, bool wr = true, const double* tdh = nullptr, WsRow ws = nullptr) {
     const int h = P.h;
     const size_t kx = ((size_t)b * (h + 1) + h) * 36;
     HS_PHASE(NT, if (tid < 36) { double x = ss ? L.xnext[tid] : P.Xbar[kx + tid] + eps * P.dX[kx + tid]; L.x[tid] = x; if (wr) P.X[kx + tid] = x; }
@@ -736,7 +742,8 @@ HD void wb_rollout_terminal(WbCore& L, PhaseC& P, PhaseC* Pn, const ModelDev& md
     const bool impact = (Pn != nullptr) && P.has_impact;
     wb_terms<NT>(L, md, impact);
     HS_PHASE(NT, if (tid == 0) {
-        double pb = wb_terminal_cost_base(P, L, b); if (wr) P.Phibase[b] = pb;
+        double pb; if constexpr (PW) pb = wb_terminal_cost_base<true>(P, L, b, ws); else pb = wb_terminal_cost_base(P, L, b);
+        if (wr) P.Phibase[b] = pb;
         double maxh = 0, c = 0; int i = 0;
         for (int f = 0; f < 4; f++) if (P.td[f] && P.nt > 0) {
             double hh; if constexpr (TDH) hh = L.fpos[3 * f + 2] - tdh[f]; else hh = L.fpos[3 * f + 2] - P.ground_height;
@@ -912,8 +919,9 @@ HD void wb_cost_gram(WbLqLds& S, double* gvec) {
 // cache commit: which regions a round of NT elements (q) touches is known at compile time: no comparison chain per element
 #define KC_REGION(s_, e_, ptr_) if (NT * q + NT - 1 >= (s_) && NT * q < (e_)) { if (NT * q >= (s_) && NT * q + NT - 1 < (e_)) (ptr_)[i - (s_)] = v; else if (i >= (s_) && i < (e_)) (ptr_)[i - (s_)] = v; }
 // LQ approximation of knot k < h (recomputes the contact solve at the stored X,U like WBM.cpp:463)
-template <int NT>
-HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int reb_active, bool cached = false) {
+// PW: the problem's own cost-weight scales, as in wb_rollout_knot.
+template <int NT, bool PW = false>
+HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int reb_active, bool cached = false, WsRow ws = nullptr) {
     WbCore& L = S.c; WbDeriv& D = S.d;
     const int h = P.h; const double dt = P.dt;
     const size_t kx = ((size_t)b * (h + 1) + k) * 36, ku = ((size_t)b * h + k) * 12, kk = (size_t)b * h + k, rw = ref_row(P, b, k);
@@ -925,7 +933,8 @@ HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int 
         const double vt = (tid < 36) ? P.xr[rw * 36 + tid] : (tid < 48) ? P.ur[rw * 12 + tid - 36] : 0.0;
         const double vf = (tid < 12) ? P.foot_pos[rw * 12 + tid] : (tid < 15) ? P.body_pos[rw * 3 + tid - 12] : (tid < 19) ? (double)P.ref_contact[rw * 4 + tid - 15] : 0.0;
         const double vv = (tid < 12) ? P.foot_vel[rw * 12 + tid] : 0.0;
-        const double vw = (tid < 36) ? P.q[tid] : (tid < 48) ? P.r[tid - 36] : 0.0;
+        double vw = (tid < 36) ? P.q[tid] : (tid < 48) ? P.r[tid - 36] : 0.0;
+        if constexpr (PW) vw = vw * ws[tid < 48 ? tid : 0];
         double gr[2], dr[2], er[2];
         _Pragma("unroll") for (int q = 0; q < 2; q++) { const int c = q * NT + tid; const size_t gi = kk * P.ng + c; const bool in = c < P.ng; gr[q] = in ? P.g[gi] : 1.0; dr[q] = in ? P.delta[gi] : 1.0; er[q] = in ? P.eps[gi] : 0.0; }
         double r[KC_SIZE / NT];
@@ -1190,8 +1199,9 @@ HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int 
 }
 
 // Terminal partials of a phase (+ AL) and the reset-map partial Px (next_n x 36, column-major) if a phase follows.
-template <int NT>
-HD void wb_lq_terminal(WbLqLds& S, PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, int al_active) {
+// PW: the tracking weights are qf[j] sqf[j] of the problem's scale row ws, as in wb_rollout_terminal.
+template <int NT, bool PW = false>
+HD void wb_lq_terminal(WbLqLds& S, PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, int al_active, WsRow ws = nullptr) {
     WbCore& L = S.c; WbDeriv& D = S.d;
     const int h = P.h;
     const size_t kx = ((size_t)b * (h + 1) + h) * 36;
@@ -1203,9 +1213,11 @@ HD void wb_lq_terminal(WbLqLds& S, PhaseC& P, PhaseC* Pn, const ModelDev& md, in
     wb_cost_blocks<NT>(S, P, h, true);
     HS_PHASE(NT, if (tid < 36) {
         const int d = tid;
-        double px = P.qf[d] * (L.x[d] - L.tmp[d]);
+        double wf = P.qf[d];
+        if constexpr (PW) wf = wf * ws[WS_QF + d];
+        double px = wf * (L.x[d] - L.tmp[d]);
         px += wb_cost_column(D, L.Jall, L.dvel(), d, D.W + d);
-        double diag = P.qf[d];
+        double diag = wf;
         if (al_active && P.nt > 0) {   // compute_AL_partials (ConstraintsBase.h:412-425); hx[0:18] = J_foot,z (psi_dyn)
             int t = 0;
             for (int f = 0; f < 4; f++) if (P.td[f]) {

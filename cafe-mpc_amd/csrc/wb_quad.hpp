@@ -240,8 +240,10 @@ template <class PT> struct QuadIn { PT xbar, dx, ubar, du, kdx, rr; };
 //   stores: X, U, Y, Xsim, Defect, g, lbase, l and the contact-solve cache of the knot in the layout the LQ knot fetches (hs_types.hpp KC_*).
 //   wr must be uniform over the wave.
 //   in: the rows of the knot's step-independent inputs (QuadIn).
-template <class Q, class PT>
-HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr, const QuadIn<PT>& in) {
+//   PW: the problem's own cost-weight scales (hsddp_weights.h), ws = the row sq[36] | sr[12] | sqf[36] of the LANE's problem (it differs from quad to
+//   quad): the lane reads the twelve scales of the base entries and the nine of its own leg with the knot's first reads.
+template <class Q, bool PW = false, class PT>
+HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr, const QuadIn<PT>& in, WsRow ws = nullptr) {
     using S = typename Q::S;
     const bool WR = wr;
     const int h = P.h;
@@ -281,19 +283,26 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
         if (P.go_jspeed >= 0) { _Pragma("unroll") for (int j = 0; j < 6; j++) { const int o = (j < 3) ? j : 12 + j - 3; eS[j] = Q::ld(P.eps, gk + P.go_jspeed + o, 3); dS[j] = Q::ld(P.delta, gk + P.go_jspeed + o, 3); } }
         if (P.go_joint >= 0) { _Pragma("unroll") for (int j = 0; j < 6; j++) { const int o = (j < 3) ? j : 12 + j - 3; eJ[j] = Q::ld(P.eps, gk + P.go_joint + o, 3); dJ[j] = Q::ld(P.delta, gk + P.go_joint + o, 3); } }
         if (P.go_height >= 0) { eH = Q::ld(P.eps, gk + P.go_height, 0); dH_ = Q::ld(P.delta, gk + P.go_height, 0); }
+        S sqb[6], svb[6], sql[3], svl[3], sul[3];      // PW: scales of the base entries (positions, velocities) and of the lane's leg (positions, velocities, torques)
+        if constexpr (PW) {
+            _Pragma("unroll") for (int i = 0; i < 6; i++) { sqb[i] = Q::ld(ws, i, 0); svb[i] = Q::ld(ws, 18 + i, 0); }
+            _Pragma("unroll") for (int j = 0; j < 3; j++) { sql[j] = Q::ld(ws, 6 + j, 3); svl[j] = Q::ld(ws, 24 + j, 3); sul[j] = Q::ld(ws, WS_R + j, 3); }
+        }
         QP(0)      // first reads issued
         // running cost, tracking part (QuadraticTrackingCost): 0.5 (sum_x + sum_u) dt, formed like the wave kernel: l = 0.5 sx; l += 0.5 su; l *= dt
         S sxq = zero, suq = zero;
         _Pragma("unroll")
         for (int i = 0; i < 6; i++) {
             const S dq = qb[i] - xrb[i], dv = vb[i] - vrb[i];
-            sxq = sxq + w0 * (dq * P.q[i] * dq + dv * P.q[18 + i] * dv);
+            if constexpr (PW) { const S wq = P.q[i] * sqb[i], wv = P.q[18 + i] * svb[i]; sxq = sxq + w0 * (dq * wq * dq + dv * wv * dv); }
+            else sxq = sxq + w0 * (dq * P.q[i] * dq + dv * P.q[18 + i] * dv);
         }
         _Pragma("unroll")
         for (int j = 0; j < 3; j++) {
             const S dq = ql[j] - xrl[j], dv = vl_[j] - vrl[j], du = ul[j] - url[j];
             // the phase's weights of the lane's leg: scalars of the descriptor picked by the lane (a per-lane index would be a vector load from constant memory)
-            const S wq = Q::legc(P.q[6 + j], P.q[9 + j], P.q[12 + j], P.q[15 + j]), wv = Q::legc(P.q[24 + j], P.q[27 + j], P.q[30 + j], P.q[33 + j]), wu = Q::legc(P.r[j], P.r[3 + j], P.r[6 + j], P.r[9 + j]);
+            S wq = Q::legc(P.q[6 + j], P.q[9 + j], P.q[12 + j], P.q[15 + j]), wv = Q::legc(P.q[24 + j], P.q[27 + j], P.q[30 + j], P.q[33 + j]), wu = Q::legc(P.r[j], P.r[3 + j], P.r[6 + j], P.r[9 + j]);
+            if constexpr (PW) { wq = wq * sql[j]; wv = wv * svl[j]; wu = wu * sul[j]; }
             sxq = sxq + (dq * wq * dq + dv * wv * dv);
             suq = suq + du * wu * du;
         }
@@ -780,11 +789,12 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     o.bad = (ns > 1e12) || !(ns == ns);      // ||Xsim|| > 1e6 (SinglePhase.cpp:205)
     return o;
 }
-template <class Q>
-HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr) {
+template <class Q, bool PW = false>
+HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr, WsRow ws = nullptr) {
     const size_t kx = ((size_t)b * (P.h + 1) + k) * 36, ku = ((size_t)b * P.h + k) * 12;
     const QuadIn<const HS_GLOBAL double*> in = {P.Xbar + kx, P.dX + kx, P.Ubar + ku, P.dU + ku, P.KdX + ku, P.rref + ref_row(P, b, k) * 80};
-    return wbq_rollout_knot<Q>(P, md, b, k, eps, reb_active, x0, wr, in);
+    if constexpr (PW) return wbq_rollout_knot<Q, true>(P, md, b, k, eps, reb_active, x0, wr, in, ws);
+    else return wbq_rollout_knot<Q>(P, md, b, k, eps, reb_active, x0, wr, in);
 }
 
 }  // namespace hs

@@ -30,8 +30,10 @@ struct QuadTermOut { double cost, dsq, maxh; };
 //   stores: X[h], Phibase, Phi, th and the successor's Xsim[0], Defect[0].  wr must be uniform over the wave.
 //   in: xbar / dx rows of 72 (knot h, then knot 0 of the successor - unread without one), rr: row h of the packed references.
 //   TDH: the lane's foot is held to the problem's own height tdh[leg] (hsddp_touchdown.h: tdh points at the problem's four) instead of ground_height.
-template <class Q, bool TDH = false, class PT>
-HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active, bool wr, const QuadIn<PT>& in, const double* tdh = nullptr) {
+//   PW: the tracking weights are qf[j] sqf[j] of the scale row ws of the lane's problem (hsddp_weights.h), read with the state.
+template <class Q, bool TDH = false, bool PW = false, class PT>
+HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active, bool wr, const QuadIn<PT>& in, const double* tdh = nullptr,
+                                    WsRow ws = nullptr) {
     using S = typename Q::S;
     const bool WR = wr;
     const int h = P.h;
@@ -49,6 +51,11 @@ HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, i
         }
     }
     const PT rr = in.rr;
+    S sqb[6], svb[6], sql[3], svl[3];      // PW: scales of the base entries (positions, velocities) and of the lane's leg
+    if constexpr (PW) {
+        _Pragma("unroll") for (int i = 0; i < 6; i++) { sqb[i] = Q::ld(ws, WS_QF + i, 0); svb[i] = Q::ld(ws, WS_QF + 18 + i, 0); }
+        _Pragma("unroll") for (int j = 0; j < 3; j++) { sql[j] = Q::ld(ws, WS_QF + 6 + j, 3); svl[j] = Q::ld(ws, WS_QF + 24 + j, 3); }
+    }
     // ---- terminal tracking cost (QuadraticTrackingCost, MHPCCost.cpp:67-87): needs the state only
     S Phi;
     {
@@ -56,12 +63,14 @@ HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, i
         _Pragma("unroll")
         for (int i = 0; i < 6; i++) {
             const S dq = qb[i] - Q::ld(rr, i, 0), dv = vb[i] - Q::ld(rr, 18 + i, 0);
-            sxq = sxq + w0 * (dq * P.qf[i] * dq + dv * P.qf[18 + i] * dv);
+            if constexpr (PW) { const S wq = P.qf[i] * sqb[i], wv = P.qf[18 + i] * svb[i]; sxq = sxq + w0 * (dq * wq * dq + dv * wv * dv); }
+            else sxq = sxq + w0 * (dq * P.qf[i] * dq + dv * P.qf[18 + i] * dv);
         }
         _Pragma("unroll")
         for (int j = 0; j < 3; j++) {
             const S dq = ql[j] - Q::ld(rr, 6 + j, 3), dv = vl_[j] - Q::ld(rr, 24 + j, 3);
-            const S wq = Q::legc(P.qf[6 + j], P.qf[9 + j], P.qf[12 + j], P.qf[15 + j]), wv = Q::legc(P.qf[24 + j], P.qf[27 + j], P.qf[30 + j], P.qf[33 + j]);
+            S wq = Q::legc(P.qf[6 + j], P.qf[9 + j], P.qf[12 + j], P.qf[15 + j]), wv = Q::legc(P.qf[24 + j], P.qf[27 + j], P.qf[30 + j], P.qf[33 + j]);
+            if constexpr (PW) { wq = wq * sql[j]; wv = wv * svl[j]; }
             sxq = sxq + (dq * wq * dq + dv * wv * dv);
         }
         Phi = 0.5 * Q::sum(sxq);
@@ -368,14 +377,14 @@ HD QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, i
 
 #ifdef HS_HOST_EMU
 // host form that gathers the rows from the phases' arrays (tests/_emu, one evaluation per knot)
-template <class Q, bool TDH = false>
-inline QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active, bool wr, const double* tdh = nullptr) {
+template <class Q, bool TDH = false, bool PW = false>
+inline QuadTermOut wbq_rollout_terminal(PhaseC& P, PhaseC* Pn, const ModelDev& md, int b, double eps, int al_active, bool wr, const double* tdh = nullptr, WsRow ws = nullptr) {
     double xb[72] = {0}, dx[72] = {0};
     const size_t kx = ((size_t)b * (P.h + 1) + P.h) * 36;
     for (int i = 0; i < 36; i++) { xb[i] = P.Xbar[kx + i]; dx[i] = P.dX[kx + i]; }
     if (Pn != nullptr) { const size_t nx = (size_t)b * (Pn->h + 1) * 36; for (int i = 0; i < 36; i++) { xb[36 + i] = Pn->Xbar[nx + i]; dx[36 + i] = Pn->dX[nx + i]; } }
     const QuadIn<const double*> in = {xb, dx, nullptr, nullptr, nullptr, P.rref + ref_row(P, b, P.h) * 80};
-    return wbq_rollout_terminal<Q, TDH>(P, Pn, md, b, eps, al_active, wr, in, tdh);
+    return wbq_rollout_terminal<Q, TDH, PW>(P, Pn, md, b, eps, al_active, wr, in, tdh, ws);
 }
 #endif
 

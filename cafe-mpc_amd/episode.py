@@ -385,7 +385,7 @@ class Episode:
         return t.value, a.value, i.value
 
 
-def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None, friction=None, plan_terrain=False, post_hook=None):
+def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None, friction=None, plan_terrain=False, post_hook=None, weight_scales=None):
     """The receding-horizon loop of MHPCLocomotion::update with the SIMULATED state fed back, for the whole batch.  solver: solved for the window
     `phases` of pd (builder.MHPCProblemData).  Per tick: episode.advance, pd.update(), builder.shift_solver_in_place, hook(tick, phases) - the
     place for solver.set_references - and solver.solve(opt_rt).  kicks: {tick: (kick_step, [B, 36])}.  episode: an Episode already reset; None
@@ -393,7 +393,9 @@ def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=No
     or int [B] is Episode.set_latency before the first tick (include/hsddp_latency.h: the loop moves the window by n_exec knots a tick, as that needs).
     friction: None leaves the episode as it is; a sim.Friction is Episode.set_friction before the first tick (it acts while the contact rule is on).
     plan_terrain: every tick, after the hook and before the solve, episode.plan_terrain() gives the new window the touchdown heights of the episode's
-    terrain (include/hsddp_touchdown.h); False plans onto the descriptors' ground_height.  post_hook(tick, phases) is called after the tick's solve.  Returns a dict: episode, phases (the last
+    terrain (include/hsddp_touchdown.h); False plans onto the descriptors' ground_height.  post_hook(tick, phases) is called after the tick's solve.
+    weight_scales: None leaves the solver as it is; (sq, sr, sqf) is Solver.set_weight_scales before the first tick (include/hsddp_weights.h) - set once,
+    the scales stay across the ticks' reconfigures; the episode's track_cost goes on using the descriptors' weights.  Returns a dict: episode, phases (the last
     window), n_iters / n_ls_iters / n_reg_iters / cost [n_ticks, B], alive [n_ticks]."""
     from . import builder
     if episode is None:
@@ -403,6 +405,8 @@ def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=No
         episode.set_latency(delay)
     if friction is not None:
         episode.set_friction(friction)
+    if weight_scales is not None:
+        solver.set_weight_scales(*weight_scales)
     out = dict(n_iters=[], n_ls_iters=[], n_reg_iters=[], cost=[], alive=[])
     for t in range(n_ticks):
         d, k = dist, None

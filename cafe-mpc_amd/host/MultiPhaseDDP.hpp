@@ -29,6 +29,7 @@
 #include "hsddp_episode.h"
 #include "hsddp_latency.h"
 #include "hsddp_touchdown.h"
+#include "hsddp_weights.h"
 
 namespace hsddp {
 
@@ -295,6 +296,14 @@ public:
     bool plan_terrain(const hsddp_terrain_t& t, const double* H, const int* map_of = nullptr, double z_ground = 0.0, bool src_device = false) {
         rc_ = hsddp_touchdown_from_terrain(h_, &t, H, map_of, z_ground, src_device ? 1 : 0); return rc_ == HSDDP_OK;
     }
+    // per-problem cost-weight scales (include/hsddp_weights.h): scales [nb][84] = sq[36] | sr[12] | sqf[36] for problems [b0, b0+nb) (host memory, or
+    // device memory with src_device) - in every whole-body phase problem b plans with q * sq, r * sr and qf * sqf; they stay across reconfigure.
+    // weight_scales: the rows in use (ones when none are set); clear: the kernels of a handle that never had scales.
+    bool set_weight_scales(const double* scales, int nb, int b0 = 0, bool src_device = false) {
+        rc_ = hsddp_weights_set(h_, b0, nb, scales, src_device ? 1 : 0); return rc_ == HSDDP_OK;
+    }
+    bool weight_scales(double* scales, int b0, int nb) { rc_ = hsddp_weights_get(h_, b0, nb, scales); return rc_ == HSDDP_OK; }
+    bool clear_weight_scales() { rc_ = hsddp_weights_clear(h_); return rc_ == HSDDP_OK; }
     // one-off closed-loop rollouts of the current policy, u = Ubar + K (x - Xbar), from n_samples initial states per problem over the first
     // n_steps whole-body control knots (x0: batch x n_samples x 36) - what the controller side of the reference does one state at a time
     // (MHPC/MHPC-Trajopt/test/testTrajOptInLoop.cpp).  An MPC loop keeps a hsddp::Simulation instead.  libhsddp_hip.so only.
