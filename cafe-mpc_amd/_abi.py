@@ -513,6 +513,62 @@ def pack_weight_scales(sq, sr, sqf, nb=None):
     return np.ascontiguousarray(np.concatenate([np.broadcast_to(a, (rows, a.shape[1])) for a in parts], axis=1))
 
 
+# include/hsddp_limits.h: per-problem constraint limits of whole-body phases (libhsddp_hip.so only)
+LIMITS_EXPORTS = ["hsddp_limits_set", "hsddp_limits_get", "hsddp_limits_clear", "hsddp_episode_plan_friction"]
+LIMITS_ROW = 12      # torque_limit | joint_lb[3] | joint_ub[3] | h_min | mu | jointspeed_lb | jointspeed_ub | pad
+LIMITS_FIELDS = {"torque_limit": (0, 1), "joint_lb": (1, 3), "joint_ub": (4, 3), "h_min": (7, 1), "mu": (8, 1), "jointspeed_lb": (9, 1), "jointspeed_ub": (10, 1)}
+
+
+def bind_limits(lib):
+    """Attach argtypes/restypes for the entry points of include/hsddp_limits.h.  Raises if the library lacks any."""
+    missing = [s for s in LIMITS_EXPORTS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"library lacks the constraint-limit entry points {missing}")
+    H = C.c_void_p
+    lib.hsddp_limits_set.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.hsddp_limits_get.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.hsddp_limits_clear.argtypes = [H]
+    lib.hsddp_episode_plan_friction.argtypes = [H, C.c_double]
+    for s in LIMITS_EXPORTS:
+        getattr(lib, s).restype = C.c_int
+    return lib
+
+
+def pack_limits(nb=None, **fields):
+    """Rows [nb, 12] from keyword arguments named like LIMITS_FIELDS: each None (NaN: the descriptor's value), a scalar (joint_lb / joint_ub: or one
+    [3]) that is broadcast to nb problems, or a per-problem array [nb] ([nb, 3])."""
+    unknown = set(fields) - set(LIMITS_FIELDS)
+    if unknown:
+        raise ValueError(f"unknown limits {sorted(unknown)}")
+    vals, rows = {}, 1 if nb is None else nb
+    for n, v in fields.items():
+        if v is None:
+            continue
+        w = LIMITS_FIELDS[n][1]
+        a = np.asarray(v, dtype=np.float64)
+        if w == 1:
+            if a.ndim > 1:
+                raise ValueError(f"{n}: shape {a.shape}, need a scalar or [nb]")
+            a = a.reshape(-1, 1)
+        else:
+            if a.ndim == 0:
+                a = np.full((1, w), float(a))
+            elif a.ndim == 1 and a.shape[0] == w:
+                a = a.reshape(1, w)
+            if a.ndim != 2 or a.shape[1] != w:
+                raise ValueError(f"{n}: shape {a.shape}, need a scalar, [{w}] or [nb, {w}]")
+        vals[n] = a
+        if nb is None:
+            rows = max(rows, a.shape[0])
+    out = np.full((rows, LIMITS_ROW), np.nan)
+    for n, a in vals.items():
+        if a.shape[0] not in (1, rows):
+            raise ValueError(f"{n}: {a.shape[0]} rows, need 1 or {rows}")
+        o, w = LIMITS_FIELDS[n]
+        out[:, o:o + w] = a
+    return out
+
+
 def _dp(a):
     return a.ctypes.data_as(DP)
 
@@ -823,6 +879,39 @@ class Solver:
     def clear_weight_scales(self):
         """Back to the descriptors' weights for every problem: the kernels of a handle that never had scales."""
         self._ck(bind_weights(self.lib).hsddp_weights_clear(self.h), "weights_clear")
+
+    def set_limits(self, torque_limit=None, joint_lb=None, joint_ub=None, h_min=None, mu=None, jointspeed_lb=None, jointspeed_ub=None, b0=0, nb=None):
+        """Constraint limits of problems b0 .. b0+nb-1 (include/hsddp_limits.h): in every whole-body phase problem b plans with its own torque limit,
+        joint and joint-speed box, minimum height and friction coefficient - absolute values.  Each argument: None (the descriptors' value goes on
+        being used), a scalar for all nb problems, or a per-problem array [nb] (joint_lb / joint_ub: [3] or [nb, 3]); nb defaults to the arrays'
+        length, or b0 to the end of the batch when every argument is a scalar.  A float64 torch tensor [nb, 12] on the handle's device passed as
+        torque_limit (everything else None) is read in place as whole rows, NaN where unset.  The limits stay across reconfigure."""
+        lib = bind_limits(self.lib)
+        rest = (joint_lb, joint_ub, h_min, mu, jointspeed_lb, jointspeed_ub)
+        if type(torque_limit).__module__.startswith("torch"):
+            import torch
+            t = torque_limit
+            if any(a is not None for a in rest) or t.dtype != torch.float64 or not t.is_contiguous() or t.device.type != "cuda" or t.dim() != 2 or t.shape[1] != LIMITS_ROW:
+                raise ValueError("set_limits: a device source is one contiguous float64 tensor [nb, 12] on the handle's device (every other argument None)")
+            self._ck(lib.hsddp_limits_set(self.h, b0, t.shape[0], t.data_ptr(), 1), "limits_set")
+            return
+        fields = dict(torque_limit=torque_limit, joint_lb=joint_lb, joint_ub=joint_ub, h_min=h_min, mu=mu, jointspeed_lb=jointspeed_lb, jointspeed_ub=jointspeed_ub)
+        rows = pack_limits(nb=nb, **fields)
+        if nb is None and rows.shape[0] == 1:
+            rows = np.ascontiguousarray(np.broadcast_to(rows, (self.batch - b0, LIMITS_ROW)))
+        self._ck(lib.hsddp_limits_set(self.h, b0, rows.shape[0], rows.ctypes.data, 0), "limits_set")
+
+    def limits(self, phase, b0=0, nb=None):
+        """The limits in use in `phase` for problems b0 .. b0+nb-1, a dict of arrays named like set_limits' arguments ([nb], joint_lb / joint_ub
+        [nb, 3]): the descriptor's values where nothing is set."""
+        nb = self.batch - b0 if nb is None else nb
+        rows = np.zeros((max(nb, 0), LIMITS_ROW))
+        self._ck(bind_limits(self.lib).hsddp_limits_get(self.h, phase, b0, nb, rows.ctypes.data), "limits_get")
+        return {n: (rows[:, o].copy() if w == 1 else rows[:, o:o + w].copy()) for n, (o, w) in LIMITS_FIELDS.items()}
+
+    def clear_limits(self):
+        """Back to the descriptors' limits for every problem: the kernels of a handle that never had limits."""
+        self._ck(bind_limits(self.lib).hsddp_limits_clear(self.h), "limits_clear")
 
     def plan_terrain(self, terrain, map_of=None, z_ground=0.0):
         """Touchdown heights of every whole-body phase with a touchdown constraint from a sim.Terrain: z_ground + the grid's height at the phase's

@@ -90,6 +90,12 @@ using PhaseC = const HS_CONST PhaseDev;
 constexpr int WS_R = 36, WS_QF = 48, WS_ROW = 84;
 using WsRow = const HS_CONST double*;
 
+// Per-problem constraint limits (hsddp_limits.h): one RESOLVED row of LIM_ROW doubles per (phase, problem),
+// torque_limit | joint_lb[3] | joint_ub[3] | h_min | mu | jspeed_lb | jspeed_ub | pad - the values the knot uses where it used the descriptor's, with
+// nothing left to decide (k_pack_limits put the descriptor's value wherever the user's row holds NaN).  Seen like a scale row.
+constexpr int LIM_TORQUE = 0, LIM_JLB = 1, LIM_JUB = 4, LIM_HMIN = 7, LIM_MU = 8, LIM_JSLB = 9, LIM_JSUB = 10, LIM_ROW = 12;
+using LimRow = const HS_CONST double*;
+
 // ReB parameter group of path constraint c (index into reb_init)
 HDH int constraint_group(const PhaseDev& P, int c) {
     if (P.go_torque >= 0 && c >= P.go_torque && c < P.go_torque + 24) return 0;

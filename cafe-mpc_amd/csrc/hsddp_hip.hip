@@ -30,6 +30,7 @@
 #include "hsddp_latency.h"
 #include "hsddp_touchdown.h"
 #include "hsddp_weights.h"
+#include "hsddp_limits.h"
 #include "hs_types.hpp"
 #include "hs_host.hpp"
 #include "wb_knot.hpp"
@@ -113,6 +114,11 @@ __global__ void __launch_bounds__(64) ROLL_HKD_ATTR k_rollout_hkd(ROLL_ARGS) { _
 // here); the prototypes are in rollout_args.hpp either way.
 #ifndef HS_PW_SEPARATE
 #include "hsddp_pw.hip"
+#endif
+// k_rollout_lim, k_rollout_quad_lim, k_lq_lim, k_pack_limits and k_lim_friction (hsddp_limits.h) and their launchers, likewise (-DHS_LIM_SEPARATE here;
+// a build with -DHS_PW_SEPARATE compiles hsddp_lim.hip on its own as well); the prototypes are in rollout_args.hpp either way.
+#if !defined(HS_LIM_SEPARATE) && !defined(HS_PW_SEPARATE)
+#include "hsddp_lim.hip"
 #endif
 
 // Batched line search, decision step (MultiPhaseDDP::line_search, MultiPhaseDDP.cpp:108-131, for the candidates of one probe launch): per
@@ -524,6 +530,10 @@ struct hsddp_handle {
     // per-problem cost-weight scales (hsddp_weights.h, weights_host.hpp): the block [2][batch][84] (table | staging of a host source), whether the
     // table is in use, and the window (window_gen) for which d_tdh holds every phase's ground_height for the scaled terminal programs (-1: none)
     double* d_ws = nullptr; bool ws_on = false; int td_shared_gen = -1;
+    // per-problem constraint limits (hsddp_limits.h, limits_host.hpp): ONE block, user [batch][12] | staging [batch][12] | resolved [nph_cap][batch][12] |
+    // descriptor rows [nph_cap][12] | ones [batch][84] (the scale table of the _lim kernels while no scales are set); whether the table is in use; the
+    // host copy of the descriptor rows that k_pack_limits resolves against
+    double* d_lim = nullptr; bool lim_on = false; std::vector<double> lim_desc;
     ProbState* d_st = nullptr;
     double* d_x0 = nullptr;
     SlotArrays sa{};
@@ -547,6 +557,7 @@ struct hsddp_handle {
 };
 
 static int td_ensure(hsddp_handle* h); static int td_fill(hsddp_handle* h, int p0, int p1); static int ws_tdh_ready(hsddp_handle* h);      // touchdown_host.hpp, weights_host.hpp
+static int lim_repack(hsddp_handle* h);      // limits_host.hpp
 static int kid(hsddp_handle* h, const char* n) {
     for (size_t i = 0; i < h->kname.size(); i++) if (h->kname[i] == n) return (int)i;
     h->kname.push_back(n); h->kms.push_back(0); h->kcnt.push_back(0); return (int)h->kname.size() - 1;
@@ -623,7 +634,7 @@ void hsddp_destroy(hsddp_handle_t* h) {
     if (h->d_cmd) hipFree(h->d_cmd);
     if (h->d_cmd_map) hipFree(h->d_cmd_map);
     if (h->d_cmd_status) hipFree(h->d_cmd_status);
-    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out, h->d_refs, h->d_refs_stage, h->d_tdh, h->d_td_H, h->d_td_map, h->d_ws}; for (void* q : p) if (q) hipFree(q); }
+    { void* p[] = {h->d_hkd_map, h->d_hkd_status, h->d_hkd_pf, h->d_hkd_out, h->d_refs, h->d_refs_stage, h->d_tdh, h->d_td_H, h->d_td_map, h->d_ws, h->d_lim}; for (void* q : p) if (q) hipFree(q); }
     for (auto e : h->pool) hipEventDestroy(e);
     if (h->h_counters) hipHostFree(h->h_counters);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -804,7 +815,8 @@ int hsddp_reconfigure(hsddp_handle_t* h, int n_phases, const hsddp_phase_desc_t*
     h->td_own.assign(n_phases, 0); h->td_n = 0;                                         // ... and its descriptor's ground_height (hsddp_touchdown.h)
     if (h->d_cmd_status) { hipFree(h->d_cmd_status); h->d_cmd_status = nullptr; }      // sized by the phase count
     HIPCK(hipGetLastError());
-    return ws_tdh_ready(h);      // the scales (hsddp_weights.h) stay: their terminal programs read the new window's ground heights from the table
+    { const int rc = ws_tdh_ready(h); if (rc) return rc; }      // the scales (hsddp_weights.h) stay: their terminal programs read the new window's ground heights from the table
+    return lim_repack(h);      // the limits (hsddp_limits.h) stay: their rows are resolved against the new window's descriptors (one launch, nothing while no table is set)
 }
 
 int hsddp_set_initial_condition(hsddp_handle_t* h, const double* x0) {
@@ -856,7 +868,47 @@ static const double* ws_table(hsddp_handle* h) {
     for (const PhaseDev& P : h->ph) if (P.model == HSDDP_MODEL_WB) return h->d_ws;
     return nullptr;
 }
+// the resolved table of per-problem constraint limits (hsddp_limits.h) if the launches of this window read it, under the same rule; lim_wtab: the scale
+// table its kernels read with it - the handle's, or ones while no scales are set (x * 1.0 is exact)
+static size_t lim_off_res(const hsddp_handle* h) { return 2 * (size_t)h->batch * LIM_ROW; }
+static size_t lim_off_desc(const hsddp_handle* h) { return lim_off_res(h) + (size_t)h->nph_cap * h->batch * LIM_ROW; }
+static size_t lim_off_ones(const hsddp_handle* h) { return lim_off_desc(h) + (size_t)h->nph_cap * LIM_ROW; }
+static const double* lim_table(hsddp_handle* h) {
+    if (!h->lim_on || h->f32 || h->has_hkd) return nullptr;
+    for (const PhaseDev& P : h->ph) if (P.model == HSDDP_MODEL_WB) return h->d_lim + lim_off_res(h);
+    return nullptr;
+}
+static const double* lim_wtab(hsddp_handle* h) { return h->ws_on ? h->d_ws : h->d_lim + lim_off_ones(h); }
+static void launch_rollout_lim(hsddp_handle* h, const double* ltab, const EpsList& el, const SlotArrays& sa, const OptDev& o, int mask, const char* name, int unit, const int* plist, int nlist) {
+    if (ws_tdh_ready(h) != HSDDP_OK) { fprintf(stderr, "[hsddp_hip] %s: the touchdown-height table of the kernels with limits is not available, launch skipped\n", name); return; }
+    const double* wtab = lim_wtab(h);
+    const std::string lim_name = std::string(name) + "_lim";      // (timed under their own names: k_rollout_lim, k_ls_probe_lim)
+    Timed t(h, lim_name.c_str());
+    hipMemsetAsync(h->d_fail, 0, (size_t)h->batch * el.n * sizeof(int), h->stream);
+    if (h->quad && o.MS && h->nq > 0) {
+        const int nprob = plist ? nlist : h->batch, nbg = (nprob + 15) / 16;
+        launch_k_rollout_quad_lim((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
+                                  h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist, wtab, ltab);
+        // terminal knots on lane quads read no path-constraint limit: what they launch without limits (scaled, with heights, plain)
+        if (h->n_term > 0 && h->ws_on)
+            launch_k_rollout_quad_term_pw((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
+                                          plist, nlist, h->d_tdh, wtab);
+        else if (h->n_term > 0 && h->td_n > 0)
+            launch_k_rollout_quad_term_tdh((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
+                                           plist, nlist, h->d_tdh);
+        else if (h->n_term > 0)
+            launch_k_rollout_quad_term((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
+                                       plist, nlist);
+        if (h->n_other > 0 && nprob > 0)
+            launch_k_rollout_lim((unsigned)((size_t)el.n * nprob * h->n_other), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
+                                 h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob, h->d_tdh, wtab, ltab);
+        return;
+    }
+    launch_k_rollout_lim((unsigned)((size_t)el.n * h->batch * h->nslots), h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
+                         h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph, (const int*)nullptr, h->batch, h->d_tdh, wtab, ltab);
+}
 static void launch_rollout_list(hsddp_handle* h, const EpsList& el, const SlotArrays& sa, const OptDev& o, int mask, const char* name, int unit = UNIT_ROLLOUT, const int* plist = nullptr, int nlist = 0) {
+    if (const double* ltab = lim_table(h)) { launch_rollout_lim(h, ltab, el, sa, o, mask, name, unit, plist, nlist); return; }
     const double* wtab = ws_table(h);
     if (wtab && ws_tdh_ready(h) != HSDDP_OK) { fprintf(stderr, "[hsddp_hip] %s: the touchdown-height table of the scaled kernels is not available, launch skipped\n", name); return; }
     const std::string pw_name = wtab ? std::string(name) + "_pw" : std::string();      // (launches with scales are timed under their own names: k_rollout_pw, k_ls_probe_pw)
@@ -921,6 +973,12 @@ static int ensure_probe_arrays(hsddp_handle* h, int cands) {
     h->sp_cands = cands; return HSDDP_OK;
 }
 static void launch_lq(hsddp_handle* h, const OptDev& o, int mask) {
+    if (const double* ltab = lim_table(h)) {
+        Timed t(h, "k_lq_lim");
+        launch_k_lq_lim((unsigned)((size_t)h->batch * h->nslots), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask, h->cache_valid ? 1 : 0, h->d_units + UNIT_LQ,
+                        lim_wtab(h), ltab, h->batch);
+        return;
+    }
     if (const double* wtab = ws_table(h)) {
         Timed t(h, "k_lq_pw");
         launch_k_lq_pw((unsigned)((size_t)h->batch * h->nslots), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask, h->cache_valid ? 1 : 0, h->d_units + UNIT_LQ, wtab);
@@ -1219,8 +1277,8 @@ int hsddp_export_solver_info(hsddp_handle_t* h, int problem, unsigned int* out) 
 // roofline figure of bench.py divides algorithmic bytes by what a launch really processed)
 int hsddp_get_kernel_units(hsddp_handle_t* h, const char* name, long long* units) {
     if (!h || !name || !units) return HSDDP_EINVAL;
-    const int id = (!strcmp(name, "k_rollout") || !strcmp(name, "k_rollout_pw")) ? UNIT_ROLLOUT : (!strcmp(name, "k_lq") || !strcmp(name, "k_lq_pw")) ? UNIT_LQ : !strcmp(name, "k_sweep") ? UNIT_SWEEP :
-                   (!strcmp(name, "k_ls_probe") || !strcmp(name, "k_ls_probe_pw")) ? UNIT_PROBE : -1;
+    const int id = (!strcmp(name, "k_rollout") || !strcmp(name, "k_rollout_pw") || !strcmp(name, "k_rollout_lim")) ? UNIT_ROLLOUT : (!strcmp(name, "k_lq") || !strcmp(name, "k_lq_pw") || !strcmp(name, "k_lq_lim")) ? UNIT_LQ : !strcmp(name, "k_sweep") ? UNIT_SWEEP :
+                   (!strcmp(name, "k_ls_probe") || !strcmp(name, "k_ls_probe_pw") || !strcmp(name, "k_ls_probe_lim")) ? UNIT_PROBE : -1;
     if (id < 0) return HSDDP_EINVAL;
     HIPCK(hipSetDevice(h->device));
     unsigned long long v = 0; HIPCK(hipMemcpy(&v, h->d_units + id, sizeof(v), hipMemcpyDeviceToHost));
@@ -1632,4 +1690,5 @@ int hsddp_get_references(hsddp_handle_t* h, int phase, int b0, int nb, double* x
 // ------------------------------------------------------------------------------------------------ per-problem touchdown heights (hsddp_touchdown.h)
 #include "touchdown_host.hpp"
 #include "weights_host.hpp"
+#include "limits_host.hpp"
 #endif

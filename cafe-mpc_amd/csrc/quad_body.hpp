@@ -4,7 +4,8 @@
 // Text and not a function template like quad_term_body because k_rollout_quad has to keep compiling to the instructions it compiles to (its register
 // allocation fills the file at one wave per SIMD), and the same statements behind a call boundary come out of the optimiser in another order.
 // QUAD_BODY_PW (set by the includer, 0 or 1): per-problem cost-weight scales (hsddp_weights.h) - the kernel has one more parameter, wtab = the handle's
-// table [batch][84], and a lane reads the row of its own quad's problem.  No include guard on purpose; it needs wb_quad.hpp, rollout_args.hpp and
+// table [batch][84], and a lane reads the row of its own quad's problem.  QUAD_BODY_LIM (0 or 1, with QUAD_BODY_PW): per-problem constraint limits
+// (hsddp_limits.h) - one more parameter again, ltab = the handle's resolved table [phase][batch][12]; a lane reads row (phase, its problem).  No include guard on purpose; it needs wb_quad.hpp, rollout_args.hpp and
 // quad_term_body.hpp (QS_* row offsets) in front of the kernel.
     PhaseC* ph = (PhaseC*)ph_;
     __shared__ double stage[16 * QS_ROW];
@@ -65,7 +66,10 @@
         const HS_LDS double* row = (const HS_LDS double*)stage + ro;
         const QuadIn<const HS_LDS double*> in = {row, row + QS_DX, row + QS_U, row + QS_DU, row + QS_KDX, row + QS_RR};
         const double eps = el.from_state ? st[bc].ls_eps : el.e[c];
-#if QUAD_BODY_PW
+#if defined(QUAD_BODY_LIM) && QUAD_BODY_LIM
+        const QuadOut q = wbq_rollout_knot<QDL, true, true>(*Pc, md, bc, kc, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, c == el.writer, in, (WsRow)wtab + (size_t)bc * WS_ROW,
+                                                            (LimRow)ltab + ((size_t)pi * batch + bc) * LIM_ROW);
+#elif QUAD_BODY_PW
         const QuadOut q = wbq_rollout_knot<QDL, true>(*Pc, md, bc, kc, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, c == el.writer, in, (WsRow)wtab + (size_t)bc * WS_ROW);
 #else
         const QuadOut q = wbq_rollout_knot<QDL>(*Pc, md, bc, kc, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, c == el.writer, in);

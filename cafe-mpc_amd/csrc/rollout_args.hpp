@@ -55,3 +55,17 @@ void launch_k_rollout_quad_term_pw(unsigned grid, hipStream_t stream, const hs::
 void launch_k_lq_pw(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, hs::ModelDev md, hs::OptDev opt,
                     const hs::ProbState* st, int mask, int use_cache, unsigned long long* units, const double* wtab);
 void launch_k_pack_weights(hipStream_t stream, const hs::WsPack& W);
+
+// The kernels with per-problem constraint limits and the kernels that write their tables (hsddp_lim.hip, hsddp_limits.h); ltab: the handle's resolved
+// table [phase][batch][12].  Arguments otherwise those of k_rollout_pw / k_rollout_quad_pw / k_lq_pw.
+namespace hs { struct LimPack; struct LimMu; }
+void launch_k_rollout_lim(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, hs::ModelDev md, EpsList el,
+                          hs::OptDev opt, const double* x0, SlotArrays sa, const hs::ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist,
+                          int unit_knots, const int* plist, int nprob, const double* tdh, const double* wtab, const double* ltab);
+void launch_k_rollout_quad_lim(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, const int* slot_phase, const int* slot_k, const int* qslots, int nq, int nslots, int batch,
+                               hs::ModelDev md, EpsList el, hs::OptDev opt, const double* x0, SlotArrays sa, const hs::ProbState* st, int mask, int* fail, unsigned long long* units,
+                               const int* plist, int nlist, const double* wtab, const double* ltab);
+void launch_k_lq_lim(unsigned grid, hipStream_t stream, const hs::PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, hs::ModelDev md, hs::OptDev opt,
+                     const hs::ProbState* st, int mask, int use_cache, unsigned long long* units, const double* wtab, const double* ltab, int batch);
+void launch_k_pack_limits(hipStream_t stream, const hs::LimPack& W);
+void launch_k_lim_mu(hipStream_t stream, const hs::LimMu& F);

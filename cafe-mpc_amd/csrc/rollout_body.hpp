@@ -3,7 +3,9 @@
 // text used to stand.  TDH (default off): per-problem touchdown heights (hsddp_touchdown.h) - tdh is the window's table [phase][batch][4] and the
 // terminal knots of whole-body phases read their row of it instead of the descriptor's ground_height.  PW (default off): per-problem cost-weight
 // scales (hsddp_weights.h) - wtab is the handle's table [batch][84] and the whole-body knots of problem b read row b of it; the instantiation with PW
-// has TDH compiled in as well (hsddp_pw.hip).
+// has TDH compiled in as well (hsddp_pw.hip).  LIM (default off): per-problem constraint limits (hsddp_limits.h) - ltab is the handle's resolved table
+// [phase][batch][12] and the running knots of whole-body phase i of problem b read row (i, b) of it; the instantiation with LIM has PW and TDH
+// compiled in (hsddp_lim.hip).
 #pragma once
 #include "hsddp.h"
 #include "hs_types.hpp"
@@ -26,13 +28,17 @@ using namespace hs;
 // Used for the young phases the receding-horizon update creates (SS_set empty, MHPCProblem.cpp:340-351; first > 0, stops at the next
 // phase with shooting nodes) and for the whole horizon when option.MS is false (MultiPhaseDDP.cpp:65-68; first = 0, descriptors with
 // every shooting flag cleared).  On entry the state to start from is in L.xnext (whole-body phase) / in Xsim[0] of the phase (SRB, HKD).
-template <bool WBM, bool TDH = false, bool PW = false, class LDS> __device__ __forceinline__ void rollout_chain(LDS& L, PhaseC* ph, int nph, int first, const ModelDev& md, int b, int nslots, double eps, const OptDev& opt, SlotOut so,
-                                              size_t slot_base, int* fail, bool wr, const double* tdh = nullptr, int batch = 0, WsRow ws = nullptr) {
+template <bool WBM, bool TDH = false, bool PW = false, bool LIM = false, class LDS> __device__ __forceinline__ void rollout_chain(LDS& L, PhaseC* ph, int nph, int first, const ModelDev& md, int b, int nslots, double eps, const OptDev& opt, SlotOut so,
+                                              size_t slot_base, int* fail, bool wr, const double* tdh = nullptr, int batch = 0, WsRow ws = nullptr, const double* ltab = nullptr) {
     for (int pj = first; pj < nph && !ph[pj].shooting; pj++) {
         PhaseC& Q = ph[pj]; PhaseC* Qn = pj + 1 < nph ? &ph[pj + 1] : nullptr; const size_t s0 = slot_base + Q.slot0;
         if (WBM && Q.model == HSDDP_MODEL_WB) {
             if constexpr (WBM) {
-            if constexpr (PW) {
+            if constexpr (LIM) {
+                LimRow lim = (LimRow)ltab + ((size_t)pj * batch + b) * LIM_ROW;
+                for (int kq = 0; kq < Q.h; kq++) wb_rollout_knot<64, true, true>(L, Q, md, b, kq, eps, opt.ReB_active, nullptr, so, s0 + kq, fail, true, wr, ws, lim);
+                wb_rollout_terminal<64, true, true>(L, Q, Qn, md, b, eps, opt.AL_active, so, s0 + Q.h, true, wr, tdh + ((size_t)pj * batch + b) * 4, ws);
+            } else if constexpr (PW) {
                 for (int kq = 0; kq < Q.h; kq++) wb_rollout_knot<64, true>(L, Q, md, b, kq, eps, opt.ReB_active, nullptr, so, s0 + kq, fail, true, wr, ws);
                 wb_rollout_terminal<64, true, true>(L, Q, Qn, md, b, eps, opt.AL_active, so, s0 + Q.h, true, wr, tdh + ((size_t)pj * batch + b) * 4, ws);
             } else {
@@ -80,8 +86,9 @@ union RedLds { HkdLds h; SrbLds s; };
 // among them; plist / nprob: the problems this launch is for (null: all nprob = batch of them, `mask` picks)
 #define ROLL_ARGS const PhaseDev* ph_, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, ModelDev md, EpsList el, OptDev opt, const double* x0, SlotArrays sa, \
                   const ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist, int unit_knots, const int* plist, int nprob
-template <bool WBM, bool TDH = false, bool PW = false, class LDS> __device__ __forceinline__ void rollout_body(LDS& L, ROLL_ARGS, const double* tdh = nullptr, const double* wtab = nullptr) {
+template <bool WBM, bool TDH = false, bool PW = false, bool LIM = false, class LDS> __device__ __forceinline__ void rollout_body(LDS& L, ROLL_ARGS, const double* tdh = nullptr, const double* wtab = nullptr, const double* ltab = nullptr) {
     static_assert(!PW || (WBM && TDH), "the scaled program is the whole-body one with the touchdown heights compiled in");
+    static_assert(!LIM || PW, "the program with limits has the scales and the touchdown heights compiled in");
     PhaseC* ph = (PhaseC*)ph_;   // descriptors: constant memory, scalar loads
     const int per = nprob * nlist;
     int c, r; cand_unit(per, blockIdx.x, c, r);
@@ -117,6 +124,10 @@ template <bool WBM, bool TDH = false, bool PW = false, class LDS> __device__ __f
             SrbLds& Ls = *reinterpret_cast<SrbLds*>(&L);
             if (k < P.h) srb_rollout_knot<64>(Ls, P, b, k, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, so, slot, fail, false, wr);
             else srb_rollout_terminal<64>(Ls, P, Pn, b, eps, so, slot, false, wr);
+        } else if constexpr (LIM) {      // (b and pi are uniform over the wave: so are both row pointers)
+            WsRow ws = (WsRow)wtab + (size_t)b * WS_ROW;
+            if (k < P.h) wb_rollout_knot<64, true, true>(L, P, md, b, k, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, so, slot, fail, false, wr, ws, (LimRow)ltab + ((size_t)pi * batch + b) * LIM_ROW);
+            else wb_rollout_terminal<64, true, true>(L, P, Pn, md, b, eps, opt.AL_active, so, slot, false, wr, tdh + ((size_t)pi * batch + b) * 4, ws);
         } else if constexpr (PW) {      // (b comes from blockIdx: the row pointer is uniform over the wave)
             WsRow ws = (WsRow)wtab + (size_t)b * WS_ROW;
             if (k < P.h) wb_rollout_knot<64, true>(L, P, md, b, k, eps, opt.ReB_active, pi == 0 ? x0 : nullptr, so, slot, fail, false, wr, ws);
@@ -129,7 +140,8 @@ template <bool WBM, bool TDH = false, bool PW = false, class LDS> __device__ __f
     }
     // single-shooting phases from here on (young phases behind a terminal knot, or the whole horizon): ONE call site, one copy of the code
     if (chain_first >= 0 && chain_first < nph && !ph[chain_first].shooting) {
-        if constexpr (PW) rollout_chain<WBM, true, true>(L, ph, nph, chain_first, md, b, nslots, eps, opt, so, slot_base, fail, wr, tdh, batch, (WsRow)wtab + (size_t)b * WS_ROW);
+        if constexpr (LIM) rollout_chain<WBM, true, true, true>(L, ph, nph, chain_first, md, b, nslots, eps, opt, so, slot_base, fail, wr, tdh, batch, (WsRow)wtab + (size_t)b * WS_ROW, ltab);
+        else if constexpr (PW) rollout_chain<WBM, true, true>(L, ph, nph, chain_first, md, b, nslots, eps, opt, so, slot_base, fail, wr, tdh, batch, (WsRow)wtab + (size_t)b * WS_ROW);
         else if constexpr (TDH) rollout_chain<WBM, true>(L, ph, nph, chain_first, md, b, nslots, eps, opt, so, slot_base, fail, wr, tdh, batch);
         else rollout_chain<WBM>(L, ph, nph, chain_first, md, b, nslots, eps, opt, so, slot_base, fail, wr);
     }

@@ -506,7 +506,9 @@ HD double wb_constraint(PhaseC& P, const WbCore& L, int c) {
 // the same value by selects instead of one divergent region per constraint family (a single wave pays every region's LDS round trip):
 //   g = fma(a, v1, t2)   torque / speed / joint / height: a = +-1, v1 the state or control entry, t2 the bound;  GRF: a = mu (1 for the
 //   normal force), v1 = fz, t2 = +-fx / +-fy (0) — the same roundings as the expressions of wb_constraint
-HD double wb_constraint_sel(PhaseC& P, const WbCore& L, int c) {
+// LIM: the bounds and mu come from the problem's resolved limits row (hsddp_limits.h), each where the descriptor's value stands.
+template <bool LIM = false>
+HD double wb_constraint_sel(PhaseC& P, const WbCore& L, int c, LimRow lim = nullptr) {
     const double* w = reinterpret_cast<const double*>(&L);
     constexpr int OX = offsetof(WbCore, x) / 8, OU = offsetof(WbCore, u) / 8, OG = offsetof(WbCore, grf) / 8;
     const int it = c - P.go_torque, is = c - P.go_jspeed, ij = c - P.go_joint;
@@ -515,14 +517,16 @@ HD double wb_constraint_sel(PhaseC& P, const WbCore& L, int c) {
     const int i = bt ? it : bs ? is : ij, lo = i < 12 ? i : i - 12;           // entry inside a 24-block: lower-bound half / upper-bound half
     const bool up = i >= 12;
     const int a3 = lo % 3;
-    const double cj = up ? pick3(P.joint_ub, a3) : -pick3(P.joint_lb, a3);
-    const double c0 = bt ? P.torque_limit : bs ? (up ? P.jspeed_ub : -P.jspeed_lb) : bj ? cj : -P.h_min;
+    const double cj = LIM ? (up ? pick3(lim + LIM_JUB, a3) : -pick3(lim + LIM_JLB, a3)) : (up ? pick3(P.joint_ub, a3) : -pick3(P.joint_lb, a3));
+    const double c0 = LIM ? (bt ? lim[LIM_TORQUE] : bs ? (up ? lim[LIM_JSUB] : -lim[LIM_JSLB]) : bj ? cj : -lim[LIM_HMIN])
+                          : (bt ? P.torque_limit : bs ? (up ? P.jspeed_ub : -P.jspeed_lb) : bj ? cj : -P.h_min);
     const double sg = bt ? (up ? 1.0 : -1.0) : (bh || !up) ? 1.0 : -1.0;
     const int i1l = bt ? OU + lo : bs ? OX + 24 + lo : bj ? OX + 6 + lo : OX + 2;
     const int ig = lin ? 0 : c - P.go_grf, ga = ig / 5, gr = ig - 5 * ga, f = feet_of(P).pick(ga & 3);
     const int i1 = lin ? i1l : OG + 3 * f + 2, i2 = lin ? i1l : OG + 3 * f + (gr >= 3 ? 1 : 0);
     const double v1 = w[i1], v2 = w[i2];
-    const double a = lin ? sg : (gr == 0 ? 1.0 : P.mu);
+    double a;
+    if constexpr (LIM) a = lin ? sg : (gr == 0 ? 1.0 : lim[LIM_MU]); else a = lin ? sg : (gr == 0 ? 1.0 : P.mu);
     const double t2 = lin ? c0 : (gr == 0 ? 0.0 : ((gr == 1 || gr == 3) ? -v2 : v2));
     return hs_fma(a, v1, t2);
 }
@@ -558,9 +562,10 @@ HD void store_image(DST dst, int tid, F f) {
 // -------------------------------------------------------------------------------------------------------
 // Rollout of one knot k < h of problem b.   eps: line-search step.
 // PW: the problem's own cost-weight scales (hsddp_weights.h), ws = its row sq[36] | sr[12] | sqf[36]: q[j] sq[j] and r[j] sr[j] stand where q[j], r[j] stand.
-template <int NT, bool PW = false>
+// LIM: the problem's own constraint limits (hsddp_limits.h), lim = its resolved row for this phase: each entry stands where the descriptor's field stands.
+template <int NT, bool PW = false, bool LIM = false>
 HD void wb_rollout_knot(WbCore& L, PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active,
-                        const double* x0, SlotOut so, size_t slot, int* fail_flag, bool ss = false, bool wr = true, WsRow ws = nullptr) {
+                        const double* x0, SlotOut so, size_t slot, int* fail_flag, bool ss = false, bool wr = true, WsRow ws = nullptr, LimRow lim = nullptr) {
     // wr = false: a PROBE of the step length eps (one candidate of a batched line-search launch): only the per-slot partials of the merit
     // function (cost, defect^2, min g, max |h|) and the divergence flag leave the wave, no trajectory / cache store
     // ss: knot of a phase WITHOUT shooting nodes (SS_set empty, a phase the receding-horizon update has just created,
@@ -663,7 +668,8 @@ HD void wb_rollout_knot(WbCore& L, PhaseC& P, const ModelDev& md, int b, int k, 
     }
     double gmin = 0.0;     // this lane's share of min(0, min_c g_c); the partial minima are folded below (a minimum does not depend on the order)
     for (int c = tid; c < P.ng; c += NT) {
-        const double g = wb_constraint_sel(P, L, c), e = L.gval()[c], dl = L.bar()[c];
+        double g; if constexpr (LIM) g = wb_constraint_sel<true>(P, L, c, lim); else g = wb_constraint_sel(P, L, c);
+        const double e = L.gval()[c], dl = L.bar()[c];
         if (wr) P.g[kk * P.ng + c] = g;
         L.bar()[c] = e * reb_barrier1(g, dl); gmin = fmin(gmin, g);
     }
@@ -920,8 +926,9 @@ HD void wb_cost_gram(WbLqLds& S, double* gvec) {
 #define KC_REGION(s_, e_, ptr_) if (NT * q + NT - 1 >= (s_) && NT * q < (e_)) { if (NT * q >= (s_) && NT * q + NT - 1 < (e_)) (ptr_)[i - (s_)] = v; else if (i >= (s_) && i < (e_)) (ptr_)[i - (s_)] = v; }
 // LQ approximation of knot k < h (recomputes the contact solve at the stored X,U like WBM.cpp:463)
 // PW: the problem's own cost-weight scales, as in wb_rollout_knot.
-template <int NT, bool PW = false>
-HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int reb_active, bool cached = false, WsRow ws = nullptr) {
+// LIM: mu of the friction pyramid's partials comes from the problem's resolved limits row (the box limits have constant gradients: nothing else reads a limit here).
+template <int NT, bool PW = false, bool LIM = false>
+HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int reb_active, bool cached = false, WsRow ws = nullptr, LimRow lim = nullptr) {
     WbCore& L = S.c; WbDeriv& D = S.d;
     const int h = P.h; const double dt = P.dt;
     const size_t kx = ((size_t)b * (h + 1) + k) * 36, ku = ((size_t)b * h + k) * 12, kk = (size_t)b * h + k, rw = ref_row(P, b, k);
@@ -1078,7 +1085,7 @@ HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int 
             P.lu[kk * P.rs + i] = lu; T1[72 + i] = luu;
             double ly = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0; const int f = i / 3, r = i % 3; int a = -1; for (int t = 0; t < P.nc; t++) if (P.feet[t] == f) a = t;
             if (P.go_grf >= 0 && a >= 0) {
-                const double mu = P.mu;
+                double mu; if constexpr (LIM) mu = lim[LIM_MU]; else mu = P.mu;
                 for (int c = 0; c < 5; c++) {
                     const double r0 = (c == 1) ? -1.0 : (c == 2) ? 1.0 : 0.0, r1 = (c == 3) ? -1.0 : (c == 4) ? 1.0 : 0.0, r2 = (c == 0) ? 1.0 : mu;
                     const double rr = (r == 0) ? r0 : (r == 1) ? r1 : r2;
@@ -1182,7 +1189,7 @@ HD void wb_lq_knot(WbLqLds& S, PhaseC& P, const ModelDev& md, int b, int k, int 
         // y: grf pyramid rows [0 0 1; -1 0 mu; 1 0 mu; 0 -1 mu; 0 1 mu] for foot f = i/3
         double ly = 0.0; const int f = i / 3, r = i % 3; int a = -1; for (int t = 0; t < P.nc; t++) if (P.feet[t] == f) a = t;
         if (P.go_grf >= 0 && a >= 0) {
-            const double mu = P.mu;
+            double mu; if constexpr (LIM) mu = lim[LIM_MU]; else mu = P.mu;
             for (int c = 0; c < 5; c++) {
                 const double r0 = (c == 1) ? -1.0 : (c == 2) ? 1.0 : 0.0, r1 = (c == 3) ? -1.0 : (c == 4) ? 1.0 : 0.0, r2 = (c == 0) ? 1.0 : mu;
                 const double rr = (r == 0) ? r0 : (r == 1) ? r1 : r2;

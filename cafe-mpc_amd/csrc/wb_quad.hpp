@@ -242,8 +242,10 @@ template <class PT> struct QuadIn { PT xbar, dx, ubar, du, kdx, rr; };
 //   in: the rows of the knot's step-independent inputs (QuadIn).
 //   PW: the problem's own cost-weight scales (hsddp_weights.h), ws = the row sq[36] | sr[12] | sqf[36] of the LANE's problem (it differs from quad to
 //   quad): the lane reads the twelve scales of the base entries and the nine of its own leg with the knot's first reads.
-template <class Q, bool PW = false, class PT>
-HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr, const QuadIn<PT>& in, WsRow ws = nullptr) {
+//   LIM: the constraint limits of the LANE's problem (hsddp_limits.h), lim = its resolved row for this phase.  The box limits and h_min are read with
+//   the knot's first reads and die with the early barrier block; mu is read with the friction-pyramid parameters, behind the block factorisation.
+template <class Q, bool PW = false, bool LIM = false, class PT>
+HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr, const QuadIn<PT>& in, WsRow ws = nullptr, LimRow lim = nullptr) {
     using S = typename Q::S;
     const bool WR = wr;
     const int h = P.h;
@@ -288,6 +290,11 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
             _Pragma("unroll") for (int i = 0; i < 6; i++) { sqb[i] = Q::ld(ws, i, 0); svb[i] = Q::ld(ws, 18 + i, 0); }
             _Pragma("unroll") for (int j = 0; j < 3; j++) { sql[j] = Q::ld(ws, 6 + j, 3); svl[j] = Q::ld(ws, 24 + j, 3); sul[j] = Q::ld(ws, WS_R + j, 3); }
         }
+        S lT = zero, lSl = zero, lSu = zero, lJl[3], lJu[3], lH = zero;      // LIM: the problem's box limits (every lane of the quad reads the same row)
+        if constexpr (LIM) {
+            lT = Q::ld(lim, LIM_TORQUE, 0); lSl = Q::ld(lim, LIM_JSLB, 0); lSu = Q::ld(lim, LIM_JSUB, 0); lH = Q::ld(lim, LIM_HMIN, 0);
+            _Pragma("unroll") for (int j = 0; j < 3; j++) { lJl[j] = Q::ld(lim, LIM_JLB + j, 0); lJu[j] = Q::ld(lim, LIM_JUB + j, 0); }
+        }
         QP(0)      // first reads issued
         // running cost, tracking part (QuadraticTrackingCost): 0.5 (sum_x + sum_u) dt, formed like the wave kernel: l = 0.5 sx; l += 0.5 su; l *= dt
         S sxq = zero, suq = zero;
@@ -314,11 +321,17 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
             if (WR) { _Pragma("unroll") for (int j = 0; j < 6; j++) Q::st(P.g, gk + c0 + ((j < 3) ? j : 12 + j - 3), 3, g[j]); }
             acc = Q::sum(acc);
         };
+        if constexpr (LIM) {
+            if (P.go_torque >= 0) { const S g[6] = {-ul[0] + lT, -ul[1] + lT, -ul[2] + lT, ul[0] + lT, ul[1] + lT, ul[2] + lT}; six(g, eT, dT, P.go_torque, accT); }
+            if (P.go_jspeed >= 0) { const S g[6] = {vl_[0] - lSl, vl_[1] - lSl, vl_[2] - lSl, -vl_[0] + lSu, -vl_[1] + lSu, -vl_[2] + lSu}; six(g, eS, dS, P.go_jspeed, accS); }
+            if (P.go_joint >= 0) { const S g[6] = {ql[0] - lJl[0], ql[1] - lJl[1], ql[2] - lJl[2], -ql[0] + lJu[0], -ql[1] + lJu[1], -ql[2] + lJu[2]}; six(g, eJ, dJ, P.go_joint, accJ); }
+        } else {
         if (P.go_torque >= 0) { const S g[6] = {-ul[0] + P.torque_limit, -ul[1] + P.torque_limit, -ul[2] + P.torque_limit, ul[0] + P.torque_limit, ul[1] + P.torque_limit, ul[2] + P.torque_limit}; six(g, eT, dT, P.go_torque, accT); }
         if (P.go_jspeed >= 0) { const S g[6] = {vl_[0] - P.jspeed_lb, vl_[1] - P.jspeed_lb, vl_[2] - P.jspeed_lb, -vl_[0] + P.jspeed_ub, -vl_[1] + P.jspeed_ub, -vl_[2] + P.jspeed_ub}; six(g, eS, dS, P.go_jspeed, accS); }
         if (P.go_joint >= 0) { const S g[6] = {ql[0] - P.joint_lb[0], ql[1] - P.joint_lb[1], ql[2] - P.joint_lb[2], -ql[0] + P.joint_ub[0], -ql[1] + P.joint_ub[1], -ql[2] + P.joint_ub[2]}; six(g, eJ, dJ, P.go_joint, accJ); }
+        }
         if (P.go_height >= 0) {      // one constraint: evaluated by every lane on the same data, counted once
-            const S g = qb[2] - P.h_min;
+            S g; if constexpr (LIM) g = qb[2] - lH; else g = qb[2] - P.h_min;
             if (WR) Q::st0(P.g, gk + P.go_height, g);
             gmin = Q::min(gmin, g);
             accH = eH * q_barrier<Q, S>(g, dH_);
@@ -673,7 +686,7 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     }
     QP(10)     // block Cholesky + lam
     // (second half of the tail's reads - foot-cost references, friction-pyramid parameters - behind the register peak of the factorisation)
-    S rel[3], fvr[3], rc, eG[5], dG[5];
+    S rel[3], fvr[3], rc, eG[5], dG[5], lMu = S(0.0);
 #ifndef QUAD_NEXT_EARLY
     read_next();
 #endif
@@ -684,6 +697,7 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
         if (P.go_grf >= 0) {      // per-lane constraint index go_grf + 5 slot + r: a swing lane reads a valid dummy (slot 0) and contributes nothing
             const S ci0 = Q::sel(on, 5.0 * before, S(0.0));      // (one per-lane base, constant offsets r: the five loads share an address register)
             _Pragma("unroll") for (int r = 0; r < 5; r++) { eG[r] = Q::ldv(P.eps, gk + P.go_grf + r, ci0); dG[r] = Q::ldv(P.delta, gk + P.go_grf + r, ci0); }
+            if constexpr (LIM) lMu = Q::ld(lim, LIM_MU, 0);
         }
     }
     const V3<S> lam = scale(cl, rhs);      // contact force of the lane's foot (world axes); zero for a swing leg
@@ -769,7 +783,7 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     }
     if (P.go_grf >= 0) {      // friction pyramid of the lane's foot (MHPCConstraint.cpp:9-70); its slot among the contact feet = number of contact feet before it
         S acc = zero;
-        const double mu = P.mu;
+        const auto mu = [&] { if constexpr (LIM) return lMu; else return (double)P.mu; }();
         const S gs[5] = {lam.z, -lam.x + mu * lam.z, lam.x + mu * lam.z, -lam.y + mu * lam.z, lam.y + mu * lam.z};
         _Pragma("unroll")
         for (int r = 0; r < 5; r++) {
@@ -789,11 +803,12 @@ HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double 
     o.bad = (ns > 1e12) || !(ns == ns);      // ||Xsim|| > 1e6 (SinglePhase.cpp:205)
     return o;
 }
-template <class Q, bool PW = false>
-HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr, WsRow ws = nullptr) {
+template <class Q, bool PW = false, bool LIM = false>
+HD QuadOut wbq_rollout_knot(PhaseC& P, const ModelDev& md, int b, int k, double eps, int reb_active, const double* x0, bool wr, WsRow ws = nullptr, LimRow lim = nullptr) {
     const size_t kx = ((size_t)b * (P.h + 1) + k) * 36, ku = ((size_t)b * P.h + k) * 12;
     const QuadIn<const HS_GLOBAL double*> in = {P.Xbar + kx, P.dX + kx, P.Ubar + ku, P.dU + ku, P.KdX + ku, P.rref + ref_row(P, b, k) * 80};
-    if constexpr (PW) return wbq_rollout_knot<Q, true>(P, md, b, k, eps, reb_active, x0, wr, in, ws);
+    if constexpr (LIM) return wbq_rollout_knot<Q, PW, true>(P, md, b, k, eps, reb_active, x0, wr, in, ws, lim);
+    else if constexpr (PW) return wbq_rollout_knot<Q, true>(P, md, b, k, eps, reb_active, x0, wr, in, ws);
     else return wbq_rollout_knot<Q>(P, md, b, k, eps, reb_active, x0, wr, in);
 }
 

@@ -17,7 +17,7 @@ static_assert(hs::WS_OK == HSDDP_OK && hs::WS_EINVAL == HSDDP_EINVAL && hs::WS_E
 static_assert(hs::WSP_ROW == hs::WS_ROW && hs::WSP_R == hs::WS_R && hs::WSP_QF == hs::WS_QF && hs::WSP_ROW == HSDDP_WEIGHTS_ROW, "one row layout");
 
 static int ws_tdh_ready(hsddp_handle* h) {
-    if (!h->ws_on || h->f32) return HSDDP_OK;
+    if ((!h->ws_on && !h->lim_on) || h->f32) return HSDDP_OK;      // (the kernels with limits, hsddp_limits.h, have the heights compiled in as well)
     if ((int)h->td_own.size() == h->nph && h->td_n > 0) return HSDDP_OK;      // touchdown_host.hpp's invariant holds the other phases' rows
     if (h->d_tdh && h->td_shared_gen == h->window_gen) return HSDDP_OK;
     { const int rc = td_ensure(h); if (rc) return rc; }

@@ -243,6 +243,14 @@ class Episode:
         if rc != 0:
             raise RuntimeError(f"hsddp_episode_plan_terrain failed rc={rc}")
 
+    def plan_friction(self, kappa=1.0):
+        """Friction-aware planning (include/hsddp_limits.h): mu of the solver's limits row of robot b <- kappa * mu_s of the friction row this episode
+        simulates robot b on, read on the device (0 < kappa <= 1: the planner's margin inside the cone).  The other limits of the rows stay as they
+        are, and the rows stay across the ticks' reconfigures: one call after set_friction serves the episode.  Raises if no friction is set."""
+        rc = _abi.bind_limits(self.lib).hsddp_episode_plan_friction(self.e, float(kappa))
+        if rc != 0:
+            raise RuntimeError(f"hsddp_episode_plan_friction failed rc={rc}")
+
     def set_friction(self, friction, on=True):
         """Coulomb friction (include/hsddp_friction.h) for every later tick with the contact rule on; `friction`: a sim.Friction whose mu_of, if
         given, is int [batch] or [batch, 1].  The sliding feet of a robot and their lagged normal forces are carried from tick to tick and cleared by
@@ -385,7 +393,7 @@ class Episode:
         return t.value, a.value, i.value
 
 
-def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None, friction=None, plan_terrain=False, post_hook=None, weight_scales=None):
+def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=None, episode=None, keep_log=False, delay=None, friction=None, plan_terrain=False, post_hook=None, weight_scales=None, limits=None, plan_friction=None):
     """The receding-horizon loop of MHPCLocomotion::update with the SIMULATED state fed back, for the whole batch.  solver: solved for the window
     `phases` of pd (builder.MHPCProblemData).  Per tick: episode.advance, pd.update(), builder.shift_solver_in_place, hook(tick, phases) - the
     place for solver.set_references - and solver.solve(opt_rt).  kicks: {tick: (kick_step, [B, 36])}.  episode: an Episode already reset; None
@@ -395,7 +403,10 @@ def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=No
     plan_terrain: every tick, after the hook and before the solve, episode.plan_terrain() gives the new window the touchdown heights of the episode's
     terrain (include/hsddp_touchdown.h); False plans onto the descriptors' ground_height.  post_hook(tick, phases) is called after the tick's solve.
     weight_scales: None leaves the solver as it is; (sq, sr, sqf) is Solver.set_weight_scales before the first tick (include/hsddp_weights.h) - set once,
-    the scales stay across the ticks' reconfigures; the episode's track_cost goes on using the descriptors' weights.  Returns a dict: episode, phases (the last
+    the scales stay across the ticks' reconfigures; the episode's track_cost goes on using the descriptors' weights.
+    limits: None leaves the solver as it is; a dict of Solver.set_limits' keyword arguments is that call before the first tick (include/hsddp_limits.h).
+    plan_friction: None plans with the limits as they are; a kappa is Episode.plan_friction(kappa) before the first tick, after `friction` and `limits`
+    (set once: the rows stay across the ticks' reconfigures).  Returns a dict: episode, phases (the last
     window), n_iters / n_ls_iters / n_reg_iters / cost [n_ticks, B], alive [n_ticks]."""
     from . import builder
     if episode is None:
@@ -407,6 +418,10 @@ def run_mhpc(solver, pd, phases, opt_rt, n_ticks, dist=None, kicks=None, hook=No
         episode.set_friction(friction)
     if weight_scales is not None:
         solver.set_weight_scales(*weight_scales)
+    if limits is not None:
+        solver.set_limits(**limits)
+    if plan_friction is not None:
+        episode.plan_friction(plan_friction)
     out = dict(n_iters=[], n_ls_iters=[], n_reg_iters=[], cost=[], alive=[])
     for t in range(n_ticks):
         d, k = dist, None

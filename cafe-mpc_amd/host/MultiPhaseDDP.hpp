@@ -30,6 +30,7 @@
 #include "hsddp_latency.h"
 #include "hsddp_touchdown.h"
 #include "hsddp_weights.h"
+#include "hsddp_limits.h"
 
 namespace hsddp {
 
@@ -165,6 +166,8 @@ public:
     // terrain-aware planning (include/hsddp_touchdown.h): the touchdown heights of the handle's current window from the terrain this episode simulates
     // on; after the window moved (reconfigure, set_references) and before the solve
     bool plan_terrain() { rc_ = e_ ? hsddp_episode_plan_terrain(e_) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
+    // friction-aware planning (include/hsddp_limits.h): mu of every robot's limits row <- kappa * mu_s of the friction row it is simulated on
+    bool plan_friction(double kappa = 1.0) { rc_ = e_ ? hsddp_episode_plan_friction(e_, kappa) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // a plant row per robot for the whole episode (include/hsddp_plant.h): plant_of [batch] or null
     bool set_plant(bool on, int n_plants = 0, const double* P = nullptr, const int* plant_of = nullptr) { rc_ = e_ ? hsddp_plant_set(hsddp_episode_sim(e_), on ? 1 : 0, n_plants, P, plant_of) : HSDDP_EINVAL; return rc_ == HSDDP_OK; }
     // per-robot policy latency for every later tick (include/hsddp_latency.h): delay_of [batch] in control steps, or null and one delay for all
@@ -304,6 +307,14 @@ public:
     }
     bool weight_scales(double* scales, int b0, int nb) { rc_ = hsddp_weights_get(h_, b0, nb, scales); return rc_ == HSDDP_OK; }
     bool clear_weight_scales() { rc_ = hsddp_weights_clear(h_); return rc_ == HSDDP_OK; }
+    // per-problem constraint limits (include/hsddp_limits.h): rows [nb][12] = torque_limit | joint_lb[3] | joint_ub[3] | h_min | mu | jointspeed_lb |
+    // jointspeed_ub | pad for problems [b0, b0+nb), absolute values, NaN = the descriptor's (host memory, or device memory with src_device); they stay
+    // across reconfigure.  limits: the rows in use in a phase; clear: the kernels of a handle that never had limits.
+    bool set_limits(const double* rows, int nb, int b0 = 0, bool src_device = false) {
+        rc_ = hsddp_limits_set(h_, b0, nb, rows, src_device ? 1 : 0); return rc_ == HSDDP_OK;
+    }
+    bool limits(double* rows, int phase, int b0, int nb) { rc_ = hsddp_limits_get(h_, phase, b0, nb, rows); return rc_ == HSDDP_OK; }
+    bool clear_limits() { rc_ = hsddp_limits_clear(h_); return rc_ == HSDDP_OK; }
     // one-off closed-loop rollouts of the current policy, u = Ubar + K (x - Xbar), from n_samples initial states per problem over the first
     // n_steps whole-body control knots (x0: batch x n_samples x 36) - what the controller side of the reference does one state at a time
     // (MHPC/MHPC-Trajopt/test/testTrajOptInLoop.cpp).  An MPC loop keeps a hsddp::Simulation instead.  libhsddp_hip.so only.

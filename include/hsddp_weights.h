@@ -32,8 +32,8 @@
  *   a warm tick allocates nothing (hsddp_debug_malloc_count).
  * HSDDP_EINVAL, with nothing changed: a NULL handle or source, a range outside the batch, nb <= 0, a bad host value.  HSDDP_ENOTSUP: an fp32 handle.
  *
- * Out of scope: scales on single-rigid-body / kinodynamic phases, on the foot costs or on constraint parameters; fp32 handles; weights that vary by
- * knot; a tuner.
+ * Out of scope: scales on single-rigid-body / kinodynamic phases, on the foot costs or on constraint parameters (per-problem constraint LIMITS are
+ * include/hsddp_limits.h); fp32 handles; weights that vary by knot; a tuner.
  *
  * Conventions as in hsddp.h: 0 on success, a negative HSDDP_E* code otherwise.
  */
