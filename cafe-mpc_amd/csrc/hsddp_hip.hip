@@ -44,6 +44,7 @@
 #include "wb_sim.hpp"
 #include "episode.hpp"
 #include "rollout_args.hpp"
+#include "roll_pick.hpp"
 
 using namespace hs;
 
@@ -74,6 +75,8 @@ __global__ void __launch_bounds__(64) ROLL_ATTR k_rollout(ROLL_ARGS) { __shared_
 #define ROLL_HKD_ATTR
 #endif
 __global__ void __launch_bounds__(64) ROLL_HKD_ATTR k_rollout_hkd(ROLL_ARGS) { __shared__ RedLds L; rollout_body<false>(L, ROLL_PASS); }
+void launch_k_rollout(unsigned grid, hipStream_t stream, const RollArgs& a) { hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(64), 0, stream, ROLL_FROM(a)); }
+void launch_k_rollout_hkd(unsigned grid, hipStream_t stream, const RollArgs& a) { hipLaunchKernelGGL(k_rollout_hkd, dim3(grid), dim3(64), 0, stream, ROLL_FROM(a)); }
 
 // The whole-body running knots of the phases with shooting nodes run on lane quads: k_rollout_quad, hsddp_quad.hip.  The Makefile compiles that
 // file as a translation unit of its own (-DHS_QUAD_SEPARATE here) because it wants one more compiler switch than the rest of the library; any
@@ -187,6 +190,8 @@ __global__ void __launch_bounds__(LQ_NT) LQ_ATTR k_lq(LQ_ARGS) { __shared__ WbLq
 #define LQ_HKD_ATTR
 #endif
 __global__ void __launch_bounds__(64) LQ_HKD_ATTR k_lq_hkd(LQ_ARGS) { __shared__ RedLds L; lq_body<false, 64>(L, LQ_PASS); }
+void launch_k_lq(unsigned grid, hipStream_t stream, const LqArgs& a) { hipLaunchKernelGGL(k_lq, dim3(grid), dim3(LQ_NT), 0, stream, LQ_FROM(a)); }
+void launch_k_lq_hkd(unsigned grid, hipStream_t stream, const LqArgs& a) { hipLaunchKernelGGL(k_lq_hkd, dim3(grid), dim3(64), 0, stream, LQ_FROM(a)); }
 
 // cost-only refresh from stored g / h with the CURRENT ReB / AL parameters (SinglePhase::compute_cost, SinglePhase.cpp:236-262)
 __global__ void __launch_bounds__(64) k_cost(const PhaseDev* ph_, const int* slot_phase, const int* slot_k, int nslots, OptDev opt, SlotArrays sa,
@@ -861,101 +866,55 @@ int hsddp_set_control_knot(hsddp_handle_t* h, int phase, int k, const double* u)
 // ---- launch helpers
 enum { UNIT_ROLLOUT = 0, UNIT_LQ = 1, UNIT_SWEEP = 2, UNIT_PROBE = 3 };
 static HistDev hist_of(hsddp_handle* h) { return HistDev{h->d_hist, h->hist_cap}; }
-// the table of per-problem cost-weight scales (hsddp_weights.h) if the launches of this window read it: one is set and a whole-body phase is there
-// to use it.  Null: the kernels of before, with the arguments of before.
-static const double* ws_table(hsddp_handle* h) {
-    if (!h->ws_on || h->f32 || h->has_hkd) return nullptr;
-    for (const PhaseDev& P : h->ph) if (P.model == HSDDP_MODEL_WB) return h->d_ws;
-    return nullptr;
+// Which kernels a launch uses is roll_pick's / lq_pick's business (roll_pick.hpp; tests/cpp/roll_pick_table.cpp walks it on the CPU).  Here only: the switches it reads, the tables
+// it names and the launchers of its enums (rollout_args.hpp).  roll_switches fills the handle's part; the four switches of a rollout launch stay false for launch_lq, whose pick ignores them.
+static RollSwitches roll_switches(const hsddp_handle* h) {
+    RollSwitches s = {h->lim_on, h->ws_on, h->td_n > 0, h->f32, h->has_hkd, false, false, false, false, false};
+    for (const PhaseDev& P : h->ph) if (P.model == HSDDP_MODEL_WB) s.has_wb = true;
+    return s;
 }
-// the resolved table of per-problem constraint limits (hsddp_limits.h) if the launches of this window read it, under the same rule; lim_wtab: the scale
-// table its kernels read with it - the handle's, or ones while no scales are set (x * 1.0 is exact)
 static size_t lim_off_res(const hsddp_handle* h) { return 2 * (size_t)h->batch * LIM_ROW; }
 static size_t lim_off_desc(const hsddp_handle* h) { return lim_off_res(h) + (size_t)h->nph_cap * h->batch * LIM_ROW; }
 static size_t lim_off_ones(const hsddp_handle* h) { return lim_off_desc(h) + (size_t)h->nph_cap * LIM_ROW; }
-static const double* lim_table(hsddp_handle* h) {
-    if (!h->lim_on || h->f32 || h->has_hkd) return nullptr;
-    for (const PhaseDev& P : h->ph) if (P.model == HSDDP_MODEL_WB) return h->d_lim + lim_off_res(h);
-    return nullptr;
+// the scale table (hsddp_weights.h; the ones live beside the limits, limits_host.hpp) and the resolved limits (hsddp_limits.h) a pick asks for
+static const double* ws_table(const hsddp_handle* h, RollWtab w) { return w == WTAB_HANDLE ? h->d_ws : w == WTAB_ONES ? h->d_lim + lim_off_ones(h) : nullptr; }
+static const double* lim_table(const hsddp_handle* h, bool ltab) { return ltab ? h->d_lim + lim_off_res(h) : nullptr; }
+static void launch_wave(RollKernel k, unsigned grid, hipStream_t stream, const RollArgs& a) {
+    if (k == RK_ROLLOUT) launch_k_rollout(grid, stream, a);
+    else if (k == RK_ROLLOUT_HKD) launch_k_rollout_hkd(grid, stream, a);
+    else if (k == RK_ROLLOUT_TDH) launch_k_rollout_tdh(grid, stream, a);
+    else if (k == RK_ROLLOUT_PW) launch_k_rollout_pw(grid, stream, a);
+    else if (k == RK_ROLLOUT_LIM) launch_k_rollout_lim(grid, stream, a);
 }
-static const double* lim_wtab(hsddp_handle* h) { return h->ws_on ? h->d_ws : h->d_lim + lim_off_ones(h); }
-static void launch_rollout_lim(hsddp_handle* h, const double* ltab, const EpsList& el, const SlotArrays& sa, const OptDev& o, int mask, const char* name, int unit, const int* plist, int nlist) {
-    if (ws_tdh_ready(h) != HSDDP_OK) { fprintf(stderr, "[hsddp_hip] %s: the touchdown-height table of the kernels with limits is not available, launch skipped\n", name); return; }
-    const double* wtab = lim_wtab(h);
-    const std::string lim_name = std::string(name) + "_lim";      // (timed under their own names: k_rollout_lim, k_ls_probe_lim)
-    Timed t(h, lim_name.c_str());
-    hipMemsetAsync(h->d_fail, 0, (size_t)h->batch * el.n * sizeof(int), h->stream);
-    if (h->quad && o.MS && h->nq > 0) {
-        const int nprob = plist ? nlist : h->batch, nbg = (nprob + 15) / 16;
-        launch_k_rollout_quad_lim((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
-                                  h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist, wtab, ltab);
-        // terminal knots on lane quads read no path-constraint limit: what they launch without limits (scaled, with heights, plain)
-        if (h->n_term > 0 && h->ws_on)
-            launch_k_rollout_quad_term_pw((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
-                                          plist, nlist, h->d_tdh, wtab);
-        else if (h->n_term > 0 && h->td_n > 0)
-            launch_k_rollout_quad_term_tdh((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
-                                           plist, nlist, h->d_tdh);
-        else if (h->n_term > 0)
-            launch_k_rollout_quad_term((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
-                                       plist, nlist);
-        if (h->n_other > 0 && nprob > 0)
-            launch_k_rollout_lim((unsigned)((size_t)el.n * nprob * h->n_other), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
-                                 h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob, h->d_tdh, wtab, ltab);
-        return;
-    }
-    launch_k_rollout_lim((unsigned)((size_t)el.n * h->batch * h->nslots), h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
-                         h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph, (const int*)nullptr, h->batch, h->d_tdh, wtab, ltab);
+static void launch_quad(RollKernel k, unsigned grid, hipStream_t stream, const QuadArgs& a) {
+    if (k == RK_QUAD) launch_k_rollout_quad(grid, stream, a);
+    else if (k == RK_QUAD_PW) launch_k_rollout_quad_pw(grid, stream, a);
+    else if (k == RK_QUAD_LIM) launch_k_rollout_quad_lim(grid, stream, a);
 }
+static void launch_quad_term(RollKernel k, unsigned grid, hipStream_t stream, const QuadTermArgs& a) {
+    if (k == RK_QUAD_TERM) launch_k_rollout_quad_term(grid, stream, a);
+    else if (k == RK_QUAD_TERM_TDH) launch_k_rollout_quad_term_tdh(grid, stream, a);
+    else if (k == RK_QUAD_TERM_PW) launch_k_rollout_quad_term_pw(grid, stream, a);
+}
+// One rollout of the window: whole-body running knots and the terminal knots behind them on lane quads where the launch has a quad path, the rest (or, without one,
+// everything) on the one-wave programs - none where every slot is on lane quads.  The tiers with scales / limits are timed under their own names (k_rollout_pw, k_ls_probe_lim).
 static void launch_rollout_list(hsddp_handle* h, const EpsList& el, const SlotArrays& sa, const OptDev& o, int mask, const char* name, int unit = UNIT_ROLLOUT, const int* plist = nullptr, int nlist = 0) {
-    if (const double* ltab = lim_table(h)) { launch_rollout_lim(h, ltab, el, sa, o, mask, name, unit, plist, nlist); return; }
-    const double* wtab = ws_table(h);
-    if (wtab && ws_tdh_ready(h) != HSDDP_OK) { fprintf(stderr, "[hsddp_hip] %s: the touchdown-height table of the scaled kernels is not available, launch skipped\n", name); return; }
-    const std::string pw_name = wtab ? std::string(name) + "_pw" : std::string();      // (launches with scales are timed under their own names: k_rollout_pw, k_ls_probe_pw)
-    Timed t(h, wtab ? pw_name.c_str() : name);
+    const int nprob = plist ? nlist : h->batch, nbg = (nprob + 15) / 16;      // the launch's problems, and groups of sixteen of them (a lane-quad unit's)
+    RollSwitches s = roll_switches(h);
+    s.quad_path = h->quad && o.MS && h->nq > 0; s.has_term = h->n_term > 0; s.has_other = h->n_other > 0; s.has_prob = nprob > 0;
+    const RollPick p = roll_pick(s);
+    const std::string timed = std::string(name) + roll_suffix(p.tier);
+    if (p.need_tdh && ws_tdh_ready(h) != HSDDP_OK) { fprintf(stderr, "[hsddp_hip] %s: the touchdown-height table its kernels read is not available, launch skipped\n", timed.c_str()); return; }
+    const RollCommon c = {h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist,
+                          h->d_tdh, ws_table(h, p.wtab), lim_table(h, p.ltab)};
+    Timed t(h, timed.c_str());
     hipMemsetAsync(h->d_fail, 0, (size_t)h->batch * el.n * sizeof(int), h->stream);
-    if (h->quad && o.MS && h->nq > 0) {      // whole-body running knots and the terminal knots behind them on lane quads, the rest on the one-wave programs
-        const int nprob = plist ? nlist : h->batch, nbg = (nprob + 15) / 16;
-        if (wtab) {      // per-problem cost-weight scales: the three kernels' twins, the terminal programs with the heights compiled in (ws_tdh_ready)
-            launch_k_rollout_quad_pw((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
-                                     h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist, wtab);
-            if (h->n_term > 0)
-                launch_k_rollout_quad_term_pw((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
-                                              plist, nlist, h->d_tdh, wtab);
-            if (h->n_other > 0 && nprob > 0)
-                launch_k_rollout_pw((unsigned)((size_t)el.n * nprob * h->n_other), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
-                                    h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob, h->d_tdh, wtab);
-            return;
-        }
-        launch_k_rollout_quad((unsigned)((size_t)h->nq * nbg), h->stream, h->d_ph, h->d_slot_phase, h->d_slot_k, h->d_qslots, h->nq, h->nslots, h->batch,
-                              h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, plist, nlist);
-        const bool tdh = h->td_n > 0;      // a phase of the window has touchdown heights of its own (hsddp_touchdown.h): the terminal knots read the table
-        if (h->n_term > 0 && tdh)
-            launch_k_rollout_quad_term_tdh((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
-                                           plist, nlist, h->d_tdh);
-        else if (h->n_term > 0)
-            launch_k_rollout_quad_term((unsigned)((size_t)h->n_term * nbg), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_tslots, h->nslots, h->batch, h->md, el, o, sa, h->d_st, mask,
-                                       plist, nlist);
-        if (h->n_other > 0 && nprob > 0 && tdh)
-            launch_k_rollout_tdh((unsigned)((size_t)el.n * nprob * h->n_other), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
-                                 h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob, h->d_tdh);
-        else if (h->n_other > 0 && nprob > 0)      // (a window whose every slot is on lane quads launches no one-wave kernel at all)
-            hipLaunchKernelGGL(k_rollout, dim3((unsigned)((size_t)el.n * nprob * h->n_other)), dim3(64), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k,
-                               h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, h->d_oslots, h->n_other, h->other_knots, plist, nprob);
-        return;
-    }
-    if (wtab) {
-        launch_k_rollout_pw((unsigned)((size_t)el.n * h->batch * h->nslots), h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
-                            h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph, (const int*)nullptr, h->batch, h->d_tdh, wtab);
-        return;
-    }
-    if (h->td_n > 0 && !h->has_hkd) {      // (heights exist for whole-body phases only, and a window with a kinodynamic phase has none)
-        launch_k_rollout_tdh((unsigned)((size_t)el.n * h->batch * h->nslots), h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
-                             h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph, (const int*)nullptr, h->batch, h->d_tdh);
-        return;
-    }
-    hipLaunchKernelGGL(h->has_hkd ? k_rollout_hkd : k_rollout, dim3((unsigned)((size_t)el.n * h->batch * h->nslots)), dim3(64), 0, h->stream, o.MS ? h->d_ph : h->d_ph_ss, h->nph, h->d_slot_phase, h->d_slot_k,
-                       h->nslots, h->batch, h->md, el, o, h->d_x0, sa, h->d_st, mask, h->d_fail, h->d_units + unit, (const int*)nullptr, h->nslots, h->nslots - h->nph, (const int*)nullptr, h->batch);
+    if (p.quad != RK_NONE) launch_quad(p.quad, (unsigned)((size_t)h->nq * nbg), h->stream, QuadArgs{c, h->d_qslots, h->nq, nlist});
+    if (p.term != RK_NONE) launch_quad_term(p.term, (unsigned)((size_t)h->n_term * nbg), h->stream, QuadTermArgs{c, h->d_tslots, nlist});
+    if (p.wave == RK_NONE) return;
+    RollArgs a = {c, h->d_oslots, h->n_other, h->other_knots, nprob};      // the slots the quad path leaves, for the launch's problems
+    if (p.whole_window) { a.ph = o.MS ? h->d_ph : h->d_ph_ss; a.slot_list = nullptr; a.nlist = h->nslots; a.unit_knots = h->nslots - h->nph; a.plist = nullptr; a.nprob = h->batch; }
+    launch_wave(p.wave, (unsigned)((size_t)el.n * a.nprob * a.nlist), h->stream, a);
 }
 static void launch_rollout(hsddp_handle* h, double eps, const OptDev& o, int mask, bool eps_from_state = false, const int* plist = nullptr, int nlist = 0) {
     EpsList el{}; el.e[0] = eps; el.n = 1; el.writer = 0; el.from_state = eps_from_state ? 1 : 0;
@@ -973,22 +932,16 @@ static int ensure_probe_arrays(hsddp_handle* h, int cands) {
     h->sp_cands = cands; return HSDDP_OK;
 }
 static void launch_lq(hsddp_handle* h, const OptDev& o, int mask) {
-    if (const double* ltab = lim_table(h)) {
-        Timed t(h, "k_lq_lim");
-        launch_k_lq_lim((unsigned)((size_t)h->batch * h->nslots), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask, h->cache_valid ? 1 : 0, h->d_units + UNIT_LQ,
-                        lim_wtab(h), ltab, h->batch);
-        return;
-    }
-    if (const double* wtab = ws_table(h)) {
-        Timed t(h, "k_lq_pw");
-        launch_k_lq_pw((unsigned)((size_t)h->batch * h->nslots), h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask, h->cache_valid ? 1 : 0, h->d_units + UNIT_LQ, wtab);
-        return;
-    }
-    Timed t(h, "k_lq");
-    if (h->has_hkd) hipLaunchKernelGGL(k_lq_hkd, dim3((unsigned)((size_t)h->batch * h->nslots)), dim3(64), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask,
-                                       0, h->d_units + UNIT_LQ);
-    else hipLaunchKernelGGL(k_lq, dim3((unsigned)((size_t)h->batch * h->nslots)), dim3(LQ_NT), 0, h->stream, h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask,
-                            h->cache_valid ? 1 : 0, h->d_units + UNIT_LQ);
+    const LqPick p = lq_pick(roll_switches(h));
+    const LqArgs a = {h->d_ph, h->nph, h->d_slot_phase, h->d_slot_k, h->nslots, h->md, o, h->d_st, mask, h->cache_valid && !p.no_cache ? 1 : 0, h->d_units + UNIT_LQ,
+                      ws_table(h, p.wtab), lim_table(h, p.ltab), h->batch};
+    const std::string timed = std::string("k_lq") + roll_suffix(p.tier);
+    Timed t(h, timed.c_str());
+    const unsigned grid = (unsigned)((size_t)h->batch * h->nslots);
+    if (p.kernel == LK_LQ) launch_k_lq(grid, h->stream, a);
+    else if (p.kernel == LK_LQ_HKD) launch_k_lq_hkd(grid, h->stream, a);
+    else if (p.kernel == LK_LQ_PW) launch_k_lq_pw(grid, h->stream, a);
+    else if (p.kernel == LK_LQ_LIM) launch_k_lq_lim(grid, h->stream, a);
 }
 static void launch_cost(hsddp_handle* h, const OptDev& o, int mask) {
     Timed t(h, "k_cost");

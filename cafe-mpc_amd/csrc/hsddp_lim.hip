@@ -12,7 +12,8 @@
 //                        because tests/test_friction_host.py lets no kernel of libhsddp_hip.so carry the friction walks' tag in its name)
 // The resolved table is a kernel ARGUMENT, [phase][batch][12]: nothing is added to PhaseDev, and the knots test nothing - every entry is the value to
 // use.  Terminal knots read no path-constraint limit: on lane quads they go on running k_rollout_quad_term / _tdh / _pw.  The kernels here have the
-// scales of hsddp_weights.h compiled in; a handle with limits and no scales hands them a table of 1.0 (limits_host.hpp).
+// scales of hsddp_weights.h compiled in; a handle with limits and no scales hands them a table of 1.0 (limits_host.hpp).  Which launch runs
+// which of them, and with which scale table: roll_pick.hpp.
 #ifdef HS_LIM_SEPARATE
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -50,21 +51,9 @@ __global__ void __launch_bounds__(256) k_lim_mu(hs::LimMu F) {
     for (size_t b = (size_t)blockIdx.x * 256u + threadIdx.x; b < (size_t)F.batch; b += (size_t)gridDim.x * 256u) hs::lim_mu_item(F, (int)b);
 }
 
-void launch_k_rollout_lim(unsigned grid, hipStream_t stream, const PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, ModelDev md, EpsList el, OptDev opt,
-                          const double* x0, SlotArrays sa, const ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist, int unit_knots,
-                          const int* plist, int nprob, const double* tdh, const double* wtab, const double* ltab) {
-    hipLaunchKernelGGL(k_rollout_lim, dim3(grid), dim3(64), 0, stream, ph, nph, slot_phase, slot_k, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, slot_list, nlist, unit_knots,
-                       plist, nprob, tdh, wtab, ltab);
-}
-void launch_k_rollout_quad_lim(unsigned grid, hipStream_t stream, const PhaseDev* ph, const int* slot_phase, const int* slot_k, const int* qslots, int nq, int nslots, int batch,
-                               ModelDev md, EpsList el, OptDev opt, const double* x0, SlotArrays sa, const ProbState* st, int mask, int* fail, unsigned long long* units,
-                               const int* plist, int nlist, const double* wtab, const double* ltab) {
-    hipLaunchKernelGGL(k_rollout_quad_lim, dim3(grid), dim3(64), 0, stream, ph, slot_phase, slot_k, qslots, nq, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, plist, nlist, wtab, ltab);
-}
-void launch_k_lq_lim(unsigned grid, hipStream_t stream, const PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, ModelDev md, OptDev opt, const ProbState* st, int mask,
-                     int use_cache, unsigned long long* units, const double* wtab, const double* ltab, int batch) {
-    hipLaunchKernelGGL(k_lq_lim, dim3(grid), dim3(LQ_NT), 0, stream, ph, nph, slot_phase, slot_k, nslots, md, opt, st, mask, use_cache, units, wtab, ltab, batch);
-}
+void launch_k_rollout_lim(unsigned grid, hipStream_t stream, const RollArgs& a) { hipLaunchKernelGGL(k_rollout_lim, dim3(grid), dim3(64), 0, stream, ROLL_FROM(a), a.tdh, a.wtab, a.ltab); }
+void launch_k_rollout_quad_lim(unsigned grid, hipStream_t stream, const QuadArgs& a) { hipLaunchKernelGGL(k_rollout_quad_lim, dim3(grid), dim3(64), 0, stream, QUAD_FROM(a), a.wtab, a.ltab); }
+void launch_k_lq_lim(unsigned grid, hipStream_t stream, const LqArgs& a) { hipLaunchKernelGGL(k_lq_lim, dim3(grid), dim3(LQ_NT), 0, stream, LQ_FROM(a), a.wtab, a.ltab, a.batch); }
 void launch_k_pack_limits(hipStream_t stream, const hs::LimPack& W) {
     const size_t n = hs::lim_pack_count(W);
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);

@@ -12,6 +12,7 @@
 // The table is a kernel ARGUMENT, [batch][84] = sq[36] | sr[12] | sqf[36] per problem: nothing is added to PhaseDev.  The two kernels that hold
 // terminal programs are instantiated with the touchdown heights of hsddp_touchdown.h compiled in, so scales and heights combine without a third and
 // fourth pair of kernels: a window without heights of its own hands them a table that holds each phase's ground_height (weights_host.hpp).
+// Which launch runs them, and that the heights table must be ready first: roll_pick.hpp.
 #ifdef HS_PW_SEPARATE
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -46,25 +47,10 @@ __global__ void __launch_bounds__(256) k_pack_weights(hs::WsPack W) {
     for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) W.dst[o + i] = hs::ws_value(W, i);
 }
 
-void launch_k_rollout_pw(unsigned grid, hipStream_t stream, const PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, ModelDev md, EpsList el, OptDev opt,
-                         const double* x0, SlotArrays sa, const ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist, int unit_knots,
-                         const int* plist, int nprob, const double* tdh, const double* wtab) {
-    hipLaunchKernelGGL(k_rollout_pw, dim3(grid), dim3(64), 0, stream, ph, nph, slot_phase, slot_k, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, slot_list, nlist, unit_knots,
-                       plist, nprob, tdh, wtab);
-}
-void launch_k_rollout_quad_pw(unsigned grid, hipStream_t stream, const PhaseDev* ph, const int* slot_phase, const int* slot_k, const int* qslots, int nq, int nslots, int batch,
-                              ModelDev md, EpsList el, OptDev opt, const double* x0, SlotArrays sa, const ProbState* st, int mask, int* fail, unsigned long long* units,
-                              const int* plist, int nlist, const double* wtab) {
-    hipLaunchKernelGGL(k_rollout_quad_pw, dim3(grid), dim3(64), 0, stream, ph, slot_phase, slot_k, qslots, nq, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, plist, nlist, wtab);
-}
-void launch_k_rollout_quad_term_pw(unsigned grid, hipStream_t stream, const PhaseDev* ph, int nph, const int* slot_phase, const int* tslots, int nslots, int batch,
-                                   ModelDev md, EpsList el, OptDev opt, SlotArrays sa, const ProbState* st, int mask, const int* plist, int nlist, const double* tdh, const double* wtab) {
-    hipLaunchKernelGGL(k_rollout_quad_term_pw, dim3(grid), dim3(64), 0, stream, ph, nph, slot_phase, tslots, nslots, batch, md, el, opt, sa, st, mask, plist, nlist, tdh, wtab);
-}
-void launch_k_lq_pw(unsigned grid, hipStream_t stream, const PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, ModelDev md, OptDev opt, const ProbState* st, int mask,
-                    int use_cache, unsigned long long* units, const double* wtab) {
-    hipLaunchKernelGGL(k_lq_pw, dim3(grid), dim3(LQ_NT), 0, stream, ph, nph, slot_phase, slot_k, nslots, md, opt, st, mask, use_cache, units, wtab);
-}
+void launch_k_rollout_pw(unsigned grid, hipStream_t stream, const RollArgs& a) { hipLaunchKernelGGL(k_rollout_pw, dim3(grid), dim3(64), 0, stream, ROLL_FROM(a), a.tdh, a.wtab); }
+void launch_k_rollout_quad_pw(unsigned grid, hipStream_t stream, const QuadArgs& a) { hipLaunchKernelGGL(k_rollout_quad_pw, dim3(grid), dim3(64), 0, stream, QUAD_FROM(a), a.wtab); }
+void launch_k_rollout_quad_term_pw(unsigned grid, hipStream_t stream, const QuadTermArgs& a) { hipLaunchKernelGGL(k_rollout_quad_term_pw, dim3(grid), dim3(64), 0, stream, QUAD_TERM_FROM(a), a.tdh, a.wtab); }
+void launch_k_lq_pw(unsigned grid, hipStream_t stream, const LqArgs& a) { hipLaunchKernelGGL(k_lq_pw, dim3(grid), dim3(LQ_NT), 0, stream, LQ_FROM(a), a.wtab); }
 void launch_k_pack_weights(hipStream_t stream, const hs::WsPack& W) {
     const size_t n = hs::ws_count(W);
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);

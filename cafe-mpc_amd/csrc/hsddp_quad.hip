@@ -33,11 +33,7 @@ k_rollout_quad(const PhaseDev* ph_, const int* slot_phase, const int* slot_k, co
 #undef QUAD_BODY_PW
 }
 
-void launch_k_rollout_quad(unsigned grid, hipStream_t stream, const PhaseDev* ph, const int* slot_phase, const int* slot_k, const int* qslots, int nq, int nslots, int batch,
-                           ModelDev md, EpsList el, OptDev opt, const double* x0, SlotArrays sa, const ProbState* st, int mask, int* fail, unsigned long long* units,
-                           const int* plist, int nlist) {
-    hipLaunchKernelGGL(k_rollout_quad, dim3(grid), dim3(64), 0, stream, ph, slot_phase, slot_k, qslots, nq, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, plist, nlist);
-}
+void launch_k_rollout_quad(unsigned grid, hipStream_t stream, const QuadArgs& a) { hipLaunchKernelGGL(k_rollout_quad, dim3(grid), dim3(64), 0, stream, QUAD_FROM(a)); }
 
 // The terminal knots the quad path owns (split_slots, hsddp_hip.hip: whole-body phase with shooting nodes whose successor, if any, is one too) on
 // LANE QUADS: wbq_rollout_terminal (wb_quad_term.hpp).  Units, packing from plist and the candidate loop are k_rollout_quad's: grid = terminal slots of
@@ -54,10 +50,7 @@ k_rollout_quad_term(const PhaseDev* ph_, int nph, const int* slot_phase, const i
     quad_term_body<false>(stage, ph_, nph, slot_phase, tslots, nslots, batch, md, el, opt, sa, st, mask, plist, nlist, nullptr);
 }
 
-void launch_k_rollout_quad_term(unsigned grid, hipStream_t stream, const PhaseDev* ph, int nph, const int* slot_phase, const int* tslots, int nslots, int batch,
-                                ModelDev md, EpsList el, OptDev opt, SlotArrays sa, const ProbState* st, int mask, const int* plist, int nlist) {
-    hipLaunchKernelGGL(k_rollout_quad_term, dim3(grid), dim3(64), 0, stream, ph, nph, slot_phase, tslots, nslots, batch, md, el, opt, sa, st, mask, plist, nlist);
-}
+void launch_k_rollout_quad_term(unsigned grid, hipStream_t stream, const QuadTermArgs& a) { hipLaunchKernelGGL(k_rollout_quad_term, dim3(grid), dim3(64), 0, stream, QUAD_TERM_FROM(a)); }
 
 #ifdef QUAD_PROF
 extern "C"

@@ -9,7 +9,7 @@
 //   k_rollout_quad_term_tdh  quad_term_body (quad_term_body.hpp) with TDH on: the terminal knots of the lane-quad path; lane = leg reads its own height
 //   k_td_terrain             one lane per (phase, problem, leg): the height of the terrain at the phase's terminal reference foothold (touchdown.hpp)
 // The heights are a kernel ARGUMENT, the window's table [phase][batch][4]: nothing is added to PhaseDev, whose layout every other kernel's scalar
-// loads depend on.
+// loads depend on.  Which launch runs them: roll_pick.hpp.
 #ifdef HS_TDH_SEPARATE
 #include <hip/hip_runtime.h>
 #include "hs_types.hpp"
@@ -38,16 +38,8 @@ __global__ void __launch_bounds__(256) k_td_terrain(const PhaseDev* ph, int nph,
     out[i] = hs::td_terrain_height(g, r, b, leg);
 }
 
-void launch_k_rollout_tdh(unsigned grid, hipStream_t stream, const PhaseDev* ph, int nph, const int* slot_phase, const int* slot_k, int nslots, int batch, ModelDev md, EpsList el, OptDev opt,
-                          const double* x0, SlotArrays sa, const ProbState* st, int mask, int* fail, unsigned long long* units, const int* slot_list, int nlist, int unit_knots,
-                          const int* plist, int nprob, const double* tdh) {
-    hipLaunchKernelGGL(k_rollout_tdh, dim3(grid), dim3(64), 0, stream, ph, nph, slot_phase, slot_k, nslots, batch, md, el, opt, x0, sa, st, mask, fail, units, slot_list, nlist, unit_knots,
-                       plist, nprob, tdh);
-}
-void launch_k_rollout_quad_term_tdh(unsigned grid, hipStream_t stream, const PhaseDev* ph, int nph, const int* slot_phase, const int* tslots, int nslots, int batch,
-                                    ModelDev md, EpsList el, OptDev opt, SlotArrays sa, const ProbState* st, int mask, const int* plist, int nlist, const double* tdh) {
-    hipLaunchKernelGGL(k_rollout_quad_term_tdh, dim3(grid), dim3(64), 0, stream, ph, nph, slot_phase, tslots, nslots, batch, md, el, opt, sa, st, mask, plist, nlist, tdh);
-}
+void launch_k_rollout_tdh(unsigned grid, hipStream_t stream, const RollArgs& a) { hipLaunchKernelGGL(k_rollout_tdh, dim3(grid), dim3(64), 0, stream, ROLL_FROM(a), a.tdh); }
+void launch_k_rollout_quad_term_tdh(unsigned grid, hipStream_t stream, const QuadTermArgs& a) { hipLaunchKernelGGL(k_rollout_quad_term_tdh, dim3(grid), dim3(64), 0, stream, QUAD_TERM_FROM(a), a.tdh); }
 void launch_k_td_terrain(hipStream_t stream, const PhaseDev* ph, int nph, int batch, const hs::TdGrid& g, double* out) {
     const size_t n = (size_t)nph * batch * 4;
     hipLaunchKernelGGL(k_td_terrain, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ph, nph, batch, g, out);

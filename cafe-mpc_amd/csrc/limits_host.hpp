@@ -4,9 +4,9 @@
 // Storage: ONE device block per handle, d_lim, allocated by the first hsddp_limits_set / hsddp_episode_plan_friction and never again (batch and
 // nph_cap are fixed at hsddp_create):
 //     user [batch][12]  |  staging of a host source [batch][12]  |  resolved [nph_cap][batch][12]  |  descriptor rows [nph_cap][12]  |  ones [batch][84]
-// lim_on: the table is in use (hsddp_limits_clear only drops the flag; the next set starts from NaN again).  lim_table (hsddp_hip.hip) hands the
-// launch helpers the resolved table while it is in use and the window has a whole-body phase, and null otherwise - then exactly the kernels of
-// before are launched.  `ones` is the scale table of the _lim kernels while hsddp_weights.h has none set; ws_on and d_ws are not touched.
+// lim_on: the table is in use (hsddp_limits_clear only drops the flag; the next set starts from NaN again).  Whether a launch reads the
+// resolved table is roll_pick's rule (roll_pick.hpp: in use, fp64, a whole-body phase and no kinodynamic one in the window); otherwise exactly the
+// kernels of before are launched.  `ones` is the scale table the rule names for the _lim kernels while hsddp_weights.h has none set; ws_on and d_ws are not touched.
 #pragma once
 #include "hsddp_limits.h"
 #include "limits.hpp"

@@ -5,7 +5,7 @@
 // nph_cap and batch are fixed at hsddp_create - and handed to the _tdh rollout kernels as an argument.  td_own[phase] marks the phases with heights of
 // their own, td_n counts them.  Invariant while td_n > 0: the rows of every other phase hold that phase's ground_height, so the _tdh kernels read the
 // table for every whole-body terminal knot and a phase without heights of its own still computes foot_z - ground_height.  td_n == 0: the table is
-// not read at all, launch_rollout_list launches the kernels it always launched.
+// not read at all, roll_pick (roll_pick.hpp) names the kernels that were always launched.
 #pragma once
 #include "hsddp_touchdown.h"
 #include "touchdown.hpp"

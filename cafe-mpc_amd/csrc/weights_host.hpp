@@ -3,8 +3,8 @@
 //
 // Storage: ONE device block per handle, d_ws = [2][batch][84] doubles, allocated by the first hsddp_weights_set and never again: the first half is
 // the table the _pw kernels read, the second half stages a host source for k_pack_weights.  ws_on: the table is in use (hsddp_weights_clear only
-// drops the flag; the next set starts from 1.0 again).  ws_table (hsddp_hip.hip) hands the launch helpers the table while it is in use and the
-// window has a whole-body phase, and null otherwise - then exactly the kernels of before are launched.
+// drops the flag; the next set starts from 1.0 again).  Whether a launch reads it is roll_pick's rule (roll_pick.hpp: in use, fp64, a
+// whole-body phase and no kinodynamic one in the window); otherwise exactly the kernels of before are launched, with no table.
 //
 // Touchdown heights: k_rollout_pw and k_rollout_quad_term_pw have them compiled in and read d_tdh for every whole-body terminal knot.  While no
 // phase has heights of its own (td_n == 0) ws_tdh_ready keeps that table filled with every phase's ground_height for the CURRENT window

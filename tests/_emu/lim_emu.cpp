@@ -24,7 +24,7 @@ static std::vector<double> lim_resolve(const hsddp_handle* h, const double* user
     return res;
 }
 
-// the launch rule of launch_rollout_lim / launch_lq (hsddp_hip.hip): with limits every whole-body running knot runs the LIM program with row (phase, b)
+// the launch rule of roll_pick / lq_pick (roll_pick.hpp): with limits every whole-body running knot runs the LIM program with row (phase, b)
 // of the resolved table and a scale row (ones while no scales are set); the one-wave terminal program is the scaled one with the heights compiled in
 static void lim_chain(hsddp_handle* h, const std::vector<PhaseDev>& ph, WbCore& L, int first, int b, double eps, const OptDev& o, SlotOut so, const double* ws, const double* res) {
     for (int pj = first; pj < h->nph && !ph[pj].shooting; pj++) {

@@ -8,7 +8,7 @@
 #define WEIGHTS_HOST_ONLY 1
 #include "weights.hpp"
 
-// the launch rule of launch_rollout_list / launch_lq (hsddp_hip.hip): with scales every whole-body knot runs the PW program with row b of the table;
+// the launch rule of roll_pick / lq_pick (roll_pick.hpp): with scales every whole-body knot runs the PW program with row b of the table;
 // the terminal programs have the touchdown heights compiled in and read the phase's ground_height from a table when the phase has none of its own
 static void pw_chain(hsddp_handle* h, const std::vector<PhaseDev>& ph, WbCore& L, int first, int b, double eps, const OptDev& o, SlotOut so, const double* ws) {
     for (int pj = first; pj < h->nph && !ph[pj].shooting; pj++) {

@@ -14,6 +14,8 @@ The reference is tests/lim_common.LimitedOracle: B single-problem oracle handles
 5. ABI: the header against the ctypes mirror, every refusal rule, pack_limits, the rules and the loops as a stand-alone program under ASan + UBSan.
 6. test_make_resources_lim: every _lim kernel at its twin's waves per SIMD and LDS size, none with scratch, the committed record is this build's.
 7. Build: the C++ mirror compiles.
+8. test_launch_rule_matches_its_transcription_and_is_clean_under_the_sanitizers: which rollout and LQ kernels a launch uses (roll_pick.hpp), every
+   switch setting against a transcription of the launch helpers' former branches, as a stand-alone program under ASan + UBSan.
 
 Real HIP execution: tests/test_limits_gpu.py."""
 import ctypes as C
@@ -249,6 +251,19 @@ def test_rules_and_loops_walk_clean_under_asan_and_ubsan(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout, r.stderr)
     assert int(r.stdout.split()[1]) > 1000
+
+
+def test_launch_rule_matches_its_transcription_and_is_clean_under_the_sanitizers(tmp_path):
+    """tests/cpp/roll_pick_table.cpp, a stand-alone program around the rule that picks the rollout and LQ kernels of a launch
+    (cafe-mpc_amd/csrc/roll_pick.hpp): all 2^10 switch settings field by field against a transcription of the branches the launch helpers had before,
+    exactly the eleven + four kernels reachable, the six kernels of before without tables and heights, the inert combinations inert, the timing suffix
+    the kernel's.  Compiled with -fsanitize=address,undefined and run directly; it has to finish clean."""
+    exe = str(tmp_path / "roll_pick_table")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-I" + CSRC, os.path.join(ROOT, "tests", "cpp", "roll_pick_table.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    print(r.stdout + r.stderr)
+    assert r.returncode == 0 and "roll_pick_table: clean" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
 
 
 def _resources(text):

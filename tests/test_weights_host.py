@@ -10,7 +10,8 @@ The reference is tests/pw_common.StackedOracle: B single-problem oracle handles 
 3. test_pack_host_build_matches_numpy: k_pack_weights' loop bit for bit - first call, later ranges, a device-style source.
 4. ABI: the header against the ctypes mirror, every refusal rule, the rules and the loop as a stand-alone program under ASan + UBSan.
 5. test_make_resources_pw: every _pw kernel at its twin's waves per SIMD and LDS size; registers, spills and scratch are printed beside the twin's.
-6. Build: the C++ mirror compiles; the gfx950 code objects of every translation unit the parent has keep their .text, .rodata and symbol list.
+6. Build: the C++ mirror compiles; the gfx950 code objects of every translation unit the parent has keep their .text, .rodata and symbol list
+   (nine units across the change that added the scales; all eleven across the one that wrote the launch rule down in roll_pick.hpp).
 
 Real HIP execution: tests/test_weights_gpu.py."""
 import ctypes as C
@@ -235,10 +236,16 @@ UNITS = {"hsddp_quad.hip": QUAD_FLAGS, "hsddp_sub.hip": ["-DHS_SUB_SEPARATE"], "
          "hsddp_tdh.hip": QUAD_FLAGS + ["-DHS_TDH_SEPARATE"], "hsddp_hip.hip": SEPARATE}
 
 
+_HASHED = {}
+
+
 def section_hashes(unit, flags, tmp, csrc=CSRC):
     """sha256 of .text, .rodata and the symbol list (llvm-readelf -sW without the __hip_cuid_ line and the index column, sorted) of the unit's gfx950
     code object, compiled with the Makefile's flags plus --cuda-device-only -c."""
     import hashlib
+    key = (unit, tuple(flags), csrc)
+    if key in _HASHED:      # (the two tests below hash the same build: each unit is compiled once)
+        return _HASHED[key]
     base = os.path.join(str(tmp), unit)
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I../../include", "-Wno-unused-value", "-DROLL_WPE=2", "--cuda-device-only", "-c", *flags,
                            unit, "-o", base + ".bun"], cwd=csrc, stderr=subprocess.DEVNULL)
@@ -250,6 +257,7 @@ def section_hashes(unit, flags, tmp, csrc=CSRC):
     syms = subprocess.run([LLVM + "/llvm-readelf", "-sW", base + ".co"], capture_output=True, text=True, check=True).stdout
     rows = sorted(" ".join(l.split()[1:]) for l in syms.splitlines() if "__hip_cuid_" not in l and len(l.split()) >= 8)
     out[".syms"] = hashlib.sha256("\n".join(rows).encode()).hexdigest()
+    _HASHED[key] = out
     return out
 
 
@@ -266,5 +274,26 @@ def test_code_objects_of_the_parent_s_translation_units_are_untouched(tmp_path):
     assert sorted({u for u, _ in rec}) == sorted(UNITS) and len(rec) == 3 * len(UNITS)
     with ThreadPoolExecutor(max_workers=min(len(UNITS), os.cpu_count() or 1, 16)) as ex:
         got = dict(zip(UNITS, ex.map(lambda u: section_hashes(u, UNITS[u], tmp_path), UNITS)))
+    for (unit, sec), h in rec.items():
+        assert got[unit][sec] == h, (unit, sec)
+
+
+ALL_UNITS = dict(UNITS, **{"hsddp_pw.hip": QUAD_FLAGS + ["-DHS_PW_SEPARATE"], "hsddp_lim.hip": QUAD_FLAGS + ["-DHS_LIM_SEPARATE"]})
+
+
+def test_code_objects_of_all_eleven_translation_units_are_untouched_by_the_launch_records(tmp_path):
+    """profiles/r20pick_section_hashes.txt: the same record for all eleven translation units across the change that moved the choice of rollout and LQ
+    kernel into roll_pick.hpp and the launchers' arguments into records (host code only).  Both columns agree in every row, and this build's code
+    objects still hash to them: no kernel's code, constants or symbols moved."""
+    rec = {}
+    for line in open(os.path.join(ROOT, "profiles", "r20pick_section_hashes.txt")):
+        if line.startswith("#") or not line.strip():
+            continue
+        unit, sec, parent, this, verdict = line.split()
+        assert parent == this and verdict == "identical", line
+        rec[(unit, sec)] = parent
+    assert sorted({u for u, _ in rec}) == sorted(ALL_UNITS) and len(ALL_UNITS) == 11 and len(rec) == 3 * len(ALL_UNITS)
+    with ThreadPoolExecutor(max_workers=min(len(ALL_UNITS), os.cpu_count() or 1, 16)) as ex:
+        got = dict(zip(ALL_UNITS, ex.map(lambda u: section_hashes(u, ALL_UNITS[u], tmp_path), ALL_UNITS)))
     for (unit, sec), h in rec.items():
         assert got[unit][sec] == h, (unit, sec)
